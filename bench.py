@@ -1,15 +1,18 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: 6-view frames/s through the EVA-02 ViT-L + ToC3D token-compression backbone.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]            (N > 1: launched by torch.distributed.run)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]      (N > 1: launched by torch.distributed.run)
 
 One "step" = one pass of the hot path over one synthetic 6-view frame per rank: patch-embed -> 24 blocks with the
 three query-guided scorers and per-window token compression (ToC3D_faster, ratios 0.5/0.4/0.3, 6 x 3 x 320 x 800,
 BASELINE.json configs[1]) -> CPFPN neck; with N > 1 ranks every rank processes its own frame (weak scaling, no
 data-path collective inside the backbone) and the per-frame neck features are all-gathered over RCCL where the
 detection head would consume them.  Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON
-line (contract in the task statement) including `roofline` for the dominant kernel (the bf16 MFMA GEMM behind
-every linear layer) and `cpu_baseline` (the oracle's eager-PyTorch fp32 port, timed on the host cores).
+line: the headline (metric, value, unit, higher_is_better, dtype, ms_per_step of the K timed steps).  With --full the
+line also carries `roofline` for the dominant kernel (the bf16 MFMA GEMM behind every linear layer), the box
+calibration, the side legs, the norm2-fold A/B and `cpu_baseline` (the oracle's eager-PyTorch fp32 port, timed on
+the host cores).  --dump-outputs DIR writes what the last timed step computed as .npy files (inputs and weights are
+seeded: the same arguments give the same inputs on every run).
 """
 from __future__ import annotations
 
@@ -70,7 +73,9 @@ def cpu_baseline(cfg, sd_cpu, inp, name):
     # torch.set_num_threads(256)): 188.7 / 189.0 / 186.3 s per frame = 0.0053 frames/s against 3.9-4.3 s = 0.24 frames/s on 32 threads -- eager PyTorch on 6000-row ops
     # collapses under a 256-way fork/join per op (and the run takes 25 minutes).  The baseline a reader would tune is the 32-thread one: that is `value`, `cores` says so,
     # `host_cores` is the box's count, and the all-cores figure is quoted in `all_cores_note`.
-    torch.set_num_threads(min(ncpu, 32))
+    # (no more threads than this process may run on: the CPUs it is pinned to, and OMP_NUM_THREADS where that is set)
+    usable = min(len(os.sched_getaffinity(0)), int(os.environ.get("OMP_NUM_THREADS") or ncpu))
+    torch.set_num_threads(min(usable, 32))
     ts = []
     with torch.no_grad():
         warm = dict(inp, x=inp["x"][:1], gumbel=[g[:1] for g in inp["gumbel"]])
@@ -85,6 +90,43 @@ def cpu_baseline(cfg, sd_cpu, inp, name):
             "sample": f"median of 3 frames (6 views @ 800x320 each) of the {name} workload after a 1-view warm-up, eager PyTorch fp32 oracle",
             "all_cores_note": "threads capped at 32: with all 256 host threads the same protocol reads 0.0053 frames/s (188 s per frame; measured in round 6, "
                               "profiles/r06_cpu_baseline_all_cores.json) against 0.24 on 32 -- eager PyTorch does not scale past a few tens of threads on these ops"}
+
+
+DUMP_BUDGET_BYTES = 63_000_000          # (the .npy headers stay well inside 64 MB)
+
+
+def dump_outputs(out_dir, outs):
+    """--dump-outputs: the arrays the timed step handed its caller -- the neck features and the backbone's return (features, per-stage token masks, kept /
+    dropped token indices) -- as DIR/<name>.npy, floats in float32, indices in float64 (exact).  At most DUMP_BUDGET_BYTES in all: an array that does not
+    fit its share is replaced by a fixed sample of its flattened elements (seeded by the name, sorted positions), the same on every run and build."""
+    import zlib
+
+    import numpy as np
+    bb = outs["backbone"]
+    arrays = {"neck_features": outs["neck"]}
+    if isinstance(bb, dict):
+        arrays.update(bb)
+    else:
+        arrays.update(bb.img_feats)
+        for key in ("token_masks", "keep_idx", "drop_idx"):
+            for s, t in enumerate(getattr(bb, key) or []):
+                arrays[f"{key}_stage{s}"] = t
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        host[name] = t.cpu().double().numpy() if not t.is_floating_point() else t.float().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    left, todo = DUMP_BUDGET_BYTES, sorted(host, key=lambda n: host[n].nbytes)
+    for i, name in enumerate(todo):
+        a = host[name]
+        share = left // (len(todo) - i)
+        if a.nbytes > share:
+            k = share // a.itemsize
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(a.size, size=k, replace=False))
+            a = a.reshape(-1)[idx]
+            print(f"[bench] --dump-outputs: {name} {tuple(host[name].shape)} sampled to {k} elements", file=sys.stderr)
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        left -= a.nbytes
 
 
 def read_clocks():
@@ -537,14 +579,25 @@ def main():
     ap.add_argument("--no-batched", action="store_true", help="skip the short run with two frames per forward that is reported beside the headline")
     ap.add_argument("--no-parity-path", action="store_true", help="skip the short run of the strict-parity fp32 (exact-f32 MFMA) path that is reported beside the headline")
     ap.add_argument("--no-breakdown", action="store_true")
-    ap.add_argument("--reps", type=int, default=3, help="the K-step timed region is repeated this many times; value / ms_per_step are the MEDIAN repetition (every one is listed)")
+    ap.add_argument("--reps", type=int, default=None, help="the K-step timed region is repeated this many times (default 1, with --full 3); value / ms_per_step are "
+                    "the MEDIAN repetition (every one is listed)")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the short legs of BASELINE.json configs 3 (dense EVA_ViT) and 4 (ToC3D_faster @ 6x1600x640)")
     ap.add_argument("--no-ab", action="store_true", help="skip the interleaved in-run A/B of the norm2 fold (the shipped default against schedule=dict(fold_norm2=False))")
     ap.add_argument("--no-calibration", action="store_true", help="skip the box calibration (GEMM yardstick, copy bandwidth, clocks) in front of the timed region")
     ap.add_argument("--packed", default=None, help="a packed-weight file written BEFORE the launch (python bench.py --write-packed PATH, or model.save_packed): every rank "
                     "restores it (toc3d_amd/packed_io.py) instead of rank 0 drawing and packing a synthetic checkpoint while the other ranks wait at a barrier")
     ap.add_argument("--write-packed", default=None, help="draw the synthetic checkpoint, write the packed weights to this path and exit (one process, before an N > 1 launch)")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline: box calibration, per-kernel roofline, the side legs (batched, parity "
+                    "paths, other configs), the norm2-fold A/B and the CPU baseline, and --reps 3 by default; the --no-* options switch single parts off again. "
+                    "Without it a run sets up, warms up, times --steps steps once and prints the headline line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed region, write what the last timed step computed (rank 0's neck features "
+                    "and the backbone outputs they came from) to DIR/<name>.npy in float32 / float64")
     args = ap.parse_args()
+    if not args.full:
+        args.no_calibration = args.no_breakdown = args.no_batched = args.no_parity_path = True
+        args.no_other_configs = args.no_ab = args.no_cpu_baseline = True
+    if args.reps is None:
+        args.reps = 3 if args.full else 1
 
     rank = int(os.environ.get("RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", 1))
@@ -639,6 +692,8 @@ def main():
     gather = tdist.FeatureGather((V, 256, h, w), dev) if world > 1 and not args.sync_gather else None
     gathered = torch.empty(world, V, 256, h, w, dtype=torch.bfloat16, device=dev) if world > 1 and args.sync_gather else None
 
+    last_outputs = {}                                        # what the most recent forward returned (aliases the workspace): --dump-outputs
+
     def one_frame(d):
         if is_toc:
             out = model(d["x"], temp_queries=d["temp_queries"], prev_exists=True, temp_ref_points=d["temp_ref_points"],
@@ -646,8 +701,10 @@ def main():
                         ego_pose_inv=d["ego_pose_inv"], gumbel_noise=d["gumbel"])
             feat = out.img_feats["last_feat"]
         else:
-            feat = model(d["x"])["last_feat"]
+            out = model(d["x"])
+            feat = out["last_feat"]
         n0 = neck([feat])[0]
+        last_outputs["backbone"], last_outputs["neck"] = out, n0
         if world > 1 and my_frames:
             if gather is not None:
                 gather.submit(n0)
@@ -683,6 +740,8 @@ def main():
     for _ in range(max(1, args.reps) - 1):                   # the same region again (no further warm-up): a 0.25 s region moves with the box's clocks
         runs.append(tdist.timed_steps(step, args.steps, 0, dev, finish=fin))
     elapsed = sorted(runs)[len(runs) // 2]
+    if args.dump_outputs and rank == 0 and last_outputs:
+        dump_outputs(args.dump_outputs, last_outputs)       # the timed region ended in a device sync: the buffers hold the last timed step
 
     last = step()
     torch.cuda.synchronize()

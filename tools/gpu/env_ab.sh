@@ -3,7 +3,7 @@ export PYTHONUNBUFFERED=1
 cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out
 N=${N:-3}
-B="python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-breakdown --no-batched --no-parity-path --no-other-configs --no-ab --no-calibration $BENCH_ARGS"
+B="python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-breakdown --no-batched --no-parity-path --no-other-configs --no-ab --no-calibration $BENCH_ARGS"
 for i in $(seq 1 $N); do
   for V in $VALS; do
     env $VAR=$V $B 2>/dev/null | python -c "

@@ -5,7 +5,7 @@ mkdir -p gpurun_out
 N=${N:-5}
 TESTS=${TESTS:-}
 if [ -n "$TESTS" ]; then timeout 1200 python -m pytest $TESTS -m gpu -q --tb=short -p no:cacheprovider -x 2>&1 | tail -4; fi
-B="python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-breakdown --no-batched --no-parity-path --no-other-configs --no-ab --no-calibration $BENCH_ARGS"
+B="python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-breakdown --no-batched --no-parity-path --no-other-configs --no-ab --no-calibration $BENCH_ARGS"
 for i in $(seq 1 $N); do
   for L in libtoc3d_prev.so libtoc3d_gfx950.so; do
     TOC3D_LIB=$L $B 2>/dev/null | python -c "

@@ -1,11 +1,14 @@
-# default bench line, whole GPU suite, smoke
-mkdir -p gpurun_out
-export PYTHONUNBUFFERED=1
-cd "$GRAFT_REPO_ROOT"
-T0=$(date +%s); timeout 1500 python bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err; echo "default bench.py wall time: $(( $(date +%s) - T0 )) s"; tail -3 gpurun_out/bench.err
+# full bench line (bench.py --full), whole GPU suite, smoke; every step stops the script when it fails
+#   OUT=<directory for the results> bash tools/gpu/suite_bench.sh
+set -eo pipefail
+: "${OUT:?set OUT to the directory that collects the results}"
+mkdir -p "$OUT"
+export OUT="$(cd "$OUT" && pwd)" PYTHONUNBUFFERED=1
+cd "$(dirname "$0")/../.."
+T0=$(date +%s); timeout -k 10 1500 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench.py --full wall time: $(( $(date +%s) - T0 )) s"; tail -3 "$OUT/bench.err"
 python - <<'PY'
-import json
-d = json.loads(open('gpurun_out/bench.json').read().strip().splitlines()[-1])
+import json, os
+d = json.loads(open(os.path.join(os.environ['OUT'], 'bench.json')).read().strip().splitlines()[-1])
 print(round(d['value'], 1), 'frames/s', d['repetitions']['ms_per_step_each'])
 print('calibration', d.get('calibration'))
 r = d['roofline']; print('roofline', {k: r[k] for k in ('frac', 'frac_issued', 'frac_event_timed', 'avg_launch_ms', 'avg_launch_ms_event_timed', 'event_pair_cost_ms', 'traffic')})
@@ -15,5 +18,5 @@ print('batched', d.get('batched', {}).get('value'), 'parity', d.get('parity_path
 print('cpu', d.get('cpu_baseline'), d.get('cpu_baseline_configs0'))
 print('other', [(o['config'][:20], round(o['value'], 1)) for o in d.get('other_configs', [])])
 PY
-timeout 3000 python -m pytest tests -m gpu -q --tb=short -p no:cacheprovider 2>&1 | tail -15 > gpurun_out/pytest.log; tail -8 gpurun_out/pytest.log
-python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -4
+rc=0; timeout -k 10 3000 python -m pytest tests -m gpu -q --tb=short -p no:cacheprovider 2>&1 | tail -15 > "$OUT/pytest.log" || rc=$?; tail -8 "$OUT/pytest.log"; [ $rc -eq 0 ]
+timeout -k 10 600 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -4
