@@ -13,7 +13,7 @@ import torch
 
 import toc3d_amd
 from oracle import toc3d_oracle as O
-from toc3d_amd import configs, synth
+from toc3d_amd import configs, lib, synth
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -641,6 +641,25 @@ def test_fp32x3_on_planes_is_bit_identical_to_the_in_kernel_split(name, prev):
             o = run_toc3d(m, inp, prev) if synth.is_toc3d(cfg) else m(inp["x"].to(DEV))
         outs.append((o.img_feats["last_feat"] if synth.is_toc3d(cfg) else o["last_feat"]).clone())
     assert torch.equal(outs[0], outs[1]), f"max abs difference {(outs[0] - outs[1]).abs().max().item():.3e}"
+    if name != "toc3d_faster":
+        return
+    # the shipped fp32x3 table was tuned on planes and names tiles that exist on planes only (lib.X3_PLANES_ONLY_VARIANTS): with x3_planes off, a model that loads it
+    # must still run -- load_tuning leaves those picks out -- and return the bits of the forward that never saw a table
+    import json
+    path = os.path.join(os.path.dirname(os.path.abspath(toc3d_amd.__file__)), "tuned", "toc3d_faster_320x800_fp32x3.json")
+    table = {tuple(k): v for k, v in json.load(open(path))["table"]}
+    assert any(v % 1000 % 100 in lib.X3_PLANES_ONLY_VARIANTS for v in table.values()), "the leg below needs a table that names planes-only tiles"
+    m = toc3d_amd.build_backbone(dict(cfg, precision="fp32x3", schedule=dict(x3_planes=False, x3_attention=False, attn_rot=False)))
+    m.load_state_dict(sd, strict=True)
+    m = m.to(DEV).eval()
+    m.autotune = False                       # every tile the forward launches comes from the table (or is the heuristic one)
+    m.load_tuning(path)
+    kept = dict(m._tuned)
+    assert kept and all(table[k] == v and v % 1000 % 100 not in lib.X3_PLANES_ONLY_VARIANTS for k, v in kept.items()) and len(kept) < len(table)
+    for _ in range(3):
+        o = run_toc3d(m, inp, prev)
+    assert any(k in kept and v != 0 for k, v in m._tuned.items()), "the forward must launch shapes the table holds"
+    assert torch.equal(o.img_feats["last_feat"], outs[0]), "x3_planes=False with the shipped table loaded: not the bits of the untuned forward"
 
 
 def test_fp32x3_attention_products_stay_parity_grade():

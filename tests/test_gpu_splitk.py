@@ -33,7 +33,9 @@ def _bits(t):
 
 
 @pytest.mark.parametrize("name,dt,tdt", DT)
-@pytest.mark.parametrize("M,N,K", [(777, 640, 512), (2178, 1024, 2752), (300, 1024, 1024)])
+# (the last five: row tails of the tile table -- one row, tiles 0, 1 of a slab valid and the rest past M, an odd tile partial, one row past a 256-row block;
+# tests/epilogue_cases.py derives the classes)
+@pytest.mark.parametrize("M,N,K", [(777, 640, 512), (2178, 1024, 2752), (300, 1024, 1024), (1, 640, 512), (24, 640, 512), (59, 640, 512), (216, 640, 512), (257, 640, 512)])
 def test_splitk_residual_epilogues_match_the_unsplit_launch(name, dt, tdt, M, N, K):
     pdt = lib.F32 if dt == lib.F32X3 else dt
     A, W, b = rnd(M, K, seed=1), rnd(N, K, seed=2, scale=K ** -0.5), rnd(N, seed=3).to(DEV)

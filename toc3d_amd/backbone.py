@@ -621,7 +621,12 @@ class _BackboneBase(nn.Module):
         with open(path) as f:
             d = json.load(f)
         if d.get("precision") == self.precision:
-            self._tuned.update({tuple(k): int(v) for k, v in d["table"]})
+            tab = {tuple(k): int(v) for k, v in d["table"]}
+            if self.precision == "fp32x3" and not self._x3p:
+                # the shipped fp32x3 tables were tuned with the operands in planes and name tiles that only exist on planes (csrc/gemm_kernels.h launch_epi_x: the
+                # 96- / 160-row tiles and the phased ones): with x3_planes off those launches would be refused -- such shapes fall back to first-use tuning / the heuristic
+                tab = {k: v for k, v in tab.items() if v % 1000 % 100 not in lib.X3_PLANES_ONLY_VARIANTS}
+            self._tuned.update(tab)
 
     # -- launch sequences -----------------------------------------------------------------------------
     def _stem_im2col(self, plan, img):

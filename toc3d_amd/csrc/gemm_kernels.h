@@ -522,9 +522,11 @@ TOC3D_DEV void gemm_epilogue(const GemmArgs& a, f32x4 (&acc)[MT][NT], int row0, 
     constexpr bool PAIR_OK = sizeof(T) == 4 && epi_act_copy(EPI) && epi_is_residual(EPI) && MT % 2 == 0;
     float keep[PAIR_OK ? NT : 1][4];
     float* keep_row = nullptr;
+    // wave-uniform: the lane-group exchange of store_planes_pair needs both partners, so every 16-column tile of the wave lies wholly inside or wholly outside N (a
+    // per-lane test let an even lane group pair up with a neighbour that had skipped its columns when N % 8 == 4: the odd row tile's last 4 columns were never stored)
     bool pair = PAIR_OK && a.out_planes;
 #pragma unroll
-    for (int j = 0; j < NT; ++j) pair = pair && (nok[j] == 0 || nok[j] == 4);
+    for (int j = 0; j < NT; ++j) pair = pair && (col0 + j * 16 >= a.N || col0 + j * 16 + 16 <= a.N);
     (void)keep; (void)keep_row;
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
@@ -535,6 +537,7 @@ TOC3D_DEV void gemm_epilogue(const GemmArgs& a, f32x4 (&acc)[MT][NT], int row0, 
 #pragma unroll
                     for (int j = 0; j < NT; ++j)
                         if (nok[j] == 4) store_planes4(keep_row, col0 + j * 16 + g * 4, keep[j]);
+                    keep_row = nullptr;                  // stored: a later odd tile past M must not store it again
                 }
             }
             continue;
@@ -620,6 +623,9 @@ TOC3D_DEV void gemm_epilogue(const GemmArgs& a, f32x4 (&acc)[MT][NT], int row0, 
                         gq[i * G + j] = sq;
                     }
                 }
+            }
+            if constexpr (PAIR_OK) {
+                if (pair && (i & 1)) keep_row = nullptr;     // the pair has left
             }
         } else {
             act_row(i, row);

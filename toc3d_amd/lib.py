@@ -24,6 +24,8 @@ NO_FUSED = (None, 0, None, 0, None, 0, 0.0, None, 0, None)     # the ten extra a
 # GEMM tile variants (mod 100; + 100 / 200 / 300 select the XCD order at run time) the product library carries: every variant the autotuner may pick or a
 # shipped table names (csrc/gemm_kernels.h launch_epi).
 PRODUCT_VARIANTS = (1, 8, 9, 10, 13, 14, 15, 16, 17, 19, 22, 24, 26, 27, 28, 29, 30, 33, 45, 47, 49, 51, 52, 53, 54, 55, 56, 57, 58, 59, 60, 61, 62, 63, 64, 65, 66)
+# ... of which the bf16 x 3 forms exist only with BOTH operands as (hi, lo) planes (TOC3D_DTYPE_F32X3P / F32X3WA): the 96- / 160-row tiles and the phased big tiles
+X3_PLANES_ONLY_VARIANTS = (54, 55, 56, 57, 58, 59, 60, 61, 62, 63)
 
 
 def has_variant(v: int) -> bool:
