@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define TOC3D_ABI_VERSION 8   /* bumped whenever entry points are added or changed; toc3d_amd/lib.py checks it before binding symbols */
+#define TOC3D_ABI_VERSION 9   /* bumped whenever entry points are added or changed; toc3d_amd/lib.py checks it before binding symbols */
 
 #define TOC3D_OK 0
 #define TOC3D_ERR_ARG (-1)
@@ -496,6 +496,42 @@ int toc3d_nchw_to_rows(int dtype, const float* x, void* out, int64_t ldo, int64_
 int toc3d_mln_apply(int dtype, const float* x, const float* gamma, const float* beta, int64_t M, int64_t E, float* out, void* out_act, int64_t ld_act,
                     toc3d_stream_t stream);
 int toc3d_se_gate(const float* pos, const float* se, float* out, int64_t n, toc3d_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * StreamPETR temporal decoder (utils/petr_transformer.py: PETRTemporalTransformer :431-517, PETRTransformerDecoder :376-428,
+ * PETRTemporalDecoderLayer._forward :714-760; called at dense_heads/streampetr_head.py:580).  The projections and the FFN run on toc3d_linear;
+ * these are the kernels between them (csrc/mha.hip).
+ * toc3d_mha_attention: the core of torch.nn.MultiheadAttention as PETRMultiheadAttention.forward calls it (petr_transformer.py:327-332; mmcv's
+ *   MultiheadAttention of self_attn likewise) at eval -- no mask, no dropout -- on ALREADY PROJECTED rows: q act [B*Nq, ldq], k / v act [B*Nk, ldk / ldv],
+ *   out act [B*Nq, ldo], each heads * 32 wide, head-major; out = softmax(q.k^T * scale).v per (sample, head).  head_dim must be 32 (else
+ *   TOC3D_ERR_UNSUPPORTED).  dtype = TOC3D_DTYPE_BF16 (bf16 buffers, products on v_mfma_f32_16x16x32_bf16, f32 softmax and accumulation) or
+ *   TOC3D_DTYPE_F32X3 (plain f32 buffers -- what the x3 GEMMs' bias epilogue emits and their A operand reads; both contractions, P included, as bf16 x 3
+ *   products on (hi, lo) splits made in registers); other dtypes: TOC3D_ERR_UNSUPPORTED.  Keys are streamed in chunks of 32 with a running (max, sum, O)
+ *   per query (exp2-based online softmax, exact up to rounding); Nq and Nk are arbitrary (tail rows and keys are masked in the kernel) and rows of `out`
+ *   past B*Nq are never written.  The keys of a query tile are cut over the wavefronts of ONE workgroup and the partial states are added in wavefront
+ *   order: no atomics, no workspace, results bit-identical from run to run.  Leading dimensions are multiples of 8 (bf16) / 4 (f32) elements,
+ *   buffers 16-byte aligned.
+ * toc3d_mha_attention_ex: the same with a second key / value segment: the key list of sample b is rows [b*Nk, (b+1)*Nk) of (k, v) followed by rows
+ *   [b*Nk2, (b+1)*Nk2) of (k2, v2) -- the decoder's self-attention keys are torch.cat([query, temp_memory]) (:717-718) and the temp_memory part is projected
+ *   once per frame for all layers, into another buffer (Nk or Nk2 may be 0).  Bit-identical to one launch on the concatenated rows.
+ *   Work split (csrc/mha.hip): 32 queries per workgroup, 8 wavefronts -- the form kept of the four measured (profiles/decoder_mha_variants.txt).
+ * toc3d_add_layernorm_pos: the `norm` steps of a layer (:737-739) with what follows folded in.  x f32 [M, ldx] (the residual epilogue's output) ->
+ *   out f32 = LayerNorm(x; gamma, beta, eps) (the residual stream) and, each optional (NULL), out_act act = out, out_act_pos act = out + pos (pos f32
+ *   [M, ldp]: `query + query_pos`, :311-312) -- the A operands of the next projections -- and out2 f32 = LayerNorm(out; gamma2, beta2, eps), the decoder's
+ *   shared post_norm (:413-425) written straight into the layer's slice of the stacked outs_dec.  dtype BF16 or F32 (act type).  One wavefront per
+ *   row, E <= 1024, two-pass variance.
+ * toc3d_add_pos_rows: x f32 [M, ldx] -> out_act act = x and / or out_act_pos act = x + pos: the decoder's inputs (tgt, memory + pos_embed,
+ *   temp_memory + temp_pos) in the form the projections read. */
+int toc3d_mha_attention(int dtype, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* out, int64_t ldo,
+                        int64_t B, int64_t Nq, int64_t Nk, int64_t heads, int64_t head_dim, float scale, toc3d_stream_t stream);
+int toc3d_mha_attention_ex(int dtype, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                           const void* k2, int64_t ldk2, const void* v2, int64_t ldv2, void* out, int64_t ldo,
+                           int64_t B, int64_t Nq, int64_t Nk, int64_t Nk2, int64_t heads, int64_t head_dim, float scale, toc3d_stream_t stream);
+int toc3d_add_layernorm_pos(int dtype, const float* x, int64_t ldx, const float* gamma, const float* beta, float eps, const float* pos, int64_t ldp,
+                            float* out, int64_t ldo, void* out_act, int64_t ld_act, void* out_act_pos, int64_t ld_act_pos,
+                            const float* gamma2, const float* beta2, float* out2, int64_t ldo2, int64_t M, int64_t E, toc3d_stream_t stream);
+int toc3d_add_pos_rows(int dtype, const float* x, int64_t ldx, const float* pos, int64_t ldp, void* out_act, int64_t ld_act, void* out_act_pos, int64_t ld_act_pos,
+                       int64_t M, int64_t E, toc3d_stream_t stream);
 
 /* Plain device-to-device copy as a kernel (recordable into a launch plan, unlike hipMemcpyAsync). */
 int toc3d_copy_bytes(void* dst, const void* src, int64_t nbytes, toc3d_stream_t stream);

@@ -1,7 +1,8 @@
-"""Registry surface: ``ToC3DEVAViT`` / ``EVA_ViT`` on mmdet's BACKBONES, ``CPFPN`` on NECKS.
+"""Registry surface: ``ToC3DEVAViT`` / ``EVA_ViT`` on mmdet's BACKBONES, ``CPFPN`` on NECKS, ``PETRTemporalTransformer`` on TRANSFORMER.
 
 The reference registers its classes with ``@BACKBONES.register_module()`` (``toc3d_eva_vit.py:25``,
-``eva_vit.py:270``) and ``@NECKS.register_module()`` (``cp_fpn.py:15``); configs name them by ``type=``.
+``eva_vit.py:270``), ``@NECKS.register_module()`` (``cp_fpn.py:15``) and ``@TRANSFORMER.register_module()``
+(``utils/petr_transformer.py:430``); configs name them by ``type=``.
 When mmdet is importable the same names are registered there (``force=True`` so this package can shadow the
 reference plugin); otherwise a shim registry with the same ``register_module()/build(cfg)`` API is used.
 """
@@ -35,12 +36,17 @@ try:  # pragma: no cover - mmdet is not installed in the build image
 except Exception:  # noqa: BLE001
     BACKBONES, NECKS = _ShimRegistry("backbone"), _ShimRegistry("neck")
     HAVE_MMDET = False
+try:  # pragma: no cover
+    from mmdet.models.utils.builder import TRANSFORMER
+except Exception:  # noqa: BLE001
+    TRANSFORMER = _ShimRegistry("transformer")
 
 
 def register_all():
     from .backbone import EVA_ViT, ToC3DEVAViT
+    from .decoder import PETRTemporalTransformer
     from .neck import CPFPN
-    for reg, cls in ((BACKBONES, ToC3DEVAViT), (BACKBONES, EVA_ViT), (NECKS, CPFPN)):
+    for reg, cls in ((BACKBONES, ToC3DEVAViT), (BACKBONES, EVA_ViT), (NECKS, CPFPN), (TRANSFORMER, PETRTemporalTransformer)):
         try:
             reg.register_module(name=cls.__name__, force=True, module=cls)
         except TypeError:
@@ -53,3 +59,7 @@ def build_backbone(cfg, **kw):
 
 def build_neck(cfg, **kw):
     return NECKS.build(cfg, **kw) if not HAVE_MMDET else NECKS.build(dict(cfg, **kw))
+
+
+def build_transformer(cfg, **kw):
+    return TRANSFORMER.build(cfg, **kw) if isinstance(TRANSFORMER, _ShimRegistry) else TRANSFORMER.build(dict(cfg, **kw))

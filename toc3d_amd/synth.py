@@ -363,3 +363,64 @@ def stack_frames(frames):
         else:
             out[k] = torch.cat([f[k] for f in frames], 0)
     return out
+
+
+# ---- StreamPETR temporal decoder (toc3d_amd.PETRTemporalTransformer) ------------------------------------------------------------------
+def decoder_cfg(embed_dims: int = 256, num_heads: int = 8, feedforward_channels: int = 2048, num_layers: int = 6) -> dict:
+    """The ``transformer=dict(...)`` block of the shipped configs (projects/configs/ToC3D/ToC3D_faster.py:114-139) at the given sizes."""
+    layer = dict(type="PETRTemporalDecoderLayer",
+                 attn_cfgs=[dict(type="MultiheadAttention", embed_dims=embed_dims, num_heads=num_heads, dropout=0.1),
+                            dict(type="PETRMultiheadAttention", embed_dims=embed_dims, num_heads=num_heads, dropout=0.1)],
+                 feedforward_channels=feedforward_channels, ffn_dropout=0.1, with_cp=True,
+                 operation_order=("self_attn", "norm", "cross_attn", "norm", "ffn", "norm"))
+    if embed_dims != 256:
+        # the layer's default ffn_cfgs pins embed_dims = 256 (petr_transformer.py:559-566): other widths name the FFN in full, as mmcv configs do
+        del layer["feedforward_channels"], layer["ffn_dropout"]
+        layer["ffn_cfgs"] = dict(type="FFN", embed_dims=embed_dims, feedforward_channels=feedforward_channels, num_fcs=2, ffn_drop=0.1,
+                                 act_cfg=dict(type="ReLU", inplace=True))
+    return dict(type="PETRTemporalTransformer",
+                decoder=dict(type="PETRTransformerDecoder", return_intermediate=True, num_layers=num_layers, transformerlayers=layer))
+
+
+DECODER_FULL = dict(embed_dims=256, num_heads=8, feedforward_channels=2048, num_layers=6)
+DECODER_TINY = dict(embed_dims=64, num_heads=2, feedforward_channels=128, num_layers=2)
+# shapes of the two fixtures (tools/gen_golden_decoder.py): B, num_query, num_propagated, memory entries, image tokens
+DECODER_FULL_SHAPE = dict(B=1, num_query=644, num_propagated=256, Nm=768, Nk=6000)
+DECODER_TINY_SHAPE = dict(B=2, num_query=24, num_propagated=8, Nm=16, Nk=48)
+
+
+def decoder_state_dict(sizes: dict, seed: int = 0):
+    """Seeded weights under the reference's state-dict names (``pts_bbox_head.transformer.*`` of a StreamPETR / ToC3D checkpoint)."""
+    g = torch.Generator().manual_seed(7000 + seed)
+    E, F, L = sizes["embed_dims"], sizes["feedforward_channels"], sizes["num_layers"]
+    r = lambda *s: torch.randn(*s, generator=g)
+    sd = {}
+    for i in range(L):
+        p = f"decoder.layers.{i}."
+        for a in range(2):
+            sd[p + f"attentions.{a}.attn.in_proj_weight"] = r(3 * E, E) * E ** -0.5
+            sd[p + f"attentions.{a}.attn.in_proj_bias"] = r(3 * E) * 0.1
+            sd[p + f"attentions.{a}.attn.out_proj.weight"] = r(E, E) * E ** -0.5
+            sd[p + f"attentions.{a}.attn.out_proj.bias"] = r(E) * 0.1
+        sd[p + "ffns.0.layers.0.0.weight"], sd[p + "ffns.0.layers.0.0.bias"] = r(F, E) * E ** -0.5, r(F) * 0.1
+        sd[p + "ffns.0.layers.1.weight"], sd[p + "ffns.0.layers.1.bias"] = r(E, F) * F ** -0.5, r(E) * 0.1
+        for n in range(3):
+            sd[p + f"norms.{n}.weight"], sd[p + f"norms.{n}.bias"] = 1.0 + 0.1 * r(E), 0.1 * r(E)
+    sd["decoder.post_norm.weight"], sd["decoder.post_norm.bias"] = 1.0 + 0.1 * r(E), 0.1 * r(E)
+    return sd
+
+
+def decoder_inputs(sizes: dict, shape: dict, seed: int = 0, with_temp: bool = True):
+    """Seeded decoder inputs shaped like the head's (streampetr_head.py:580, :424-453): ``tgt`` zero for the ``num_query`` fresh queries and non-zero for
+    the propagated ones, positional terms of order one, ``memory`` with a few heavy channels."""
+    g = torch.Generator().manual_seed(8000 + seed)
+    E, B, Nq, Nk, Nm = sizes["embed_dims"], shape["B"], shape["num_query"] + shape["num_propagated"], shape["Nk"], shape["Nm"]
+    r = lambda *s: torch.randn(*s, generator=g)
+    tgt = r(B, Nq, E)
+    tgt[:, :shape["num_query"]] = 0.0
+    memory = r(B, Nk, E)
+    memory[..., torch.arange(3) * (E // 3) + 1] *= 8.0
+    out = dict(memory=memory, tgt=tgt, query_pos=r(B, Nq, E), pos_embed=r(B, Nk, E), temp_memory=None, temp_pos=None)
+    if with_temp:
+        out["temp_memory"], out["temp_pos"] = r(B, Nm, E), r(B, Nm, E)
+    return out
