@@ -521,7 +521,8 @@ int toc3d_se_gate(const float* pos, const float* se, float* out, int64_t n, toc3
  *   shared post_norm (:413-425) written straight into the layer's slice of the stacked outs_dec.  dtype BF16 or F32 (act type).  One wavefront per
  *   row, E <= 1024, two-pass variance.
  * toc3d_add_pos_rows: x f32 [M, ldx] -> out_act act = x and / or out_act_pos act = x + pos: the decoder's inputs (tgt, memory + pos_embed,
- *   temp_memory + temp_pos) in the form the projections read. */
+ *   temp_memory + temp_pos) in the form the projections read.  One thread per element: M * E <= (2^31 - 1) * 256 (toc3d_relu_inplace: n likewise),
+ *   larger counts are refused. */
 int toc3d_mha_attention(int dtype, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* out, int64_t ldo,
                         int64_t B, int64_t Nq, int64_t Nk, int64_t heads, int64_t head_dim, float scale, toc3d_stream_t stream);
 int toc3d_mha_attention_ex(int dtype, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv,

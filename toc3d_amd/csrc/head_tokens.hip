@@ -152,6 +152,7 @@ int toc3d_head_frustum_inputs(int dtype, const float* img2lidar, const float* in
 
 int toc3d_relu_inplace(int dtype, void* x, int64_t n, toc3d_stream_t stream) {
     TOC3D_REQUIRE(x && n >= 0, "toc3d_relu_inplace: bad arguments");
+    TOC3D_REQUIRE(n <= ((1ll << 31) - 1) * 256, "toc3d_relu_inplace: too many elements for one launch");      // the grid below: at most 2^31 - 1 workgroups
     if (n == 0) return TOC3D_OK;
     dim3 grid((unsigned)((n + 255) / 256));
     if (dtype == TOC3D_BF16) toc3d_launch(relu_kernel<bf16_t>, grid, dim3(256), 0, as_stream(stream), (bf16_t*)x, n);

@@ -395,6 +395,8 @@ int toc3d_add_pos_rows(int dtype, const float* x, int64_t ldx, const float* pos,
                        int64_t M, int64_t E, toc3d_stream_t stream) {
     TOC3D_REQUIRE(x && (out_act || out_act_pos) && M >= 0 && E > 0 && ldx >= E, "toc3d_add_pos_rows: bad arguments");
     TOC3D_REQUIRE((!out_act || ld_act >= E) && (!out_act_pos || (pos && ldp >= E && ld_act_pos >= E)), "toc3d_add_pos_rows: an output lacks its inputs");
+    // one thread per element on a one-dimensional grid of at most 2^31 - 1 workgroups (a larger count would wrap in the cast below and cover a part of the rows only)
+    TOC3D_REQUIRE(E < (1ll << 31) && M <= ((1ll << 31) - 1) * 256 / E, "toc3d_add_pos_rows: too many elements for one launch");
     if (M == 0) return TOC3D_OK;
     dim3 grid((unsigned)((M * E + 255) / 256));
     if (dtype == TOC3D_BF16)
