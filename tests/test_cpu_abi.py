@@ -222,6 +222,33 @@ def test_copies_of_modules_drop_recorded_plans_and_packed_weights():
     parent.neck = n
     parent.load_state_dict({"neck." + k: v for k, v in n.state_dict().items()})
     assert n._ws == {} and n._packed is None
+    # the decoder and the head-token module keep the same protocol (toc3d_amd.plan.DerivedState): copies and pickles start without packed weights, workspaces,
+    # recorded plans, streams and the capture instrument; configuration is copied
+    from toc3d_amd import synth
+    dec = toc3d_amd.build_transformer(synth.decoder_cfg(**synth.DECODER_TINY))
+    tok = toc3d_amd.HeadTokenEmbedding(in_channels=64, embed_dims=64, depth_num=32)
+
+    def plant(mod):
+        mod._packed, mod._ws = {"w": lp}, {(1, 2, 3): {"buf": torch.zeros(2), "cplan": lp}}
+        if mod is dec:
+            dec._states, dec._pool, dec.capture = {(1, 2, 3, 0): {"cplan": lp, "warm": True}}, [lp], {"l0_norm0": torch.zeros(2)}
+            dec._sk_ws, dec._sk_ws_old = {(0, 0): torch.zeros(2)}, [torch.zeros(2)]
+    for mod in (dec, tok):
+        plant(mod)
+        for c in (copy.deepcopy(mod), pickle.loads(pickle.dumps(mod))):
+            assert c._packed is None and c._ws == {} and c.precision == mod.precision
+            assert all(torch.equal(a, b) and a.data_ptr() != b.data_ptr() for a, b in zip(c.state_dict().values(), mod.state_dict().values()))
+            if mod is dec:
+                assert c._states == {} and c._pool == [] and c.capture is None and c._sk_ws == {} and c._sk_ws_old == [] and c.launch_mode == dec.launch_mode
+    assert dec._pool == [lp] and dec.capture is not None and tok._ws != {}, "the originals keep theirs"
+    # new weights, loaded into the module itself, leave every derived attribute empty -- and keep what belongs to the instance (streams, the instrument)
+    m._stream_pool, m._sk_ws, m._sk_ws_old = [lp], {(0, 0): torch.zeros(2)}, [torch.zeros(2)]
+    n._ws, n._packed, n._stream_pool = {(1, 2, 3): {"launch": {7: {"cplan": lp}}}}, {"w": lp}, [lp]
+    for mod in (m, n, dec, tok):
+        mod.load_state_dict(mod.state_dict())
+        assert mod._packed is None and all(getattr(mod, k) == empty for k, empty in type(mod)._DERIVED.items()), type(mod).__name__
+    assert m._plans == {} and m._sk_ws == {} and m._sk_ws_old == [] and n._ws == {} and dec._ws == {} and dec._states == {} and dec._sk_ws == {} and tok._ws == {}
+    assert m._stream_pool == [lp] and n._stream_pool == [lp] and dec._pool == [lp] and dec.capture is not None
 
 
 def test_recording_lane_is_thread_local():
@@ -333,9 +360,11 @@ def test_backbone_survives_pickles_written_before_gumbel_seed_became_a_property(
     m.gumbel_seed = 1234
     st = m.__getstate__()
     st["gumbel_seed"] = st.pop("_gumbel_seed")                 # the old layout
+    del st["_forward_pre_hooks_with_kwargs"]                   # ... written by a torch that did not have this hook dictionary yet
     old = m.__class__.__new__(m.__class__)
     old.__setstate__(st)
     assert old.gumbel_seed == 1234 and "gumbel_seed" not in old.__dict__
+    assert old._forward_pre_hooks_with_kwargs == {}, "nn.Module.__setstate__ back-fills what old pickles lack (ADVICE.md, fourth item)"
     assert pickle.loads(pickle.dumps(m)).gumbel_seed == 1234 and copy.deepcopy(m).gumbel_seed == 1234
 
 
@@ -365,3 +394,83 @@ def test_splitk_workspace_is_sized_from_the_launched_tile_shape():
                 got = L.toc3d_linear_splitk_workspace_bytes(1000 * split + v, M, N)
                 assert got == want, (v, split, M, N, got, want)
     assert L.toc3d_linear_splitk_workspace_bytes(2060, 128, 128) < 0 and L.toc3d_linear_splitk_workspace_bytes(16, 128, 128) < 0      # no split-K form / not a split variant
+
+
+def test_gemm_launcher_hands_the_library_its_arguments_in_header_order():
+    """toc3d_amd.gemm.linear, the one launcher of the fused GEMM family: for every epilogue form the product uses, the exact positional tuple that reaches lib.call,
+    written out in the order of include/toc3d.h.  The expected tuples are what the launcher this one replaced (backbone.tuned_linear with its ten-slot `fused=`
+    tuple) passed for the same inputs -- recorded from that code, not from this one.  No device: lib.call is a recorder, the recording lane makes
+    lib.stream_ptr() a lane handle and sends an untabled shape down the "first seen while recording" branch (variant 0, no timing, nothing tabled)."""
+    import types
+
+    from toc3d_amd import gemm
+    L = lib
+    z = torch.zeros
+    A, W, bias, out, res, rep_out, act = z(4, 64), z(128, 64), z(128), z(4, 128), z(4, 128), z(2, 128), z(4, 128)
+    rep_index, ridx, rc = (z(4, dtype=torch.int32) for _ in range(3))
+    st, st2, c1, zeros, tab = z(64), z(64), z(128), z(256, dtype=torch.uint8), z(2, 2, 8, 16)
+    calls = []
+    real_call, lib.call = lib.call, lambda name, *a: calls.append((name, a))
+    lib.set_rec_lane(1)
+
+    def run(precision, epi, tuned=None, x3_planes=True, twice=False, **kw):
+        owner = types.SimpleNamespace(_tuned=dict(tuned or {}), autotune=True, precision=precision, x3_planes=x3_planes)
+        del calls[:]
+        for _ in range(2 if twice else 1):
+            gemm.linear(owner, epi, A, W, bias, out, 4, 128, 64, **kw)
+        assert owner._tuned == (tuned or {})                        # nothing is tabled while recording; EPI_QKV_ROPE never records a key of its own
+        for name, args in calls:
+            assert len(args) == len(lib._SIGS[name]), name
+        return owner, calls[0] if not twice else list(calls)
+    try:
+        stream = lib.stream_ptr()
+        q = L.ATTN_ROT_Q_SCALE
+        plain = (None, 0, None, 0, None, 0, 0.0, None, 0, None)      # the ten epilogue arguments at their neutral values
+        same = lambda got, want: len(got) == len(want) and all(g is w if isinstance(w, torch.Tensor) else (g == w and type(g) is type(w)) for g, w in zip(got, want))
+
+        def fused(got, *want):
+            assert got[0] == "toc3d_linear_fused" and same(got[1], want + (stream,)), (got, want)
+
+        def roped(got, *want):
+            assert got[0] == "toc3d_linear_qkv_rope" and same(got[1], want + (stream,)), (got, want)
+        fused(run("bf16", L.EPI_BIAS)[1], 1, 0, 0, A, 64, W, 64, bias, out, 128, None, 0, 0, None, None, 4, 128, 64, 0, *plain)
+        fused(run("fp32", L.EPI_GELU)[1], 0, 3, 0, A, 64, W, 64, bias, out, 128, None, 0, 0, None, None, 4, 128, 64, 0, *plain)
+        fused(run("fp32x6", L.EPI_RESIDUAL, residual=res, ldr=128, residual_row_mod=2)[1],
+              3, 1, 0, A, 64, W, 64, bias, out, 128, res, 128, 2, None, None, 4, 128, 64, 0, *plain)
+        fused(run("bf16", L.EPI_RESIDUAL, residual=res, ldr=128, rep_out=rep_out, rep_index=rep_index, residual_index=ridx)[1],
+              1, 1, 0, A, 64, W, 64, bias, out, 128, res, 128, 0, rep_out, rep_index, 4, 128, 64, 0, None, 0, None, 0, None, 0, 0.0, None, 0, ridx)
+        fused(run("bf16", L.EPI_SWIGLU, n_valid=50)[1], 1, 2, 0, A, 64, W, 64, bias, out, 128, None, 0, 0, None, None, 4, 128, 64, 50, *plain)
+        fused(run("bf16", L.EPI_SWIGLU_STATS, n_valid=50, stats_out=(st, 2))[1],
+              1, 4, 0, A, 64, W, 64, bias, out, 128, None, 0, 0, None, None, 4, 128, 64, 50, st, 2, None, 0, None, 0, 0.0, None, 0, None)
+        fused(run("bf16", L.EPI_RESIDUAL_LN, residual=out, ldr=128, rep_out=rep_out, rep_index=rep_index, stats_in=(st, 2, 1), col_sums=c1, ln_n=50, ln_eps=1e-6)[1],
+              1, 5, 0, A, 64, W, 64, bias, out, 128, out, 128, 0, rep_out, rep_index, 4, 128, 64, 0, None, 0, st, 4294967298, c1, 50, 1e-06, None, 0, None)
+        fused(run("bf16", L.EPI_RESIDUAL_STATS, residual=res, ldr=128, rep_out=rep_out, rep_index=rep_index, stats_out=(st2, 2), out_act=act, ld_act=128, residual_index=ridx)[1],
+              1, 6, 0, A, 64, W, 64, bias, out, 128, res, 128, 0, rep_out, rep_index, 4, 128, 64, 0, st2, 2, None, 0, None, 0, 0.0, act, 128, ridx)
+        fused(run("bf16", L.EPI_SWIGLU_STATS_LN, n_valid=50, stats_out=(st, 2), stats_in=(st2, 2, 1), col_sums=c1, ln_n=64, ln_eps=1e-6)[1],
+              1, 7, 0, A, 64, W, 64, bias, out, 128, None, 0, 0, None, None, 4, 128, 64, 50, st, 2, st2, 4294967298, c1, 64, 1e-06, None, 0, None)
+        fused(run("bf16", L.EPI_CONV3X3, conv=(zeros, 2, 2))[1],
+              1, 8, 0, A, 64, W, 64, bias, out, 128, None, 0, 0, None, None, 4, 128, 64, 0, None, 0, None, 0, None, 0, 0.0, zeros, 8589934594, None)
+        # EPI_QKV_ROPE looks its tile up under the EPI_BIAS key
+        roped(run("bf16", L.EPI_QKV_ROPE, tuned={(L.EPI_BIAS, 4, 128, 64): 14}, rope=(rc, tab, 8, q))[1],
+              1, 14, A, 64, W, 64, bias, out, 128, 4, 128, 64, rc, tab, 8, 0.18033688011112042)
+        # fp32x3 with the weights in planes (TOC3D_DTYPE_F32X3W): every (a_planes, o_planes) -> F32X3W / WO / WA / P; the rotating epilogue always writes planes
+        for ap, op, dt, dt_rope in ((False, False, 4, 6), (False, True, 6, 6), (True, False, 7, 5), (True, True, 5, 5)):
+            fused(run("fp32x3", L.EPI_BIAS, a_planes=ap, o_planes=op)[1], dt, 0, 0, A, 64, W, 64, bias, out, 128, None, 0, 0, None, None, 4, 128, 64, 0, *plain)
+            roped(run("fp32x3", L.EPI_QKV_ROPE, a_planes=ap, o_planes=op, rope=(rc, tab, 8, q))[1],
+                  dt_rope, 0, A, 64, W, 64, bias, out, 128, 4, 128, 64, rc, tab, 8, 0.18033688011112042)
+        # ... and with x3_planes off the flags mean nothing: plain TOC3D_DTYPE_F32X3
+        fused(run("fp32x3", L.EPI_BIAS, x3_planes=False, a_planes=True, o_planes=True)[1], 2, 0, 0, A, 64, W, 64, bias, out, 128, None, 0, 0, None, None, 4, 128, 64, 0, *plain)
+        # a tabled variant; a variant the caller decides (the decoder) needs no table at all
+        fused(run("bf16", L.EPI_RESIDUAL, tuned={(L.EPI_RESIDUAL, 4, 128, 64): 16}, residual=out, ldr=128)[1],
+              1, 1, 16, A, 64, W, 64, bias, out, 128, out, 128, 0, None, None, 4, 128, 64, 0, *plain)
+        fused(run("bf16", L.EPI_RESIDUAL, residual=out, ldr=128, variant=14)[1], 1, 1, 14, A, 64, W, 64, bias, out, 128, out, 128, 0, None, None, 4, 128, 64, 0, *plain)
+        # a tabled split-K variant goes to toc3d_linear_fused_ws with a zeroed workspace of the size the library asks for, reused by the second launch
+        owner, (c0, c1_) = run("bf16", L.EPI_RESIDUAL, tuned={(L.EPI_RESIDUAL, 4, 128, 64): 2014}, twice=True, residual=out, ldr=128)
+        ws = c0[1][-3]
+        assert lib.load().toc3d_linear_splitk_workspace_bytes(2014, 4, 128) == 131072
+        assert ws.dtype == torch.int32 and ws.numel() * 4 == 131072 and not ws.any() and c1_[1][-3] is ws and owner._sk_ws == {(None, stream): ws}
+        for c in (c0, c1_):
+            assert c[0] == "toc3d_linear_fused_ws" and same(c[1], (1, 1, 2014, A, 64, W, 64, bias, out, 128, out, 128, 0, None, None, 4, 128, 64, 0, *plain, ws, 131072, stream))
+    finally:
+        lib.call = real_call
+        lib.set_rec_lane(None)

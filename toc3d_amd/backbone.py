@@ -22,13 +22,14 @@ from __future__ import annotations
 
 import math
 from functools import partial
-from typing import Dict, List, Optional
+from typing import Dict
 
 import torch
 import torch.nn as nn
 
-from . import lib
-from .plan import MODES, EagerExec, run_frame
+from . import gemm, lib
+from .gemm import DEFAULT_PRECISION, round_up              # (DEFAULT_PRECISION: re-exported, the configs and tests read it from here)
+from .plan import MODES, DerivedState, EagerExec, run_frame
 from .synth import MOTION_DIM, QUERY_DIM, rope_tables
 
 
@@ -53,10 +54,6 @@ def _return_type():
     ref = sys.modules.get("projects.mmdet3d_plugin.models.backbones.toc3d_utils")
     cls = getattr(ref, "ToC3DViTReturnType", None) if ref is not None else None
     return cls if isinstance(cls, type) else ToC3DViTReturnType
-
-
-def _round_up(a: int, b: int) -> int:
-    return (a + b - 1) // b * b
 
 
 # ------------------------------------------------------------------------------------------------
@@ -157,28 +154,6 @@ def _init_weights(m):
 # ------------------------------------------------------------------------------------------------
 # shared engine: weight packing + per-shape plan + the launch sequence
 # ------------------------------------------------------------------------------------------------
-# What a reference config dropped in UNCHANGED gets (no `precision` key): the fastest path that meets the reference's own tolerance -- north_star's
-# 1e-3 relative on the fp32 feature maps (tools/test.py:204-206 runs the reference in fp32): "fp32x3" (f32 buffers, every contraction as three bf16 MFMAs on (hi, lo)
-# operand splits: 3e-5 rel. max on the full-size goldens, ~0.5x the bf16 path's frames/s).  "bf16" -- BASELINE.json configs[1], the benchmarked headline: rel. L2
-# 1.3e-2 with the reference's token selection forced, like a torch-bf16 run of the reference -- is an explicit opt-in (`precision="bf16"` in the config dict);
-# "fp32" = exact-f32 MFMA (5e-6), "fp32x6" = f32-grade products from six bf16 MFMAs.  INTEGRATION.md, "Precision".
-DEFAULT_PRECISION = "fp32x3"
-
-_flush = None                   # 256 MB scratch shared by all models: evicts L2 + Infinity Cache between tuning launches
-
-
-# + 100: 8 row bands per XCD.  The 2-D XCD partitions (+ 200 / + 300, round 3) win 6-20 % on isolated cold w1|w2 / w3 launches and nothing inside the frame
-# (profiles/r03_xcd_order_sweep.txt): they stay available through the C ABI but are not tuning candidates.
-_VARIANTS = {lib.BF16: (1, 8, 9, 10, 13, 14, 15, 16, 17, 19, 22, 24, 26, 27, 28, 29, 30, 33, 45, 47, 49, 51, 52, 53, 54, 55, 56, 57, 58, 59, 60, 61, 62, 63, 110, 114, 116, 117, 126, 145, 147, 149, 151, 152,
-                        154, 155, 156, 158, 159, 160, 161, 163),
-             lib.F32: (1, 8, 9, 10, 13, 14, 16, 17, 22, 26, 28, 33, 110, 126),
-             lib.F32X3: (1, 8, 9, 10, 14, 16, 17, 19, 22, 26, 28, 29, 33, 45, 47, 49, 52, 53, 110, 114, 116, 117, 122, 126, 129, 145, 147, 149, 152)}
-# the phased big tiles on planes (round 6) need BOTH operands in planes: candidates of TOC3D_DTYPE_F32X3P only
-_VARIANTS_X3P = _VARIANTS[lib.F32X3] + (54, 55, 56, 57, 58, 59, 60, 61, 62, 63, 154, 155, 156, 158, 159, 160, 161, 162, 163)      # (54-59: the 96- / 160-row tiles, planes only too)
-_VARIANTS[lib.F32X6] = _VARIANTS[lib.F32X3W] = _VARIANTS[lib.F32X3WO] = _VARIANTS[lib.F32X3WA] = _VARIANTS[lib.F32X3]
-_VARIANTS[lib.F32X3P] = _VARIANTS_X3P
-
-
 def schedule_defaults(precision):
     """The launch-schedule switches of the backbones and their shipped defaults per precision.  Plain attributes (``model.fold_norm2 = False`` before the
     first forward, or ``schedule=dict(...)`` at construction); every one is pinned by a test (tests/test_gpu_e2e.py, tests/test_cpu_abi.py).  The
@@ -190,7 +165,7 @@ def schedule_defaults(precision):
         x3_attention=precision == "fp32x3",  # fp32x3: the attention's two contractions as bf16 x 3 products too (f32 RoPE / softmax / accumulation; TOC3D_DTYPE_F32X3 of toc3d_window_attention)
         x3_planes=precision == "fp32x3",   # fp32x3: packed weights, the GEMMs' A operands and the GEMM-to-GEMM activations as (hi, lo) bf16 planes (TOC3D_DTYPE_F32X3W / F32X3P)
         carry_compact=fast,          # consecutive accelerated blocks of one window type continue on the same compact rows (_accel_block)
-        fold_ffn_ln=fast,            # SwiGLU.ffn_ln folded across the w1|w2 -> w3 GEMM boundary (include/toc3d.h, toc3d_linear_fused)
+        fold_ffn_ln=fast,            # SwiGLU.ffn_ln folded across the w1|w2 -> w3 GEMM boundary (include/toc3d.h, the fused GEMM's LayerNorm epilogues)
         fold_norm2=fast,             # norm2 folded across the attention-projection -> w1|w2 boundary the same way
         gathered_residual=True,      # the gather skips the f32 copy of the kept rows; the projection GEMM reads their residual from x through crow_tok
         prefetch_weights=192 if bf16 else 0,   # workgroups of each attention launch that pull the next GEMMs' weights towards the chip (0 = off)
@@ -205,88 +180,7 @@ def schedule_defaults(precision):
     )
 
 
-def tuned_linear(self, epi, A, lda, W, ldw, bias, out, ldo, res, ldr, res_mod, rep_out, rep_index, M, N, K, n_valid, fused=lib.NO_FUSED, a_planes=False, o_planes=False):
-    """toc3d_linear_fused with the fastest tile/pipeline variant for this (epilogue, M, N, K), measured once on the
-    real operands the first time the shape is seen (never while a launch plan is being recorded: shapes are warmed up eagerly).
-    ``self`` = the owner of the table: anything with ``_tuned`` (dict), ``autotune`` (bool) and ``_dt`` (the backbones, the neck).
-    All variants accumulate K in the same order, so the choice does not change results."""
-    global _flush
-    dtg = getattr(self, "_dt_gemm", None)
-    dtg = self._dt if dtg is None else dtg                 # the linear layers' arithmetic: _dt, or F32X3 / F32X3W on the "fp32x3" precision
-    if dtg == lib.F32X3W:                                   # fp32x3 on (hi, lo) planes: W always; A when its producer wrote planes; the SwiGLU hidden units / out_act when the consuming GEMM reads planes
-        dtg = {(False, False): lib.F32X3W, (True, False): lib.F32X3WA, (False, True): lib.F32X3WO, (True, True): lib.F32X3P}[(bool(a_planes), bool(o_planes))]
-    key = (epi, M, N, K)
-    var = self._tuned.get(key)
-    s = lib.stream_ptr()
-    if epi == lib.EPI_QKV_ROPE:
-        # the rotating epilogue costs what the bias epilogue costs: it shares that epilogue's tile table (no second tuning sweep)
-        rope = fused
-        if var is None:
-            var = self._tuned.get((lib.EPI_BIAS, M, N, K), 0)
-        if dtg in (lib.F32X3WA, lib.F32X3W):                # (the rotated rows always leave as planes on the x3 path: toc3d_window_attention_rot stages them by DMA)
-            dtg = lib.F32X3P if dtg == lib.F32X3WA else lib.F32X3WO
-        lib.call("toc3d_linear_qkv_rope", dtg, var, A, lda, W, ldw, bias, out, ldo, M, N, K, *rope, s)
-        return
-    if var is None:
-        var = 0
-        if lib.recording():
-            # a shape first seen while recording (the eager warm-up forward normally tunes every shape): heuristic tile, no timing
-            lib.call("toc3d_linear_fused", dtg, epi, 0, A, lda, W, ldw, bias, out, ldo, res, ldr, res_mod, rep_out, rep_index, M, N, K, n_valid, *fused, s)
-            return
-        if self.autotune and not torch.cuda.is_current_stream_capturing():
-            o = out
-            if epi in (lib.EPI_RESIDUAL, lib.EPI_RESIDUAL_LN, lib.EPI_RESIDUAL_STATS):   # in-place residual add: tune into scratch
-                o = torch.empty(M, ldo, dtype=torch.float32, device=out.device)
-            rep_s = torch.empty_like(rep_out) if rep_out is not None else None
-            cands = _VARIANTS[dtg]
-            if epi in (lib.EPI_SWIGLU, lib.EPI_SWIGLU_STATS, lib.EPI_SWIGLU_STATS_LN):
-                cands = [v for v in cands if v not in (33, 45, 145, 52, 53, 152)]   # wave slabs that are not whole (w1, w2) 32-column groups
-            if epi in (lib.EPI_SWIGLU_STATS, lib.EPI_SWIGLU_STATS_LN):  # statistics slots are 128 packed columns: N-tiles of 128 / 256 only
-                cands = [v for v in cands if v % 100 not in (9, 13, 14, 27, 33, 45, 47)]
-            # Inside the block sequence every GEMM starts on cold operands (the previous kernels streamed tens of MB through
-            # L2 / Infinity Cache): time single launches behind a cache-sized memset, not a warm back-to-back loop, or the
-            # tuner prefers shallow pipelines that lose in place (tools/ubench/n1024_all_variants.py).
-            if _flush is None or _flush.device != out.device:
-                _flush = torch.empty(64 * 1024 * 1024, dtype=torch.float32, device=out.device)
-
-            def cold_time(v, reps):
-                args = (dtg, epi, v, A, lda, W, ldw, bias, o, ldo, res, ldr, res_mod, rep_s, rep_index, M, N, K, n_valid, *fused, s)
-                try:
-                    lib.call("toc3d_linear_fused", *args)
-                except RuntimeError:                             # a tile variant that cannot serve this epilogue
-                    return float("inf")
-                ts = []
-                for _ in range(reps):
-                    _flush.zero_()
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    lib.call("toc3d_linear_fused", *args)
-                    e1.record()
-                    e1.synchronize()
-                    ts.append(e0.elapsed_time(e1))
-                return min(ts)
-            # two passes: a quick one over every candidate, then the four best again with more samples (single cold launches
-            # are noisy, and a wrong pick costs 10-20 % on that shape for the lifetime of the model)
-            short = sorted((cold_time(v, 3), v) for v in cands)[:4]
-            var = min((cold_time(v, 9), v) for _, v in short)[1]
-        self._tuned[key] = var
-    if var >= 1000:
-        # a deterministic split-K pick (include/toc3d.h, toc3d_linear_fused_ws; only a table can name one: the tuner's candidates are the unsplit variants --
-        # measured slower on every launch of the frame, profiles/r05_splitk.txt).  One zeroed workspace per owner and stream: launches on one lane share it.
-        need = int(lib.load().toc3d_linear_splitk_workspace_bytes(var, M, N))
-        pool = self.__dict__.setdefault("_sk_ws", {})
-        s = (out.device.index, s)                     # (the default stream's handle is 0 on every device: ADVICE r05)
-        ws = pool.get(s)
-        if ws is None or ws.numel() * 4 < need:
-            if ws is not None:
-                self.__dict__.setdefault("_sk_ws_old", []).append(ws)      # recorded plans may still name it
-            ws = pool[s] = torch.zeros((need + 3) // 4, dtype=torch.int32, device=out.device)
-        lib.call("toc3d_linear_fused_ws", dtg, epi, var, A, lda, W, ldw, bias, out, ldo, res, ldr, res_mod, rep_out, rep_index, M, N, K, n_valid, *fused, ws, ws.numel() * 4, s[1])
-        return
-    lib.call("toc3d_linear_fused", dtg, epi, var, A, lda, W, ldw, bias, out, ldo, res, ldr, res_mod, rep_out, rep_index, M, N, K, n_valid, *fused, s)
-
-
-class _BackboneBase(nn.Module):
+class _BackboneBase(DerivedState, nn.Module):
     LN_EPS = 1e-6            # norm_layer=partial(nn.LayerNorm, eps=1e-6), toc3d_eva_vit.py:38
     SCORER_LN_EPS = 1e-5     # nn.LayerNorm default inside the scorers
 
@@ -330,8 +224,7 @@ class _BackboneBase(nn.Module):
         self._out_features = [out_feature]
         self._out_feature_channels = {out_feature: embed_dim}
         self._out_feature_strides = {out_feature: patch_size}
-        self._packed = None
-        self._plans: Dict[tuple, dict] = {}
+        self._drop_derived()
         self._tuned: Dict[tuple, int] = {}
         self.autotune = True            # pick the GEMM tile variant per shape by measurement (first eager forward)
         self.alias_outputs = False      # True: returned tensors alias the reused workspace (benchmarks)
@@ -347,34 +240,14 @@ class _BackboneBase(nn.Module):
         assert self.launch_mode in MODES, self.launch_mode
         self._stream_pool = []
 
-    # -- state-dict hook: re-pack after new weights arrive ------------------------------------------
-    def _load_from_state_dict(self, *a, **k):
-        self._packed = None
-        self._plans = {}                # recorded launch plans point into the packed weights
-        self.__dict__.pop("_sk_ws", None), self.__dict__.pop("_sk_ws_old", None)      # split-K workspaces belong to the dropped plans' device
-        return super()._load_from_state_dict(*a, **k)
-
-    def _apply(self, fn, *a, **k):
-        self._packed = None
-        self._plans = {}                # (the Gumbel frame counter survives: plans on the same device keep naming it, _rng_state carries its value to a new one)
-        self.__dict__.pop("_sk_ws", None), self.__dict__.pop("_sk_ws_old", None)      # split-K workspaces belong to the dropped plans' device
-        return super()._apply(fn, *a, **k)
-
-    def load_state_dict(self, *a, **k):
-        self._packed = None
-        self._plans = {}
-        self.__dict__.pop("_sk_ws", None), self.__dict__.pop("_sk_ws_old", None)      # split-K workspaces belong to the dropped plans' device
-        return super().load_state_dict(*a, **k)
-
-    # -- copies / pickles: recorded launch plans (native handles with baked device pointers), workspaces and packed weights belong to
-    # THIS instance's buffers; a copy starts without them and re-packs / re-records on its first forward -----------------------------
-    _TRANSIENT = ("_packed", "_plans", "_stream_pool", "_gumbel_rng", "_sk_ws", "_sk_ws_old")
+    # -- derived state (plan.DerivedState): new weights or a device move drop the packed weights, the recorded launch plans that point into them and
+    # the split-K workspaces of the dropped plans' device (the Gumbel frame counter survives: plans on the same device keep naming it, _rng_state
+    # carries its value to a new one); copies / pickles start without them and without this instance's streams -----------------------------------
+    _DERIVED = dict(_packed=None, _plans={}, _sk_ws={}, _sk_ws_old=[])
+    _INSTANCE = dict(_stream_pool=[])
 
     def __getstate__(self):
-        d = dict(self.__dict__)
-        d["_packed"], d["_plans"], d["_stream_pool"] = None, {}, []
-        d.pop("_sk_ws", None)
-        d.pop("_sk_ws_old", None)
+        d = super().__getstate__()
         if d.get("_gumbel_rng") is not None:
             # A copy CONTINUES the noise stream where this model stands (same key, the counter's value carried as a host tensor that _rng_state moves to
             # the copy's device) instead of replaying it from frame 0: original and replica then draw the same noise for the frames that follow -- replicas
@@ -387,52 +260,26 @@ class _BackboneBase(nn.Module):
         if "gumbel_seed" in d and "_gumbel_seed" not in d:
             d = dict(d)
             d["_gumbel_seed"] = d.pop("gumbel_seed")
-        self.__dict__.update(d)
-
-    def __deepcopy__(self, memo):
-        import copy
-        new = self.__class__.__new__(self.__class__)
-        memo[id(self)] = new
-        for k, v in self.__getstate__().items():
-            new.__dict__[k] = copy.deepcopy(v, memo)
-        return new
+        super().__setstate__(d)           # (nn.Module back-fills the hook dictionaries that pickles of older torch versions lack)
 
     # -- helpers ---------------------------------------------------------------------------------------
     def _accelerated(self, i):
         return False                                      # dense backbone: every block is Block.forward (ToC3DEVAViT overrides)
 
+    # -- dtype codes of this precision and schedule (gemm.dtypes has the table) -------------------------------
     @property
-    def _dt(self):
-        return lib.BF16 if self.precision == "bf16" else lib.F32
+    def _dts(self):
+        return gemm.dtypes(self.precision, self.x3_planes, self.x3_attention)
 
-    @property
-    def _dt_gemm(self):
-        """Arithmetic of the linear layers: "fp32x3" keeps every buffer in f32 and forms the GEMM products as three bf16 MFMAs on the operands'
-        (hi, lo) splits (include/toc3d.h TOC3D_DTYPE_F32X3) -- the parity-grade path at a third of the bf16 MFMA rate instead of a sixteenth."""
-        return {"fp32x3": lib.F32X3W if self.x3_planes else lib.F32X3, "fp32x6": lib.F32X6}.get(self.precision, self._dt)
-
-    def _planes(self, w):
-        """fp32x3 with x3_planes: a packed f32 weight -> (hi, lo) bf16 planes, in place (include/toc3d.h, TOC3D_DTYPE_F32X3W): the GEMM then DMAs the planes
-        instead of splitting the W tile in LDS in every workgroup of every launch."""
-        if self.precision == "fp32x3" and self.x3_planes:
-            lib.call("toc3d_x3_planes", w, w.shape[1], w, w.shape[1], w.shape[0], w.shape[1], lib.stream_ptr())
-        return w
-
-    @property
-    def _tdt(self):
-        return torch.bfloat16 if self.precision == "bf16" else torch.float32
+    _dt = property(lambda self: self._dts.act)
+    _tdt = property(lambda self: self._dts.torch)
+    _dt_gemm = property(lambda self: self._dts.gemm)
+    _dt_rows = property(lambda self: self._dts.rows)
+    _dt_attn = property(lambda self: self._dts.attn)
+    _x3p = property(lambda self: self._dts.x3p)
 
     def _block_side(self, i):
         return self.global_window_size if i in self.global_attn_indexes else self.window_size
-
-    def _pack_linear(self, w: torch.Tensor):
-        """f32 [N, K] -> act [ceil128(N), ceil64(K)] via the C ABI."""
-        w = w.detach().float().contiguous()
-        N, K = w.shape
-        Np, Kp = _round_up(N, 128), _round_up(K, 64)
-        out = torch.empty(Np, Kp, dtype=self._tdt, device=w.device)
-        lib.call("toc3d_pack_weight", self._dt, w, N, K, out, Np, Kp, lib.stream_ptr())
-        return self._planes(out)
 
     @staticmethod
     def _f32(t):
@@ -440,18 +287,19 @@ class _BackboneBase(nn.Module):
 
     def _pack_blocks(self, dev):
         C, Hd = self.embed_dim, self.hidden_dim
-        Hp = _round_up(Hd, 64)
+        Hp = round_up(Hd, 64)
+        pack = partial(gemm.pack_weight, dts=self._dts)
         blocks = []
         for blk in self.blocks:
             a, m = blk.attn, blk.mlp
             p = {}
-            p["wqkv"] = self._pack_linear(torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight], 0))
+            p["wqkv"] = pack(torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight], 0))
             zb = torch.zeros(C, device=dev)
             qb = a.q_bias if a.q_bias is not None else zb
             vb = a.v_bias if a.v_bias is not None else zb
             p["bqkv"] = self._f32(torch.cat([qb, zb, vb]))
             p["v_bias"] = self._f32(vb)
-            p["wproj"], p["bproj"] = self._pack_linear(a.proj.weight), self._f32(a.proj.bias)
+            p["wproj"], p["bproj"] = pack(a.proj.weight), self._f32(a.proj.bias)
             w12 = torch.empty(2 * Hp, C, dtype=self._tdt, device=dev)
             b12 = torch.empty(2 * Hp, dtype=torch.float32, device=dev)
             lib.call("toc3d_pack_swiglu", self._dt, self._f32(m.w1.weight), self._f32(m.w2.weight), self._f32(m.w1.bias),
@@ -463,19 +311,19 @@ class _BackboneBase(nn.Module):
                          self._f32(blk.norm2.weight), self._f32(blk.norm2.bias), Hd, C, w12, p["c1_12"], p["c2_12"], Hp, C, lib.stream_ptr())
             if self.fold_ffn_ln:
                 N3, K3 = m.w3.weight.shape
-                w3f = torch.empty(_round_up(N3, 128), Hp, dtype=self._tdt, device=dev)
+                w3f = torch.empty(round_up(N3, 128), Hp, dtype=self._tdt, device=dev)
                 p["c1"], p["c2"] = torch.empty(N3, device=dev), torch.empty(N3, device=dev)
                 lib.call("toc3d_pack_weight_lnfold", self._dt, self._f32(m.w3.weight), self._f32(m.ffn_ln.weight), self._f32(m.ffn_ln.bias),
                          self._f32(m.w3.bias), N3, K3, w3f, w3f.shape[0], Hp, p["c1"], p["c2"], lib.stream_ptr())
-                p["w3"] = self._planes(w3f)                       # gamma-scaled; c1 / c2 carry the mean and beta / bias terms
+                p["w3"] = gemm.planes(w3f, self._dts)                       # gamma-scaled; c1 / c2 carry the mean and beta / bias terms
             else:
-                p["w3"], p["b3"] = self._pack_linear(m.w3.weight), self._f32(m.w3.bias)
-            self._planes(w12)
+                p["w3"], p["b3"] = pack(m.w3.weight), self._f32(m.w3.bias)
+            gemm.planes(w12, self._dts)
             for n, mod in (("ln1", blk.norm1), ("ln2", blk.norm2), ("lnf", m.ffn_ln)):
                 p[n + "_w"], p[n + "_b"] = self._f32(mod.weight), self._f32(mod.bias)
             p["cos"], p["sin"] = self._f32(a.rope.freqs_cos), self._f32(a.rope.freqs_sin)
             p["rope_side"] = self._check_axial_rope(p["cos"], p["sin"])
-            if self.attn_rot:                                     # compact axial tables [2, L, 16]: one entry per frequency pair (toc3d_linear_qkv_rope)
+            if self.attn_rot:                                     # compact axial tables [2, L, 16]: one entry per frequency pair (the q|k|v GEMM's rotating epilogue)
                 L = p["rope_side"]
                 tabs = []
                 for nm in ("cos", "sin"):
@@ -510,7 +358,7 @@ class _BackboneBase(nn.Module):
         lib.load()
         P = {"dev": dev}
         C = self.embed_dim
-        P["w_patch"] = self._pack_linear(self.patch_embed.proj.weight.reshape(C, -1))
+        P["w_patch"] = gemm.pack_weight(self.patch_embed.proj.weight.reshape(C, -1), self._dts)
         P["b_patch"] = self._f32(self.patch_embed.proj.bias)
         P["blocks"] = self._pack_blocks(dev)
         P["pos"] = {}                                   # (h, w) -> bicubic-resized abs-pos, built on first use
@@ -548,7 +396,7 @@ class _BackboneBase(nn.Module):
         return d
 
     def _base_plan(self, V, H, W, dev, max_rows):
-        C, Hp = self.embed_dim, _round_up(self.hidden_dim, 64)
+        C, Hp = self.embed_dim, round_up(self.hidden_dim, 64)
         p = self.patch_size
         h, w = H // p, W // p
         T, M = h * w, V * h * w
@@ -562,10 +410,10 @@ class _BackboneBase(nn.Module):
                     att=torch.empty(R, C, dtype=tdt, device=dev),
                     hid=torch.zeros(R, Hp, dtype=tdt, device=dev),
                     hln=torch.zeros(R, Hp, dtype=tdt, device=dev),
-                    col=torch.zeros(M, _round_up(Kc, 64), dtype=tdt, device=dev),
+                    col=torch.zeros(M, round_up(Kc, 64), dtype=tdt, device=dev),
                     Kc=Kc)
         if self.fold_ffn_ln:                                      # per-row partial (sum, sum^2) slots of the hidden units: header + [R, cap, 2]
-            plan["stats_cap"] = _round_up(-(-2 * Hp // 128), 2)
+            plan["stats_cap"] = round_up(-(-2 * Hp // 128), 2)
             plan["stats"] = torch.zeros(4 + R * plan["stats_cap"] * 2, dtype=torch.float32, device=dev)
             plan["stats2_cap"] = C // 64                          # norm2 fold: one slot per 64 residual-stream columns
             plan["stats2"] = torch.zeros(4 + R * plan["stats2_cap"] * 2, dtype=torch.float32, device=dev)
@@ -577,28 +425,9 @@ class _BackboneBase(nn.Module):
                 d["rc"] = (((r % L) << 16) | (c % L)).reshape(-1).contiguous()
         return plan
 
-    # -- linear layers with a per-shape autotuned tile variant -----------------------------------------------
-    def _linear(self, epi, A, lda, W, ldw, bias, out, ldo, res, ldr, res_mod, rep_out, rep_index, M, N, K, n_valid, fused=lib.NO_FUSED, a_planes=False, o_planes=False):
-        tuned_linear(self, epi, A, lda, W, ldw, bias, out, ldo, res, ldr, res_mod, rep_out, rep_index, M, N, K, n_valid, fused, a_planes, o_planes)
-
-    @property
-    def _dt_rows(self):
-        """dtype handed to the row kernels that produce a GEMM's A operand (LayerNorm / gather / rebase, the f32 attention): f32 arithmetic either way,
-        the output rows as (hi, lo) planes on fp32x3 with x3_planes (include/toc3d.h, TOC3D_DTYPE_F32X3P)."""
-        return lib.F32X3P if self._x3p else self._dt
-
-    @property
-    def _dt_attn(self):
-        """dtype of the f32-buffer attention launch: exact f32 products or, on fp32x3 with x3_attention, bf16 x 3 products; output rows plain or as planes."""
-        if self.precision != "fp32x3":
-            return self._dt
-        x3a = bool(self.x3_attention)
-        return {(False, False): lib.F32, (False, True): lib.F32X3WO, (True, False): lib.F32X3, (True, True): lib.F32X3P}[(x3a, self._x3p)]
-
-    @property
-    def _x3p(self):
-        """fp32x3 with its GEMM operands as (hi, lo) planes (schedule switch x3_planes)."""
-        return self.precision == "fp32x3" and self.x3_planes
+    def _linear(self, epi, A, W, bias, out, M, N, K, **kw):
+        """One linear layer with a per-shape autotuned tile variant (gemm.linear; this model owns the table)."""
+        gemm.linear(self, epi, A, W, bias, out, M, N, K, **kw)
 
     def save_packed(self, path):
         """Write the packed device weights (what the kernels consume) to a safetensors file; see ``packed_io``."""
@@ -646,10 +475,9 @@ class _BackboneBase(nn.Module):
     def _stem_gemm(self, plan, P):
         """PatchEmbed GEMM + abs-pos add (toc3d_eva_vit.py:243-247) -> residual stream x f32 [V*T, C]."""
         C = self.embed_dim
-        Kp = plan["col"].shape[1]
         pos = P["pos"][(plan["h"], plan["w"])]
-        self._linear(lib.EPI_RESIDUAL, plan["col"], Kp, P["w_patch"], P["w_patch"].shape[1], P["b_patch"],
-                     plan["x"], C, pos, C, plan["T"] if pos is not None else 0, None, None, plan["M"], C, Kp, 0)
+        self._linear(lib.EPI_RESIDUAL, plan["col"], P["w_patch"], P["b_patch"], plan["x"], plan["M"], C, plan["col"].shape[1],
+                     residual=pos, ldr=C, residual_row_mod=plan["T"] if pos is not None else 0)
 
     def _ensure_pos(self, P, h, w, dev):
         if (h, w) not in P["pos"]:
@@ -666,35 +494,31 @@ class _BackboneBase(nn.Module):
         if not self.prefetch_weights:
             lib.call("toc3d_window_attention", *args, s)
             return
-        import ctypes
+        lib.call("toc3d_window_attention_pf", *args, *self._prefetch_args(P, i), s)
+
+    def _prefetch_args(self, P, i):
+        """(n_prefetch, prefetch_ptrs, prefetch_bytes, prefetch_workgroups) of block i's attention launch: the weights of the GEMMs that follow it."""
         bp = P["blocks"][i]
         ts = [bp["wproj"], bp["w12"], bp["w3"]] + ([P["blocks"][i + 1]["wqkv"]] if i + 1 < self.depth else [])
-        ptrs = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-        nb = (ctypes.c_int64 * len(ts))(*[t.numel() * t.element_size() for t in ts])
-        lib.call("toc3d_window_attention_pf", *args, len(ts), ptrs, nb, self.prefetch_weights, s)
+        if not self.prefetch_weights:
+            ts = []
+        return (len(ts), *lib.ptr_arrays(ts, min_len=1), self.prefetch_weights)
 
     def _qkv_attention(self, P, i, plan, M, rope_rc, arows, aslots, count_q, count_k, npad, pad, stride, nwin, max_count, v_bias):
         """q|k|v projection + windowed attention of block i on plan["a"] [M, C] -> plan["att"] (eva_vit.py:97-113, toc3d_eva_vit.py:495-512)."""
         bp = P["blocks"][i]
         C, dt = self.embed_dim, self._dt
         if self._rot_ok(stride):
-            self._linear(lib.EPI_QKV_ROPE, plan["a"], C, bp["wqkv"], C, bp["bqkv"], plan["qkv"], 3 * C, None, 0, 0, None, None, M, 3 * C, C, 0,
-                         fused=(rope_rc, bp["rope_tab"], bp["rope_side"], lib.ATTN_ROT_Q_SCALE), a_planes=self._x3p, o_planes=self._x3p)
+            self._linear(lib.EPI_QKV_ROPE, plan["a"], bp["wqkv"], bp["bqkv"], plan["qkv"], M, 3 * C, C,
+                         rope=(rope_rc, bp["rope_tab"], bp["rope_side"], lib.ATTN_ROT_Q_SCALE), a_planes=self._x3p, o_planes=self._x3p)
             if self._x3p:       # planes in, planes out; no weight prefetch riding on this form
                 lib.call("toc3d_window_attention_rot", lib.F32X3P, plan["qkv"], 3 * C, plan["att"], C, arows, aslots, count_q, count_k, npad, pad, stride, nwin, max_count,
                          self.num_heads, v_bias, 0, None, None, 0, lib.stream_ptr())
                 return
-            import ctypes
-            nxt = P["blocks"][i + 1] if i + 1 < self.depth else None
-            ts = [bp["wproj"], bp["w12"], bp["w3"]] + ([nxt["wqkv"]] if nxt is not None else [])
-            if not self.prefetch_weights:
-                ts = []
-            ptrs = (ctypes.c_void_p * max(1, len(ts)))(*[t.data_ptr() for t in ts])
-            nb = (ctypes.c_int64 * max(1, len(ts)))(*[t.numel() * t.element_size() for t in ts])
             lib.call("toc3d_window_attention_rot", dt, plan["qkv"], 3 * C, plan["att"], C, arows, aslots, count_q, count_k, npad, pad, stride, nwin, max_count,
-                     self.num_heads, v_bias, len(ts), ptrs, nb, self.prefetch_weights, lib.stream_ptr())
+                     self.num_heads, v_bias, *self._prefetch_args(P, i), lib.stream_ptr())
             return
-        self._linear(lib.EPI_BIAS, plan["a"], C, bp["wqkv"], C, bp["bqkv"], plan["qkv"], 3 * C, None, 0, 0, None, None, M, 3 * C, C, 0, a_planes=self._x3p)
+        self._linear(lib.EPI_BIAS, plan["a"], bp["wqkv"], bp["bqkv"], plan["qkv"], M, 3 * C, C, a_planes=self._x3p)
         self._attention(P, i, self._dt_attn, plan["qkv"], 3 * C, plan["att"], C, arows, aslots, count_q, count_k, npad, pad,
                         stride, nwin, max_count, self.num_heads, bp["cos"], bp["sin"], bp["rope_side"], v_bias, 64 ** -0.5)
 
@@ -713,13 +537,12 @@ class _BackboneBase(nn.Module):
         norm2 folded the epilogue also leaves the updated rows in bf16 (plan["a"]) and their statistics (plan["stats2"]) for the w1|w2 GEMM."""
         C = self.embed_dim
         res = out if res is None else res
+        kw = dict(residual=res, ldr=C, rep_out=rep_out, rep_index=rep_index, residual_index=res_index, a_planes=self._x3p)
         if self.fold_norm2:
-            self._linear(lib.EPI_RESIDUAL_STATS, plan["att"], C, bp["wproj"], C, bp["bproj"], out, C, res, C, 0, rep_out, rep_index, rows, C, C, 0,
-                         fused=(plan["stats2"], plan["stats2_cap"], None, 0, None, 0, 0.0, plan["a"], C, res_index),
-                         a_planes=self._x3p, o_planes=self._x3p)     # the f32 copy leaves as planes: the w1|w2 GEMM's A operand
+            self._linear(lib.EPI_RESIDUAL_STATS, plan["att"], bp["wproj"], bp["bproj"], out, rows, C, C, stats_out=(plan["stats2"], plan["stats2_cap"]),
+                         out_act=plan["a"], ld_act=C, o_planes=self._x3p, **kw)     # the f32 copy leaves as planes: the w1|w2 GEMM's A operand
         else:
-            self._linear(lib.EPI_RESIDUAL, plan["att"], C, bp["wproj"], C, bp["bproj"], out, C, res, C, 0, rep_out, rep_index, rows, C, C, 0,
-                         fused=lib.NO_FUSED[:9] + (res_index,), a_planes=self._x3p)
+            self._linear(lib.EPI_RESIDUAL, plan["att"], bp["wproj"], bp["bproj"], out, rows, C, C, **kw)
 
     def _mlp(self, bp, plan, rows, res, rep_out, rep_index):
         """norm2 -> SwiGLU (w1|w2, ffn_ln, w3) -> + residual (eva_vit.py:263, toc3d_eva_vit.py:381-384); res is f32 [rows, C]."""
@@ -732,22 +555,19 @@ class _BackboneBase(nn.Module):
             # norm2 folded the same way: plan["a"] / plan["stats2"] were left by the projection GEMM (_proj), no LayerNorm launch here
             st, cap = plan["stats"], plan["stats_cap"]
             if self.fold_norm2:
-                self._linear(lib.EPI_SWIGLU_STATS_LN, plan["a"], C, bp["w12"], C, bp["c2_12"], plan["hid"], Hp, None, 0, 0, None, None, rows, 2 * Hp, C, Hd,
-                             fused=(st, cap, plan["stats2"], plan["stats2_cap"] | (C // 64) << 32, bp["c1_12"], C, self.LN_EPS, None, 0, None),
+                self._linear(lib.EPI_SWIGLU_STATS_LN, plan["a"], bp["w12"], bp["c2_12"], plan["hid"], rows, 2 * Hp, C, n_valid=Hd, stats_out=(st, cap),
+                             stats_in=(plan["stats2"], plan["stats2_cap"], C // 64), col_sums=bp["c1_12"], ln_n=C, ln_eps=self.LN_EPS,
                              a_planes=self._x3p, o_planes=self._x3p)       # A = the projection's copy (planes), hidden units as planes for w3
             else:
                 lib.call("toc3d_layernorm_rows", dt, res, C, None, None, bp["ln2_w"], bp["ln2_b"], self.LN_EPS, plan["a"], C, rows, C, s)
-                self._linear(lib.EPI_SWIGLU_STATS, plan["a"], C, bp["w12"], C, bp["b12"], plan["hid"], Hp, None, 0, 0, None, None, rows, 2 * Hp, C, Hd,
-                             fused=(st, cap, None, 0, None, 0, 0.0, None, 0, None), o_planes=self._x3p)
-            self._linear(lib.EPI_RESIDUAL_LN, plan["hid"], Hp, bp["w3"], bp["w3"].shape[1], bp["c2"], res, C, res, C, 0,
-                         rep_out, rep_index, rows, C, Hp, 0, fused=(None, 0, st, cap | (-(-2 * Hp // 128)) << 32, bp["c1"], Hd, self.LN_EPS, None, 0, None),
-                         a_planes=self._x3p)
+                self._linear(lib.EPI_SWIGLU_STATS, plan["a"], bp["w12"], bp["b12"], plan["hid"], rows, 2 * Hp, C, n_valid=Hd, stats_out=(st, cap), o_planes=self._x3p)
+            self._linear(lib.EPI_RESIDUAL_LN, plan["hid"], bp["w3"], bp["c2"], res, rows, C, Hp, residual=res, ldr=C, rep_out=rep_out, rep_index=rep_index,
+                         stats_in=(st, cap, -(-2 * Hp // 128)), col_sums=bp["c1"], ln_n=Hd, ln_eps=self.LN_EPS, a_planes=self._x3p)
             return
         lib.call("toc3d_layernorm_rows", dt, res, C, None, None, bp["ln2_w"], bp["ln2_b"], self.LN_EPS, plan["a"], C, rows, C, s)
-        self._linear(lib.EPI_SWIGLU, plan["a"], C, bp["w12"], C, bp["b12"], plan["hid"], Hp, None, 0, 0, None, None, rows, 2 * Hp, C, Hd)
+        self._linear(lib.EPI_SWIGLU, plan["a"], bp["w12"], bp["b12"], plan["hid"], rows, 2 * Hp, C, n_valid=Hd)
         lib.call("toc3d_layernorm_act", dt, plan["hid"], Hp, bp["lnf_w"], bp["lnf_b"], self.LN_EPS, plan["hln"], Hp, rows, Hd, s)
-        self._linear(lib.EPI_RESIDUAL, plan["hln"], Hp, bp["w3"], bp["w3"].shape[1], bp["b3"], res, C, res, C, 0,
-                     rep_out, rep_index, rows, C, Hp, 0)
+        self._linear(lib.EPI_RESIDUAL, plan["hln"], bp["w3"], bp["b3"], res, rows, C, Hp, residual=res, ldr=C, rep_out=rep_out, rep_index=rep_index)
 
     def _dense_block(self, i, plan, P):
         """Block.forward (eva_vit.py:247-268): LN -> window attention (pads folded analytically) -> +res; MLP -> +res."""
@@ -964,8 +784,8 @@ class ToC3DEVAViT(_BackboneBase):
                 rc = (((sl // L) << 16) | (sl % L)).to(torch.int32).contiguous()
                 a_rep = a_row.expand(L * L, C).contiguous()
                 bp["pad_rot"] = torch.empty(L * L, 3 * C, dtype=self._tdt, device=dev)
-                lib.call("toc3d_linear_qkv_rope", lib.F32X3WO if self._x3p else self._dt, 0, a_rep, C, bp["wqkv"], C, bp["bqkv"], bp["pad_rot"], 3 * C, L * L, 3 * C, C,
-                         rc, bp["rope_tab"], L, lib.ATTN_ROT_Q_SCALE, s)      # (fp32x3: A = the plain f32 LayerNorm row, W in planes, the rotated rows as planes)
+                self._linear(lib.EPI_QKV_ROPE, a_rep, bp["wqkv"], bp["bqkv"], bp["pad_rot"], L * L, 3 * C, C, rope=(rc, bp["rope_tab"], L, lib.ATTN_ROT_Q_SCALE),
+                             variant=0)                               # (fp32x3: A = the plain f32 LayerNorm row, W in planes, the rotated rows as planes)
                 keep_alive += [a_rep, rc]
         torch.cuda.current_stream().synchronize()
         nfl = lib.load().toc3d_motion_weights_floats()
@@ -974,7 +794,7 @@ class ToC3DEVAViT(_BackboneBase):
         d3 = (10000 ** (2 * torch.div(d3, 2, rounding_mode="floor") / 128)).to(dev)
         d1 = torch.arange(256, dtype=torch.float32)
         d1 = (10000 ** (2 * torch.div(d1, 2, rounding_mode="floor") / 256)).to(dev)
-        f = self._f32
+        f, pack = self._f32, partial(gemm.pack_weight, dts=self._dts)
         P["scorers"] = []
         keep = []
         P["motion_all"] = torch.empty(len(self.score_predictor), nfl, dtype=torch.float32, device=dev)
@@ -995,9 +815,9 @@ class ToC3DEVAViT(_BackboneBase):
             q["scale"] = QUERY_DIM ** -0.5 if self.pruning_attn_scale else 1.0
             # first-frame scorer (ScoreBasedTokenSelector.score)
             q["ln_w"], q["ln_b"] = f(sp.in_conv[0].weight), f(sp.in_conv[0].bias)
-            q["w_ic"], q["b_ic"] = self._pack_linear(sp.in_conv[1].weight), f(sp.in_conv[1].bias)
-            q["w_o0"], q["b_o0"] = self._pack_linear(sp.out_conv[0].weight), f(sp.out_conv[0].bias)
-            q["w_o2"], q["b_o2"] = self._pack_linear(sp.out_conv[2].weight), f(sp.out_conv[2].bias)
+            q["w_ic"], q["b_ic"] = pack(sp.in_conv[1].weight), f(sp.in_conv[1].bias)
+            q["w_o0"], q["b_o0"] = pack(sp.out_conv[0].weight), f(sp.out_conv[0].bias)
+            q["w_o2"], q["b_o2"] = pack(sp.out_conv[2].weight), f(sp.out_conv[2].bias)
             q["w_o4"], q["b_o4"] = f(sp.out_conv[4].weight), f(sp.out_conv[4].bias)
             P["scorers"].append(q)
         torch.cuda.current_stream().synchronize()
@@ -1136,11 +956,10 @@ class ToC3DEVAViT(_BackboneBase):
             # queries here and discards them (:376-385) -- skipped, no observable effect
             t_act, u1, u2 = plan["att"], plan["u1"], plan["u2"]
             lib.call("toc3d_layernorm_rows", dt, x, C, None, mask_prev, q["ln_w"], q["ln_b"], self.SCORER_LN_EPS, plan["a"], C, M, C, s)
-            self._linear(lib.EPI_GELU, plan["a"], C, q["w_ic"], q["w_ic"].shape[1], q["b_ic"], t_act, C, None, 0, 0, None, None, M, C, C, 0)
+            self._linear(lib.EPI_GELU, plan["a"], q["w_ic"], q["b_ic"], t_act, M, C, C)
             lib.call("toc3d_global_mean_half", dt, t_act, C, V, T, C, s)
-            self._linear(lib.EPI_GELU, t_act, C, q["w_o0"], q["w_o0"].shape[1], q["b_o0"], u1, u1.shape[1], None, 0, 0, None, None, M, C // 2, C, 0)
-            self._linear(lib.EPI_GELU, u1, u1.shape[1], q["w_o2"], q["w_o2"].shape[1], q["b_o2"], u2, u2.shape[1], None, 0, 0, None, None,
-                         M, C // 4, q["w_o2"].shape[1], 0)
+            self._linear(lib.EPI_GELU, t_act, q["w_o0"], q["b_o0"], u1, M, C // 2, C)
+            self._linear(lib.EPI_GELU, u1, q["w_o2"], q["b_o2"], u2, M, C // 4, q["w_o2"].shape[1])
             lib.call("toc3d_score_head", dt, u2, u2.shape[1], C // 4, q["w_o4"], q["b_o4"], g, M, pred, score, mask, s)
         self._stage_override(st, plan, score, mask)
 

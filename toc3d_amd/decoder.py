@@ -18,16 +18,12 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from . import lib
+from . import gemm, lib
 from . import plan as _plan
-from .backbone import DEFAULT_PRECISION
+from .gemm import DEFAULT_PRECISION
 
 _ORDER = ("self_attn", "norm", "cross_attn", "norm", "ffn", "norm")
 _SUPPORTED = ("bf16", "fp32x3")
-
-
-def _ru(x, m):
-    return (x + m - 1) // m * m
 
 
 class _Attention(nn.Module):                # parameter container: PETRMultiheadAttention / mmcv MultiheadAttention keep an nn.MultiheadAttention under `.attn`
@@ -60,7 +56,7 @@ class _Decoder(nn.Module):
         self.embed_dims = embed_dims
 
 
-SPLITK_VARIANT = 4014     # four K slices on 64x64 tiles, added in slice order (include/toc3d.h, toc3d_linear_fused_ws)
+SPLITK_VARIANT = 4014     # four K slices on 64x64 tiles, added in slice order (include/toc3d.h, the fused GEMM's split-K entry point)
 
 
 def _tile_variant(M, N, K, residual):
@@ -145,7 +141,7 @@ def _parse(encoder, decoder):
     return num_layers, E, H, F
 
 
-class PETRTemporalTransformer(nn.Module):
+class PETRTemporalTransformer(_plan.DerivedState, nn.Module):
     def __init__(self, encoder=None, decoder=None, init_cfg=None, cross=False, precision=DEFAULT_PRECISION, launch_mode="plan"):
         super().__init__()
         L, E, H, F = _parse(encoder, decoder)
@@ -158,60 +154,24 @@ class PETRTemporalTransformer(nn.Module):
         self.embed_dims, self.num_heads, self.feedforward_channels, self.num_layers = E, H, F, L
         self.cross, self.precision, self.launch_mode = cross, precision, launch_mode
         self.capture = None                    # test instrument: a dict here receives clones of every norm's output (eager launches only)
-        self._packed, self._ws, self._states, self._pool = None, {}, {}, []
+        self._pool = []
+        self._drop_derived()
 
     def init_weights(self):                    # petr_transformer.py:461-466
         for m in self.modules():
             if hasattr(m, "weight") and isinstance(m.weight, torch.Tensor) and m.weight.dim() > 1:
                 nn.init.xavier_uniform_(m.weight)
-        self._drop()
+        self._drop_derived()
 
-    # packed weights, workspaces and recorded plans (which point into both) are derived state
-    def _drop(self):
-        self._packed, self._ws, self._states = None, {}, {}
-
-    def load_state_dict(self, *a, **k):
-        self._drop()
-        return super().load_state_dict(*a, **k)
-
-    def _load_from_state_dict(self, *a, **k):
-        self._drop()
-        return super()._load_from_state_dict(*a, **k)
-
-    def _apply(self, fn, *a, **k):
-        self._drop()
-        return super()._apply(fn, *a, **k)
-
-    def __getstate__(self):
-        d = dict(self.__dict__)
-        d["_packed"], d["_ws"], d["_states"], d["_pool"], d["capture"] = None, {}, {}, [], None
-        return d
-
-    def __deepcopy__(self, memo):
-        import copy
-        new = self.__class__.__new__(self.__class__)
-        memo[id(self)] = new
-        for k, v in self.__getstate__().items():
-            new.__dict__[k] = copy.deepcopy(v, memo)
-        return new
+    # packed weights, workspaces (the split-K ones of gemm.linear included) and recorded plans, which point into both, are derived state
+    _DERIVED = dict(_packed=None, _ws={}, _states={}, _sk_ws={}, _sk_ws_old=[])
+    _INSTANCE = dict(_pool=[], capture=None)
 
     # ------------------------------------------------------------------------------------------------------------------------------
     def _pack(self, dev):
-        bf = self.precision == "bf16"
-        dt, tdt = (lib.BF16, torch.bfloat16) if bf else (lib.F32, torch.float32)
-        s = lib.stream_ptr()
-        E = self.embed_dims
-
-        def pack(w, b):
-            w = w.detach().float().contiguous().to(dev)
-            N, K = w.shape
-            out = torch.empty(_ru(N, 128), _ru(K, 64), dtype=tdt, device=dev)
-            lib.call("toc3d_pack_weight", dt, w, N, K, out, out.shape[0], out.shape[1], s)
-            if not bf:                                             # fp32x3: weights as (hi, lo) planes (include/toc3d.h, TOC3D_DTYPE_F32X3W)
-                lib.call("toc3d_x3_planes", out, out.shape[1], out, out.shape[1], out.shape[0], out.shape[1], s)
-            return out, b.detach().float().contiguous().to(dev)
-
+        dts = gemm.dtypes(self.precision)                          # (fp32x3: weights as (hi, lo) planes)
         f32 = lambda t: t.detach().float().contiguous().to(dev)
+        pack = lambda w, b: (gemm.pack_weight(w, dts, dev), f32(b))
         layers = []
         thirds = lambda a: (a.attn.in_proj_weight.detach().chunk(3), a.attn.in_proj_bias.detach().chunk(3))
         ck, cv, tk, tv = [], [], [], []
@@ -226,7 +186,8 @@ class PETRTemporalTransformer(nn.Module):
                                f0=pack(f0.weight, f0.bias), f1=pack(f1.weight, f1.bias),
                                norms=[(f32(n.weight), f32(n.bias), float(n.eps)) for n in lay.norms]))
         cat = lambda ps: pack(torch.cat([w for w, _ in ps]), torch.cat([b for _, b in ps]))
-        P = dict(dt=dt, tdt=tdt, dtg=lib.BF16 if bf else lib.F32X3W, dta=lib.BF16 if bf else lib.F32X3, layers=layers,
+        # (the attention reads and writes plain rows: bf16 x 3 products on fp32x3, no planes)
+        P = dict(dt=dts.act, tdt=dts.torch, dta=gemm.attn_dtype(self.precision, x3_attention=True, planes_out=False), layers=layers,
                  ck=cat(ck), cv=cat(cv), tk=cat(tk), tv=cat(tv), post=(f32(self.decoder.post_norm.weight), f32(self.decoder.post_norm.bias)))
         torch.cuda.current_stream().synchronize()
         return P
@@ -242,9 +203,6 @@ class PETRTemporalTransformer(nn.Module):
                  mem_a=z(B * Nk, E), mem_pa=z(B * Nk, E), ck=z(B * Nk, L * E), cv=z(B * Nk, L * E),
                  x=[z(B * Nq, E, f) for _ in range(3)], y=z(B * Nq, E, f), xa=z(B * Nq, E), xpa=z(B * Nq, E), qk=z(B * Nq, 2 * E), v=z(B * Nq, E),
                  att=z(B * Nq, E), qc=z(B * Nq, E), h=z(B * Nq, F), outs=torch.zeros(L, B * Nq, E, dtype=f, device=dev))
-        need = int(lib.load().toc3d_linear_splitk_workspace_bytes(SPLITK_VARIANT, B * Nq, E))
-        assert need > 0
-        W["splitk"] = torch.zeros((need + 3) // 4, dtype=torch.int32, device=dev)      # arrival tickets (zero before the first launch; launches re-arm them) + partial tiles
         if Nm:
             W.update(tmem=z(B * Nm, E, f), tpos=z(B * Nm, E, f), tm_a=z(B * Nm, E), tm_pa=z(B * Nm, E), tk=z(B * Nm, L * E), tv=z(B * Nm, L * E))
         self._ws[key] = W
@@ -254,7 +212,7 @@ class PETRTemporalTransformer(nn.Module):
         """The launch sequence of one frame on the staged inputs of workspace ``W`` (eager or being recorded)."""
         P, (B, Nq, Nk, Nm) = self._packed, key
         E, F, L, H = self.embed_dims, self.feedforward_channels, self.num_layers, self.num_heads
-        dt, dtg, dta = P["dt"], P["dtg"], P["dta"]
+        dt, dta = P["dt"], P["dta"]
         Mq = B * Nq
         cap = None if lib.recording() else self.capture
         with ex.lane(0):
@@ -262,14 +220,8 @@ class PETRTemporalTransformer(nn.Module):
 
             def linear(a, wb, out, M, N, K, residual=None):
                 wgt, b = wb
-                epi = lib.EPI_BIAS if residual is None else lib.EPI_RESIDUAL
-                var = _tile_variant(M, N, K, residual is not None)
-                args = (dtg, epi, var, a, a.shape[1], wgt, wgt.shape[1], b, out, out.shape[1], residual, 0 if residual is None else residual.shape[1], 0, None, None,
-                        M, N, K, 0, *lib.NO_FUSED)
-                if var >= 1000:
-                    lib.call("toc3d_linear_fused_ws", *args, W["splitk"], W["splitk"].numel() * 4, s)
-                else:
-                    lib.call("toc3d_linear_fused", *args, s)
+                gemm.linear(self, lib.EPI_BIAS if residual is None else lib.EPI_RESIDUAL, a, wgt, b, out, M, N, K, residual=residual,
+                            ldr=0 if residual is None else residual.shape[1], variant=_tile_variant(M, N, K, residual is not None))
 
             def norm(nrm, x_out, act=None, act_pos=None, post=None, out2=None):
                 g, b, eps = nrm

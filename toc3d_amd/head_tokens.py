@@ -14,11 +14,9 @@ from typing import Sequence
 import torch
 import torch.nn as nn
 
-from . import lib
-
-
-def _ru(x, m):
-    return (x + m - 1) // m * m
+from . import gemm, lib
+from .gemm import round_up as _ru
+from .plan import DerivedState
 
 
 class _MLN(nn.Module):                      # parameter container: models/utils/misc.py:161-172
@@ -34,7 +32,7 @@ class _SE(nn.Module):                       # models/utils/misc.py:140-145
         self.conv_reduce, self.conv_expand = nn.Linear(ch, ch), nn.Linear(ch, ch)
 
 
-class HeadTokenEmbedding(nn.Module):
+class HeadTokenEmbedding(DerivedState, nn.Module):
     def __init__(self, in_channels=256, embed_dims=256, depth_num=64, depth_start=1.0, LID=True, stride=16,
                  position_range: Sequence[float] = (-61.2, -61.2, -10.0, 61.2, 61.2, 10.0), precision="fp32", **unused):
         super().__init__()
@@ -53,29 +51,15 @@ class HeadTokenEmbedding(nn.Module):
             cd = depth_start + (pr[3] - depth_start) / depth_num * index
         self.register_buffer("coords_d", cd, persistent=False)
         self._pr = pr                                                       # host copy: the C ABI takes position_range from the host
-        self._packed = None
-        self._ws = {}
+        self._drop_derived()
 
-    def _load_from_state_dict(self, *a, **k):
-        self._packed = None
-        return super()._load_from_state_dict(*a, **k)
-
-    def _apply(self, fn, *a, **k):
-        self._packed = None
-        return super()._apply(fn, *a, **k)
+    # packed weights and the workspaces (keyed by shape only: they are the old device's after a move) are derived state
+    _DERIVED = dict(_packed=None, _ws={})
 
     def _pack(self, dev):
-        dt = lib.BF16 if self.precision == "bf16" else lib.F32
-        tdt = torch.bfloat16 if self.precision == "bf16" else torch.float32
-        s = lib.stream_ptr()
-
-        def pack(lin):
-            wgt = lin.weight.detach().float().contiguous()
-            N, K = wgt.shape
-            out = torch.empty(_ru(N, 128), _ru(K, 64), dtype=tdt, device=dev)
-            lib.call("toc3d_pack_weight", dt, wgt, N, K, out, out.shape[0], out.shape[1], s)
-            return out, lin.bias.detach().float().contiguous()
-        P = dict(dt=dt, tdt=tdt, pe0=pack(self.position_encoder[0]), pe2=pack(self.position_encoder[2]), me0=pack(self.memory_embed[0]),
+        dts = gemm.dtypes(self.precision)
+        pack = lambda lin: (gemm.pack_weight(lin.weight, dts, dev), lin.bias.detach().float().contiguous())
+        P = dict(dt=dts.act, tdt=dts.torch, pe0=pack(self.position_encoder[0]), pe2=pack(self.position_encoder[2]), me0=pack(self.memory_embed[0]),
                  me2=pack(self.memory_embed[2]), red=pack(self.spatial_alignment.reduce[0]), gam=pack(self.spatial_alignment.gamma),
                  bet=pack(self.spatial_alignment.beta), se1=pack(self.featurized_pe.conv_reduce), se2=pack(self.featurized_pe.conv_expand))
         torch.cuda.current_stream().synchronize()

@@ -170,23 +170,24 @@ def call(name: str, *args):
         raise RuntimeError(f"{name} failed ({rc}): {lib.toc3d_last_error().decode()}")
 
 
+def ptr_arrays(tensors, min_len=0):
+    """(void* [n], int64 [n]): the device pointers and byte counts of ``tensors``, as the ABI's pointer-list arguments take them (n >= min_len, zero filled)."""
+    n = max(min_len, len(tensors))
+    return (ctypes.c_void_p * n)(*[t.data_ptr() for t in tensors]), (ctypes.c_int64 * n)(*[t.numel() * t.element_size() for t in tensors])
+
+
 def copy_segments(pairs, stream):
     """[(dst tensor, src tensor), ...] (same byte sizes) staged with one toc3d_copy_segments launch per 16 pairs."""
     for i in range(0, len(pairs), 16):
         chunk = pairs[i:i + 16]
-        n = len(chunk)
-        d = (ctypes.c_void_p * n)(*[t.data_ptr() for t, _ in chunk])
-        s = (ctypes.c_void_p * n)(*[t.data_ptr() for _, t in chunk])
-        b = (ctypes.c_int64 * n)(*[t.numel() * t.element_size() for t, _ in chunk])
-        call("toc3d_copy_segments", n, d, s, b, stream)
+        d, b = ptr_arrays([t for t, _ in chunk])
+        s, _ = ptr_arrays([t for _, t in chunk])
+        call("toc3d_copy_segments", len(chunk), d, s, b, stream)
 
 
 def prefetch(tensors, workgroups, stream):
     """One toc3d_prefetch launch over up to 8 (contiguous) device tensors."""
-    n = len(tensors)
-    p = (ctypes.c_void_p * n)(*[t.data_ptr() for t in tensors])
-    b = (ctypes.c_int64 * n)(*[t.numel() * t.element_size() for t in tensors])
-    call("toc3d_prefetch", n, p, b, workgroups, stream)
+    call("toc3d_prefetch", len(tensors), *ptr_arrays(tensors), workgroups, stream)
 
 
 # Lane of the launch plan being recorded by THIS thread (toc3d_amd/plan.py); None = launch on torch's current stream.  Thread-local

@@ -12,10 +12,8 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-
-from . import lib
-from .backbone import _round_up, tuned_linear
-from .plan import MODES, run_frame
+from . import gemm, lib
+from .plan import MODES, DerivedState, run_frame
 
 
 class _ConvModule(nn.Module):
@@ -24,7 +22,7 @@ class _ConvModule(nn.Module):
         self.conv = nn.Conv2d(cin, cout, k, padding=padding)
 
 
-class CPFPN(nn.Module):
+class CPFPN(DerivedState, nn.Module):
     def __init__(self, in_channels, out_channels, num_outs, start_level=0, end_level=-1, add_extra_convs=False,
                  relu_before_extra_convs=False, no_norm_on_lateral=False, conv_cfg=None, norm_cfg=None, act_cfg=None,
                  upsample_cfg=dict(mode="nearest"), init_cfg=None, precision=None, **unused):
@@ -34,7 +32,7 @@ class CPFPN(nn.Module):
                 or act_cfg is not None or conv_cfg is not None or num_outs not in (1, 2)):
             raise NotImplementedError("CPFPN is built for the shipped single-level configuration (in_channels=[C], num_outs<=2)")
         if precision is None:
-            from .backbone import DEFAULT_PRECISION as precision       # the path that meets the reference's 1e-3 (backbone.py); bf16 is an explicit opt-in
+            precision = gemm.DEFAULT_PRECISION                         # the path that meets the reference's 1e-3 (gemm.py); bf16 is an explicit opt-in
         assert precision in ("bf16", "fp32", "fp32x3", "fp32x6")
         self.in_channels, self.out_channels, self.num_outs = in_channels, out_channels, num_outs
         self.precision = precision
@@ -45,74 +43,27 @@ class CPFPN(nn.Module):
             if isinstance(m, nn.Conv2d):
                 nn.init.xavier_uniform_(m.weight)
                 nn.init.zeros_(m.bias)
-        self._packed = None
-        self._ws = {}
-        self._tuned = {}                # (epilogue, M, N, K) -> GEMM tile variant (toc3d_amd.backbone.tuned_linear); bench.py shares the backbone's table
+        self._drop_derived()
+        self._tuned = {}                # (epilogue, M, N, K) -> GEMM tile variant (toc3d_amd.gemm.linear); bench.py shares the backbone's table
         self.autotune = True
         self.alias_outputs = False      # True: the returned level-0 tensor is the reused workspace (benchmarks, fused pipelines)
         self.launch_mode = unused.get("launch_mode", "plan")            # see toc3d_amd/plan.py
         assert self.launch_mode in MODES
         self._stream_pool = []
 
-    @property
-    def _dt(self):
-        return lib.BF16 if self.precision == "bf16" else lib.F32
-
-    @property
-    def _dt_gemm(self):
-        return {"fp32x3": lib.F32X3W, "fp32x6": lib.F32X6}.get(self.precision, self._dt)      # fp32x3: weights as (hi, lo) planes (include/toc3d.h)
-
-    def load_state_dict(self, *a, **k):
-        self._packed = None
-        self._ws = {}
-        return super().load_state_dict(*a, **k)
-
-    def _apply(self, fn, *a, **k):
-        self._packed = None
-        self._ws = {}
-        return super()._apply(fn, *a, **k)
-
-    def _load_from_state_dict(self, *a, **k):
-        # weights that arrive through the parent detector (mmcv load_checkpoint -> detector.load_state_dict) reach this module only
-        # here: the packed weights and the recorded launch plans (they point into them) are stale from then on
-        self._packed = None
-        self._ws = {}
-        return super()._load_from_state_dict(*a, **k)
-
-    # copies / pickles start without workspaces, packed weights and recorded plans (see _BackboneBase.__getstate__)
-    def __getstate__(self):
-        d = dict(self.__dict__)
-        d["_packed"], d["_ws"], d["_stream_pool"] = None, {}, []
-        return d
-
-    def __deepcopy__(self, memo):
-        import copy
-        new = self.__class__.__new__(self.__class__)
-        memo[id(self)] = new
-        for k, v in self.__getstate__().items():
-            new.__dict__[k] = copy.deepcopy(v, memo)
-        return new
+    # packed weights, workspaces and the recorded launch plans inside them are derived state (plan.DerivedState): weights that arrive through the
+    # parent detector (mmcv load_checkpoint -> detector.load_state_dict) reach this module only in _load_from_state_dict, which drops them too
+    _DERIVED = dict(_packed=None, _ws={}, _sk_ws={}, _sk_ws_old=[])
+    _INSTANCE = dict(_stream_pool=[])
 
     def _pack(self, dev):
-        dt = lib.BF16 if self.precision == "bf16" else lib.F32
-        tdt = torch.bfloat16 if self.precision == "bf16" else torch.float32
-        s = lib.stream_ptr()
-
-        def pack(w2d):
-            w2d = w2d.detach().float().contiguous()
-            N, K = w2d.shape
-            out = torch.empty(_round_up(N, 128), _round_up(K, 64), dtype=tdt, device=dev)
-            lib.call("toc3d_pack_weight", dt, w2d, N, K, out, out.shape[0], out.shape[1], s)
-            if self.precision == "fp32x3":
-                lib.call("toc3d_x3_planes", out, out.shape[1], out, out.shape[1], out.shape[0], out.shape[1], s)
-            return out
-
+        dts = gemm.dtypes(self.precision)
         lw = self.lateral_convs[0].conv
         fw = self.fpn_convs[0].conv
-        P = dict(dt=dt, tdt=tdt,
-                 w_lat=pack(lw.weight.reshape(self.out_channels, -1)), b_lat=lw.bias.detach().float().contiguous(),
+        P = dict(dt=dts.act, tdt=dts.torch,
+                 w_lat=gemm.pack_weight(lw.weight.reshape(self.out_channels, -1), dts, dev), b_lat=lw.bias.detach().float().contiguous(),
                  # (Cout, Cin, ky, kx) -> (Cout, ky, kx, Cin) to match toc3d_im2col_3x3's column order
-                 w_fpn=pack(fw.weight.permute(0, 2, 3, 1).reshape(self.out_channels, -1)), b_fpn=fw.bias.detach().float().contiguous())
+                 w_fpn=gemm.pack_weight(fw.weight.permute(0, 2, 3, 1).reshape(self.out_channels, -1), dts, dev), b_fpn=fw.bias.detach().float().contiguous())
         torch.cuda.current_stream().synchronize()
         return P
 
@@ -156,13 +107,12 @@ class CPFPN(nn.Module):
             # [M, 9*C] im2col matrix (27 MB per frame, one launch) is gone.  Both with a per-shape autotuned tile (N = 256 leaves 94 tiles of
             # 128x128 for 256 CUs: the default tile is the wrong one).
             if ws["implicit"]:
-                tuned_linear(self, lib.EPI_BIAS, a, Kl, P["w_lat"], Kl, P["b_lat"], ws["lat"], Co, None, 0, 0, None, None, M, Co, Kl, 0)
-                tuned_linear(self, lib.EPI_CONV3X3, ws["lat"], Co, P["w_fpn"], Kf, P["b_fpn"], ws["o0"], Co, None, 0, 0, None, None, M, Co, Kf, 0,
-                             fused=(None, 0, None, 0, None, 0, 0.0, ws["zeros"], (h << 32) | w, None))
+                gemm.linear(self, lib.EPI_BIAS, a, P["w_lat"], P["b_lat"], ws["lat"], M, Co, Kl)
+                gemm.linear(self, lib.EPI_CONV3X3, ws["lat"], P["w_fpn"], P["b_fpn"], ws["o0"], M, Co, Kf, conv=(ws["zeros"], h, w))
             else:                                        # channel counts that are not multiples of 64 (test configs): materialised im2col rows
-                tuned_linear(self, lib.EPI_RESIDUAL, a, Kl, P["w_lat"], Kl, P["b_lat"], ws["lat"], Co, None, 0, 0, None, None, M, Co, Kl, 0)
+                gemm.linear(self, lib.EPI_RESIDUAL, a, P["w_lat"], P["b_lat"], ws["lat"], M, Co, Kl)
                 lib.call("toc3d_im2col_3x3", dt, ws["lat"], ws["col"], Kf, V, h, w, Co, s)
-                tuned_linear(self, lib.EPI_RESIDUAL, ws["col"], Kf, P["w_fpn"], Kf, P["b_fpn"], ws["o0"], Co, None, 0, 0, None, None, M, Co, Kf, 0)
+                gemm.linear(self, lib.EPI_RESIDUAL, ws["col"], P["w_fpn"], P["b_fpn"], ws["o0"], M, Co, Kf)
             lib.call("toc3d_nhwc_to_nchw", ws["o0"], ws["out0"], V, h * w, Co, s)
 
         # The launch sequence names the input buffer: it can be recorded (and replayed with one C call) only for an input that sits

@@ -113,8 +113,8 @@ def load_packed(model, path: str):
     P = _listify(root)
     P["pos"] = {tuple(int(i) for i in k.split("x")): v for k, v in P.get("pos", {}).items()}
     P["dev"] = dev
+    model._drop_derived()                  # recorded launch plans point into the previous packed buffers
     model._packed = P
-    model._plans = {}                      # recorded launch plans point into the previous packed buffers
 
 
 def convert_checkpoint(ckpt_path: str, cfg: dict, out_path: str, prefix: str = "img_backbone.", device: str = "cuda",

@@ -13,6 +13,7 @@ far on lane b".  Two executors implement that vocabulary:
 from __future__ import annotations
 
 import contextlib
+import copy
 from typing import List
 
 import torch
@@ -77,6 +78,43 @@ class LaunchPlan:
                 self.handle = None
         except Exception:  # noqa: BLE001  (interpreter shutdown)
             pass
+
+
+class DerivedState:
+    """Mixin (in front of ``nn.Module``) for modules that keep packed weights, workspaces and recorded plans: device buffers and native handles derived from
+    the parameters, pointing into each other.  The module names them in two tiers, ``{attribute: its empty value}``:
+
+    * ``_DERIVED``   -- what new weights (``load_state_dict``, directly or through a parent module) or a device move invalidate;
+    * ``_INSTANCE``  -- what additionally belongs to THIS instance only (stream pools, test instruments): kept by the above, left out of copies and pickles.
+
+    A copy / pickle starts with both tiers empty and re-packs / re-records on its first forward; everything else (tuning tables, schedule attributes) is
+    configuration and is copied."""
+    _DERIVED: dict = {}
+    _INSTANCE: dict = {}
+
+    def _drop_derived(self):
+        for k, empty in self._DERIVED.items():
+            self.__dict__[k] = copy.copy(empty)
+
+    def _load_from_state_dict(self, *a, **k):
+        self._drop_derived()
+        return super()._load_from_state_dict(*a, **k)
+
+    def _apply(self, fn, *a, **k):
+        self._drop_derived()
+        return super()._apply(fn, *a, **k)
+
+    def __getstate__(self):
+        d = dict(self.__dict__)
+        d.update((k, copy.copy(empty)) for k, empty in {**self._DERIVED, **self._INSTANCE}.items())
+        return d
+
+    def __deepcopy__(self, memo):
+        new = self.__class__.__new__(self.__class__)
+        memo[id(self)] = new
+        for k, v in self.__getstate__().items():
+            new.__dict__[k] = copy.deepcopy(v, memo)
+        return new
 
 
 class RecordExec:

@@ -69,7 +69,7 @@ orig = lib.call
 def spy(nm, *a):
     if nm == "toc3d_linear_fused":
         used.setdefault((a[1], a[15], a[16], a[17]), a[2])
-    elif nm == "toc3d_linear_qkv_rope":                       # shares the bias epilogue's table entry (toc3d_amd.backbone.tuned_linear)
+    elif nm == "toc3d_linear_qkv_rope":                       # shares the bias epilogue's table entry (toc3d_amd.gemm.linear)
         used.setdefault((lib.EPI_BIAS, a[9], a[10], a[11]), a[1])
     return orig(nm, *a)
 lib.call = spy
