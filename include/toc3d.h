@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define TOC3D_ABI_VERSION 9   /* bumped whenever entry points are added or changed; toc3d_amd/lib.py checks it before binding symbols */
+#define TOC3D_ABI_VERSION 10  /* bumped whenever entry points are added or changed; toc3d_amd/lib.py checks it before binding symbols */
 
 #define TOC3D_OK 0
 #define TOC3D_ERR_ARG (-1)
@@ -533,6 +533,42 @@ int toc3d_add_layernorm_pos(int dtype, const float* x, int64_t ldx, const float*
                             const float* gamma2, const float* beta2, float* out2, int64_t ldo2, int64_t M, int64_t E, toc3d_stream_t stream);
 int toc3d_add_pos_rows(int dtype, const float* x, int64_t ldx, const float* pos, int64_t ldp, void* out_act, int64_t ld_act, void* out_act_pos, int64_t ld_act_pos,
                        int64_t M, int64_t E, toc3d_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Output side of StreamPETRHead (csrc/head_outputs.hip): class / box branches behind the decoder and NMS-free box decoding.  Replaces the second half of
+ * StreamPETRHead.get_transformer_outputs (dense_heads/streampetr_head.py:582-602) and StreamPETRHead.get_bboxes (:1051-1071) over NMSFreeCoder.decode
+ * (core/bbox/coders/nms_free_coder.py:39-111, denormalize_bbox core/bbox/util.py:24-51).  The E -> E layers of cls_branches / reg_branches (:239-260) are
+ * toc3d_linear_fused launches; the first layers of the two towers read the same rows and run as ONE GEMM on weights concatenated along N, so both towers live in one
+ * [M, 2E] buffer: class tower in columns [0, E), box tower in [E, 2E).
+ * toc3d_head_nan_to_num_rows (:582, torch.nan_to_num): x f32 [M, ldx] -> out f32 [M, ldo] = x with NaN -> 0, +-inf -> +-FLT_MAX (exact) and / or out_act [M, ld_act] =
+ *   the same rows in the form the first GEMM reads: dtype BF16, F32 or F32X3P ((hi, lo) planes: 128-byte aligned, ld_act and E multiples of 32).  E a multiple of 4;
+ *   one thread per 4 elements, M * E / 4 <= (2^31 - 1) * 256.
+ * toc3d_head_ln_relu_rows (:242-243, :253): out_act[:, 0:E_ln] = relu(LayerNorm(x[:, 0:E_ln]; gamma, beta, eps)) (the class tower: f32 statistics, biased variance) and
+ *   out_act[:, E_ln:E_ln + E_relu] = relu(x[:, E_ln:E_ln + E_relu]) (the box tower; E_relu may be 0), x f32 [M, ldx].  dtype as above.  One wavefront per row,
+ *   E_ln, E_relu <= 1024 and multiples of 4.
+ * toc3d_head_outputs (:247, :254, :586-600): h f32 [M, ldh >= 2E] = the towers' rows BEFORE their last LayerNorm + ReLU / ReLU, which are applied on load;
+ *   cls_out f32 [M, ld_cls] = relu(LN(h[:, 0:E])) . w_cls^T + b_cls (w_cls f32 [num_cls, E], unpadded); bbox_out f32 [M, ld_bbox] = relu(h[:, E:2E]) . w_reg^T + b_reg
+ *   (w_reg f32 [code_size, E]) with columns 0:3 <- sigmoid(. + inverse_sigmoid(reference_points[m % ref_rows])) * (pc_range[3:6] - pc_range[0:3]) + pc_range[0:3]
+ *   (inverse_sigmoid as mmdet: clamp to [0, 1], eps 1e-5; reference_points f32 [ref_rows, 3] on the device, pc_range 6 floats on the HOST, read at call time).
+ *   Both weight blocks sit in LDS ((num_cls + code_size) * E * 4 <= 64 KB), one wavefront per row, products in f32 FMA, libm exp / log.
+ * toc3d_nms_free_decode (nms_free_coder.py:39-111, streampetr_head.py:1066): cls_scores f32 [B, Q, ld_cls] logits, bbox_preds f32 [B, Q, ld_bbox]; per sample the
+ *   max_num largest sigmoid(logit) of the Q * num_classes values in descending order, ties to the lowest flat index; label = index % num_classes, query = index /
+ *   num_classes; the gathered box rows through denormalize_bbox (exp of columns 3:6, atan2(col 6, col 7), velocity columns 8, 9 kept when code_size >= 10; code_size
+ *   8 -> 7 output columns); survivors of centre in post_center_range (6 floats on the HOST, inclusive at both ends) and, if use_threshold, score >= score_threshold
+ *   are compacted in score order; sub_half_height applies z -= h / 2 after the mask.  Outputs of fixed capacity: boxes f32 [B, max_num, 9 or 7], scores f32
+ *   [B, max_num], labels / query_index int64 [B, max_num], counts int64 [B]; rows past a sample's count are zero (indices -1).  The inputs are not modified.
+ *   One workgroup per sample, keys in registers: Q * num_classes <= 16384, max_num <= min(2048, Q * num_classes); no atomics (bit-stable order). */
+int toc3d_head_nan_to_num_rows(int dtype, const float* x, int64_t ldx, float* out, int64_t ldo, void* out_act, int64_t ld_act, int64_t M, int64_t E,
+                               toc3d_stream_t stream);
+int toc3d_head_ln_relu_rows(int dtype, const float* x, int64_t ldx, const float* gamma, const float* beta, float eps, void* out_act, int64_t ld_act,
+                            int64_t M, int64_t E_ln, int64_t E_relu, toc3d_stream_t stream);
+int toc3d_head_outputs(const float* h, int64_t ldh, const float* gamma, const float* beta, float eps, const float* w_cls, const float* b_cls,
+                       const float* w_reg, const float* b_reg, const float* reference_points, int64_t ref_rows, const float* pc_range,
+                       float* cls_out, int64_t ld_cls, float* bbox_out, int64_t ld_bbox, int64_t M, int64_t E, int64_t num_cls, int64_t code_size,
+                       toc3d_stream_t stream);
+int toc3d_nms_free_decode(const float* cls_scores, int64_t ld_cls, const float* bbox_preds, int64_t ld_bbox, int64_t B, int64_t Q, int64_t num_classes,
+                          int64_t code_size, int64_t max_num, const float* post_center_range, int use_threshold, float score_threshold, int sub_half_height,
+                          float* boxes, float* scores, int64_t* labels, int64_t* query_index, int64_t* counts, toc3d_stream_t stream);
 
 /* Plain device-to-device copy as a kernel (recordable into a launch plan, unlike hipMemcpyAsync). */
 int toc3d_copy_bytes(void* dst, const void* src, int64_t nbytes, toc3d_stream_t stream);

@@ -56,19 +56,7 @@ class _Decoder(nn.Module):
         self.embed_dims = embed_dims
 
 
-SPLITK_VARIANT = 4014     # four K slices on 64x64 tiles, added in slice order (include/toc3d.h, the fused GEMM's split-K entry point)
-
-
-def _tile_variant(M, N, K, residual):
-    """GEMM tile variant (include/toc3d.h, toc3d_linear_ex) for a decoder GEMM.  The query-side GEMMs have M = 900 rows: the library's default 128x128 tile
-    makes 16 workgroups of the N = 256 ones on a 256-CU chip.  Measured at M = 900 (profiles/decoder_gemm_small_m.txt): 64x64 tiles (variant 14) win every shape
-    of fewer than 256 default tiles in fp32x3 and tie in bf16; the FFN's second layer (K = 2048 into N = 256) wants the K dimension cut as well -- 62 -> 18 us
-    (fp32x3), 22 -> 11 us (bf16) with the deterministic four-way split-K.  0 = the library's heuristic (the M = 6000 key / value projections)."""
-    if ((M + 127) // 128) * ((N + 127) // 128) >= 256:
-        return 0
-    if residual and K >= 1024 and K % 512 == 0:
-        return SPLITK_VARIANT
-    return 14
+SPLITK_VARIANT, _tile_variant = gemm.SPLITK_VARIANT, gemm.small_m_variant      # the tile choice for query-side GEMMs, shared with head_outputs.py
 
 
 def _parse(encoder, decoder):

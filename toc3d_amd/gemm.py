@@ -89,8 +89,24 @@ def pack_weight(w: torch.Tensor, dts: Dtypes, device=None):
 
 # ------------------------------------------------------------------------------------------------
 # the launcher
+SPLITK_VARIANT = 4014     # four K slices on 64x64 tiles, added in slice order (include/toc3d.h, the fused GEMM's split-K entry point)
+
+
+def small_m_variant(M, N, K, residual):
+    """GEMM tile variant (include/toc3d.h, toc3d_linear_ex) for a query-side GEMM (the decoder's, the head branches').  These have M = 900 .. 5400 rows: the
+    library's default 128x128 tile makes 16 workgroups of the M = 900, N = 256 ones on a 256-CU chip.  Measured at M = 900 (profiles/decoder_gemm_small_m.txt):
+    64x64 tiles (variant 14) win every shape of fewer than 256 default tiles in fp32x3 and tie in bf16; the FFN's second layer (K = 2048 into N = 256) wants the K
+    dimension cut as well -- 62 -> 18 us (fp32x3), 22 -> 11 us (bf16) with the deterministic four-way split-K.  0 = the library's heuristic (the M = 6000 key /
+    value projections)."""
+    if ((M + 127) // 128) * ((N + 127) // 128) >= 256:
+        return 0
+    if residual and K >= 1024 and K % 512 == 0:
+        return SPLITK_VARIANT
+    return 14
+
+
 # ------------------------------------------------------------------------------------------------
-_flush = None                   # 256 MB scratch shared by all models: evicts L2 + Infinity Cache between tuning launches
+_flush = None                  # 256 MB scratch shared by all models: evicts L2 + Infinity Cache between tuning launches
 
 # + 100: 8 row bands per XCD.  The 2-D XCD partitions (+ 200 / + 300, round 3) win 6-20 % on isolated cold w1|w2 / w3 launches and nothing inside the frame
 # (profiles/r03_xcd_order_sweep.txt): they stay available through the C ABI but are not tuning candidates.

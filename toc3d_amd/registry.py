@@ -1,8 +1,10 @@
-"""Registry surface: ``ToC3DEVAViT`` / ``EVA_ViT`` on mmdet's BACKBONES, ``CPFPN`` on NECKS, ``PETRTemporalTransformer`` on TRANSFORMER.
+"""Registry surface: ``ToC3DEVAViT`` / ``EVA_ViT`` on mmdet's BACKBONES, ``CPFPN`` on NECKS, ``PETRTemporalTransformer`` on TRANSFORMER, ``NMSFreeCoder`` on
+BBOX_CODERS.
 
 The reference registers its classes with ``@BACKBONES.register_module()`` (``toc3d_eva_vit.py:25``,
 ``eva_vit.py:270``), ``@NECKS.register_module()`` (``cp_fpn.py:15``) and ``@TRANSFORMER.register_module()``
-(``utils/petr_transformer.py:430``); configs name them by ``type=``.
+(``utils/petr_transformer.py:430``), its box coder with ``@BBOX_CODERS.register_module()`` (``core/bbox/coders/nms_free_coder.py:8``); configs name them
+by ``type=``.
 When mmdet is importable the same names are registered there (``force=True`` so this package can shadow the
 reference plugin); otherwise a shim registry with the same ``register_module()/build(cfg)`` API is used.
 """
@@ -40,13 +42,18 @@ try:  # pragma: no cover
     from mmdet.models.utils.builder import TRANSFORMER
 except Exception:  # noqa: BLE001
     TRANSFORMER = _ShimRegistry("transformer")
+try:  # pragma: no cover
+    from mmdet.core.bbox.builder import BBOX_CODERS
+except Exception:  # noqa: BLE001
+    BBOX_CODERS = _ShimRegistry("bbox_coder")
 
 
 def register_all():
     from .backbone import EVA_ViT, ToC3DEVAViT
     from .decoder import PETRTemporalTransformer
+    from .head_outputs import NMSFreeCoder
     from .neck import CPFPN
-    for reg, cls in ((BACKBONES, ToC3DEVAViT), (BACKBONES, EVA_ViT), (NECKS, CPFPN), (TRANSFORMER, PETRTemporalTransformer)):
+    for reg, cls in ((BACKBONES, ToC3DEVAViT), (BACKBONES, EVA_ViT), (NECKS, CPFPN), (TRANSFORMER, PETRTemporalTransformer), (BBOX_CODERS, NMSFreeCoder)):
         try:
             reg.register_module(name=cls.__name__, force=True, module=cls)
         except TypeError:
@@ -63,3 +70,7 @@ def build_neck(cfg, **kw):
 
 def build_transformer(cfg, **kw):
     return TRANSFORMER.build(cfg, **kw) if isinstance(TRANSFORMER, _ShimRegistry) else TRANSFORMER.build(dict(cfg, **kw))
+
+
+def build_bbox_coder(cfg, **kw):
+    return BBOX_CODERS.build(cfg, **kw) if isinstance(BBOX_CODERS, _ShimRegistry) else BBOX_CODERS.build(dict(cfg, **kw))

@@ -424,3 +424,60 @@ def decoder_inputs(sizes: dict, shape: dict, seed: int = 0, with_temp: bool = Tr
     if with_temp:
         out["temp_memory"], out["temp_pos"] = r(B, Nm, E), r(B, Nm, E)
     return out
+
+
+# ---- output side of the head (toc3d_amd.HeadOutputs, toc3d_amd.NMSFreeCoder) -----------------------------------------------------------------
+HEAD_OUTPUTS_FULL = dict(num_classes=10, embed_dims=256, num_reg_fcs=2, code_size=10, num_pred=6)       # streampetr_head.py:85-111, ToC3D_faster.py:99-146
+HEAD_OUTPUTS_TINY = dict(num_classes=10, embed_dims=64, num_reg_fcs=2, code_size=10, num_pred=2)
+# shapes of the two fixtures (tools/gen_golden_head_outputs.py): decoder levels, batch, queries; nonfinite = NaN / +-inf entries in outs_dec
+HEAD_OUTPUTS_FULL_SHAPE = dict(L=6, B=1, Q=900, nonfinite=False)
+HEAD_OUTPUTS_TINY_SHAPE = dict(L=2, B=2, Q=32, nonfinite=True)
+PC_RANGE = [-51.2, -51.2, -5.0, 51.2, 51.2, 3.0]                                                       # point_cloud_range of the shipped configs
+
+
+def bbox_coder_cfg(max_num: int = 300, post_center_range=None, score_threshold=None) -> dict:
+    """The ``bbox_coder=dict(...)`` block of the shipped configs (projects/configs/ToC3D/ToC3D_faster.py:140-146)."""
+    cfg = dict(type="NMSFreeCoder", post_center_range=[-61.2, -61.2, -10.0, 61.2, 61.2, 10.0] if post_center_range is None else list(post_center_range),
+               pc_range=list(PC_RANGE), max_num=max_num, voxel_size=[0.2, 0.2, 8], num_classes=10)
+    if score_threshold is not None:
+        cfg["score_threshold"] = score_threshold
+    return cfg
+
+
+def head_outputs_state_dict(sizes: dict, seed: int = 0):
+    """Seeded weights under the reference's state-dict names (``pts_bbox_head.cls_branches.*`` / ``reg_branches.*``): the ``num_pred`` levels hold ONE module
+    (streampetr_head.py:257-260), so every level's keys carry the same tensors.  Biases non-zero, LayerNorm weights 1 + noise, the last class bias near
+    ``bias_init_with_prob(0.01)`` = -4.6 so that the scores look like a trained head's (a few confident ones over a floor near 0.01)."""
+    g = torch.Generator().manual_seed(9000 + seed)
+    E, NC, CS, P = sizes["embed_dims"], sizes["num_classes"], sizes["code_size"], sizes["num_pred"]
+    r = lambda *s: torch.randn(*s, generator=g)
+    one = OrderedDict()
+    for i in (0, 3):
+        one[f"cls.{i}.weight"], one[f"cls.{i}.bias"] = r(E, E) * E ** -0.5, r(E) * 0.1
+        one[f"cls.{i + 1}.weight"], one[f"cls.{i + 1}.bias"] = 1.0 + 0.1 * r(E), 0.1 * r(E)
+    one["cls.6.weight"], one["cls.6.bias"] = r(NC, E) * 2.0 * E ** -0.5, -4.6 + 0.3 * r(NC)
+    for i in (0, 2):
+        one[f"reg.{i}.weight"], one[f"reg.{i}.bias"] = r(E, E) * (2.0 / E) ** 0.5, r(E) * 0.1
+    one["reg.4.weight"], one["reg.4.bias"] = r(CS, E) * E ** -0.5, r(CS) * 0.1
+    sd = OrderedDict()
+    for branch in ("cls", "reg"):
+        for lvl in range(P):
+            for k, v in one.items():
+                if k.startswith(branch):
+                    sd[f"{branch}_branches.{lvl}.{k[4:]}"] = v
+    return sd
+
+
+def head_outputs_inputs(sizes: dict, shape: dict, seed: int = 0):
+    """Seeded ``outs_dec`` (L, B, Q, E) (unit-variance rows, as the decoder's post_norm leaves them) and ``reference_points`` (B, Q, 3) in [0, 1].  With
+    ``shape['nonfinite']`` (the tiny case): NaN entries on every level, +-inf entries on level 0 only (``nan_to_num`` turns them into +-FLT_MAX, which the
+    linear layers overflow on: the last level, which decoding reads, stays finite), and reference points exactly at 0 and 1 and below the 1e-5 clamp."""
+    g = torch.Generator().manual_seed(9500 + seed)
+    L, B, Q, E = shape["L"], shape["B"], shape["Q"], sizes["embed_dims"]
+    outs = torch.randn(L, B, Q, E, generator=g)
+    ref = torch.rand(B, Q, 3, generator=g)
+    if shape.get("nonfinite"):
+        outs[0, 0, 3, 5], outs[L - 1, B - 1, 7, E - 1], outs[L - 1, 0, 0, 0] = float("nan"), float("nan"), float("nan")
+        outs[0, 0, 9, 1], outs[0, B - 1, 11, 2] = float("inf"), float("-inf")
+        ref[0, 1], ref[0, 2, 0], ref[B - 1, 4, 1], ref[B - 1, 5, 2] = torch.tensor([0.0, 1.0, 0.5]), 3e-6, 1.0 - 3e-6, 0.0
+    return dict(outs_dec=outs, reference_points=ref)
