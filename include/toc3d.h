@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define TOC3D_ABI_VERSION 10  /* bumped whenever entry points are added or changed; toc3d_amd/lib.py checks it before binding symbols */
+#define TOC3D_ABI_VERSION 11  /* bumped whenever entry points are added or changed; toc3d_amd/lib.py checks it before binding symbols */
 
 #define TOC3D_OK 0
 #define TOC3D_ERR_ARG (-1)
@@ -569,6 +569,38 @@ int toc3d_head_outputs(const float* h, int64_t ldh, const float* gamma, const fl
 int toc3d_nms_free_decode(const float* cls_scores, int64_t ld_cls, const float* bbox_preds, int64_t ld_bbox, int64_t B, int64_t Q, int64_t num_classes,
                           int64_t code_size, int64_t max_num, const float* post_center_range, int use_threshold, float score_threshold, int sub_half_height,
                           float* boxes, float* scores, int64_t* labels, int64_t* query_index, int64_t* counts, toc3d_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Query side of StreamPETRHead (csrc/head_queries.hip): from the temporal memory bank to the decoder's inputs.  Replaces StreamPETRHead.forward
+ * (dense_heads/streampetr_head.py:641-652) and StreamPETRHead.temporal_alignment (:424-453) around their Linear layers, which are toc3d_linear_fused launches.
+ * E must be 256 (pos2posemb3d yields 3 * 128 columns, pos2posemb1d 256, MLN(180) has f_dim 256).  Rows are the B * n memory entries, sample-major.
+ * toc3d_head_query_inputs (:427-428, :437-438, :443; models/utils/positional_encoding.py:14-81): the three GEMM A operands in ONE launch, dtype BF16, F32 or F32X3P
+ *   ((hi, lo) planes: 128-byte aligned, leading dimensions multiples of 32):
+ *     pos3d [B n, ld_pos >= 384] = pos2posemb3d((reference_point - pc_range[0:3]) / (pc_range[3:6] - pc_range[0:3])), concatenated (y, x, z);
+ *     nerf  [B n, ld_nerf >= 192] = nerf_positional_encoding(cat([velo, timestamp, egopose[:3, :]]).float()), frequency-major (for each of 6 frequencies the sin of
+ *           all 15 scalars, then the cos): 180 columns, columns 180..191 written as zeros (the K padding of the GEMM); NULL = not wanted (with_ego_pos = False);
+ *     t1d   [B n, ld_t1d >= 256] = pos2posemb1d(timestamp) evaluated in f64 and rounded once to f32.
+ *   reference_point f32 [B][n][3], velo f32 [B][n][2], timestamp f64 [B][n], egopose f32 [B][n][4][4]: each with its own sample stride in ELEMENTS (the bank's views
+ *   of capacity buffers go in as they are).  pc_range: 6 floats on the HOST, read at call time.  dim_t3 f32 [128] / dim_t1 f32 [256]: the dim_t tables on the device,
+ *   computed by the host with the reference's expression (a 1-ulp change of dim_t changes results).  Arguments are formed as (p * float(2 pi)) / dim_t with correctly
+ *   rounded division; sinf / cosf / sin / cos are the range-reduced libm forms.  The normalised reference points of rows r < np of sample b are also written to
+ *   ref_out + b * ref_out_stride + 3 r (the tail of the concatenated reference_points, :448); np = 0: ref_out may be NULL.
+ * toc3d_head_query_combine (:439-451; models/utils/misc.py:181-188): one wavefront per row,
+ *     temp_pos    = gamma_pe * LN0(qe) + beta_pe + LN(te; ln_weight, ln_bias, ln_eps)
+ *     temp_memory = gamma_mem * LN0(memory_embedding) + beta_mem
+ *   LN0 = LayerNorm without affine, eps 1e-5, f32 statistics (a zero row gives exactly zero); qe, te f32 [B n, ld]; gb_pe / gb_mem f32 [B n, ld >= 512] = gamma in columns
+ *   [0, 256), beta in [256, 512) (one N = 512 GEMM per MLN), or NULL = that MLN is skipped (with_ego_pos = False: temp_pos = qe + LN(te), temp_memory =
+ *   memory_embedding); memory_embedding f32 [B][n][256] with sample stride mem_stride and row stride ld_mem.  Rows r < np of sample b are stored to query_pos_tail +
+ *   b * query_pos_stride + r * ld_tail and tgt_tail + b * tgt_stride + r * ld_tail (the torch.cat of :446-447 as store addresses), rows r >= np to row
+ *   b (n - np) + r - np of temp_pos / temp_memory [B (n - np), ld_temp] (:450-451).  All f32, 16-byte aligned, leading dimensions and strides multiples of 4. */
+int toc3d_head_query_inputs(int dtype, const float* reference_point, int64_t ref_stride, const float* velo, int64_t velo_stride, const double* timestamp,
+                            int64_t ts_stride, const float* egopose, int64_t pose_stride, const float* pc_range, const float* dim_t3, const float* dim_t1,
+                            void* pos3d, int64_t ld_pos, void* nerf, int64_t ld_nerf, void* t1d, int64_t ld_t1d, float* ref_out, int64_t ref_out_stride,
+                            int64_t B, int64_t n, int64_t np, int64_t E, toc3d_stream_t stream);
+int toc3d_head_query_combine(const float* qe, int64_t ld_qe, const float* gb_pe, int64_t ld_gb_pe, const float* te, int64_t ld_te, const float* ln_weight,
+                             const float* ln_bias, float ln_eps, const float* memory_embedding, int64_t mem_stride, int64_t ld_mem, const float* gb_mem,
+                             int64_t ld_gb_mem, float* query_pos_tail, int64_t query_pos_stride, float* tgt_tail, int64_t tgt_stride, int64_t ld_tail,
+                             float* temp_pos, float* temp_memory, int64_t ld_temp, int64_t B, int64_t n, int64_t np, int64_t E, toc3d_stream_t stream);
 
 /* Plain device-to-device copy as a kernel (recordable into a launch plan, unlike hipMemcpyAsync). */
 int toc3d_copy_bytes(void* dst, const void* src, int64_t nbytes, toc3d_stream_t stream);

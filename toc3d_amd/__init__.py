@@ -10,9 +10,10 @@ from .memory import TemporalMemory
 from .head_tokens import HeadTokenEmbedding
 from .decoder import PETRTemporalTransformer
 from .head_outputs import HeadOutputs, NMSFreeCoder
+from .head_queries import HeadQueries
 from .registry import BACKBONES, BBOX_CODERS, NECKS, TRANSFORMER, build_backbone, build_bbox_coder, build_neck, build_transformer, register_all
 
 register_all()
 
 __all__ = ["ToC3DEVAViT", "EVA_ViT", "CPFPN", "ToC3DViTReturnType", "BACKBONES", "NECKS", "build_backbone", "build_neck", "prepare_images", "TemporalMemory", "HeadTokenEmbedding",
-           "PETRTemporalTransformer", "TRANSFORMER", "build_transformer", "HeadOutputs", "NMSFreeCoder", "BBOX_CODERS", "build_bbox_coder"]
+           "PETRTemporalTransformer", "TRANSFORMER", "build_transformer", "HeadOutputs", "HeadQueries", "NMSFreeCoder", "BBOX_CODERS", "build_bbox_coder"]

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, os.environ.get("TOC3D_LIB", "libtoc3d_gfx950.so"))       # TOC3D_LIB: a development build beside the shipped one (library A/B runs)
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "toc3d.h")
 
-ABI_VERSION = 10                # == TOC3D_ABI_VERSION of include/toc3d.h (tests/test_cpu_abi.py cross-checks)
+ABI_VERSION = 11                # == TOC3D_ABI_VERSION of include/toc3d.h (tests/test_cpu_abi.py cross-checks)
 F32, BF16, F32X3, F32X6, F32X3W, F32X3P, F32X3WO, F32X3WA = 0, 1, 2, 3, 4, 5, 6, 7          # F32X3: linear layers only -- f32 buffers, products as three bf16 MFMAs (include/toc3d.h)
 EPI_BIAS, EPI_RESIDUAL, EPI_SWIGLU, EPI_GELU, EPI_SWIGLU_STATS, EPI_RESIDUAL_LN, EPI_RESIDUAL_STATS, EPI_SWIGLU_STATS_LN, EPI_CONV3X3, EPI_QKV_ROPE = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 # q scale of the pre-rotated attention path (toc3d_linear_qkv_rope -> toc3d_window_attention_rot, head_dim 64): head_dim^-0.5 (eva_vit.py:104-109) times log2(e) --
@@ -89,6 +89,8 @@ _SIGS = {
     "toc3d_head_ln_relu_rows": "iplppfpllllp",
     "toc3d_head_outputs": "plppfppppplpplplllllp",
     "toc3d_nms_free_decode": "plpllllllpifipppppp",
+    "toc3d_head_query_inputs": "iplplplplppp" + "plplpl" + "pl" + "llll" + "p",
+    "toc3d_head_query_combine": "plplplppf" + "pllpl" + "plpll" + "ppl" + "llll" + "p",
     "toc3d_copy_bytes": "pplp",
     "toc3d_copy_segments": "lpppp",
     "toc3d_plan_create": "p",

@@ -481,3 +481,55 @@ def head_outputs_inputs(sizes: dict, shape: dict, seed: int = 0):
         outs[0, 0, 9, 1], outs[0, B - 1, 11, 2] = float("inf"), float("-inf")
         ref[0, 1], ref[0, 2, 0], ref[B - 1, 4, 1], ref[B - 1, 5, 2] = torch.tensor([0.0, 1.0, 0.5]), 3e-6, 1.0 - 3e-6, 0.0
     return dict(outs_dec=outs, reference_points=ref)
+
+
+# ---- query side of the head (toc3d_amd.HeadQueries) ----------------------------------------------------------------------------------------------------
+HEAD_QUERIES_FULL = dict(num_query=644, memory_len=1024, num_propagated=256, embed_dims=256)              # ToC3D_faster.py:99-112
+# every row count off the 4-row and 16-row tiles: 21 learned queries, 27 memory entries of which 7 are propagated (B = 2: 54 rows), 9 new entries per frame
+HEAD_QUERIES_TINY = dict(num_query=21, memory_len=27, num_propagated=7, embed_dims=256)
+HEAD_QUERIES_TINY_SHAPE = dict(B=2, topk_proposals=9, num_classes=10, frames=5)
+
+
+def head_queries_state_dict(sizes: dict, with_ego_pos: bool = True, seed: int = 0):
+    """Seeded weights under the reference's state-dict names (the query-side slice of ``pts_bbox_head.*``, streampetr_head.py:277-298).  The MLNs' ``gamma`` /
+    ``beta`` weights are random, not the reference's zero init (models/utils/misc.py:175-179), which would hide both GEMMs.  ``with_ego_pos=False`` drops the
+    MLN keys and leaves every other tensor as it is."""
+    g = torch.Generator().manual_seed(11000 + seed)
+    E = sizes["embed_dims"]
+    r = lambda *s: torch.randn(*s, generator=g)
+    sd = OrderedDict()
+    sd["reference_points.weight"] = torch.rand(sizes["num_query"], 3, generator=g)
+    for name, (o, i) in {"query_embedding.0": (E, E * 3 // 2), "query_embedding.2": (E, E), "time_embedding.0": (E, E)}.items():
+        sd[name + ".weight"], sd[name + ".bias"] = r(o, i) * i ** -0.5, r(o) * 0.1
+    sd["time_embedding.1.weight"], sd["time_embedding.1.bias"] = 1.0 + 0.1 * r(E), 0.1 * r(E)
+    for mln in ("ego_pose_pe", "ego_pose_memory"):
+        for name, (o, i) in {"reduce.0": (E, 180), "gamma": (E, E), "beta": (E, E)}.items():
+            w, b = r(o, i) * i ** -0.5, r(o) * 0.1
+            if with_ego_pos:
+                sd[f"{mln}.{name}.weight"], sd[f"{mln}.{name}.bias"] = w, (b + 1.0 if name == "gamma" else b)
+    return sd
+
+
+def head_queries_bank(sizes: dict, B: int, frame: int, seed: int = 0):
+    """A seeded memory bank as ``pre_update_memory`` leaves it (streampetr_head.py:322-346), without running the memory updates: frame 0 is the scene start
+    (zeros, the pseudo reference points and identity poses in the first ``num_propagated`` entries), later frames are populated -- unit-variance embeddings,
+    reference points inside and slightly outside pc_range, timestamps 0.5 s apart counted back from the current frame (f64), poses a few metres and degrees from
+    the identity, velocities of a few m/s."""
+    g = torch.Generator().manual_seed(12000 + 10 * seed + frame)
+    n, np_, E = sizes["memory_len"], sizes["num_propagated"], sizes["embed_dims"]
+    r = lambda *s: torch.randn(*s, generator=g)
+    lo, hi = torch.tensor(PC_RANGE[:3]), torch.tensor(PC_RANGE[3:])
+    if frame == 0:
+        ref, pose = torch.zeros(B, n, 3), torch.zeros(B, n, 4, 4)
+        ref[:, :np_] = torch.rand(np_, 3, generator=g) * (hi - lo) + lo
+        pose[:, :np_] = torch.eye(4)
+        return dict(memory_embedding=torch.zeros(B, n, E), memory_reference_point=ref, memory_timestamp=torch.zeros(B, n, 1, dtype=torch.float64),
+                    memory_egopose=pose, memory_velo=torch.zeros(B, n, 2))
+    ref = (torch.rand(B, n, 3, generator=g) * 1.1 - 0.05) * (hi - lo) + lo
+    age = torch.arange(n, dtype=torch.float64).div(max(np_, 1), rounding_mode="floor") + 1.0
+    ts = (-0.5 * age).view(1, n, 1).repeat(B, 1, 1) + 1e-3 * r(B, n, 1).double()
+    ang = 0.05 * r(B, n)
+    pose = torch.eye(4).repeat(B, n, 1, 1)
+    pose[..., 0, 0], pose[..., 0, 1], pose[..., 1, 0], pose[..., 1, 1] = torch.cos(ang), -torch.sin(ang), torch.sin(ang), torch.cos(ang)
+    pose[..., :3, 3] = r(B, n, 3) * torch.tensor([4.0, 1.0, 0.1])
+    return dict(memory_embedding=r(B, n, E), memory_reference_point=ref, memory_timestamp=ts, memory_egopose=pose, memory_velo=r(B, n, 2) * 3.0)
