@@ -55,7 +55,10 @@ extern "C" {
  *   F32X3W: W in planes (packed once: toc3d_pack_* with TOC3D_DTYPE_F32, then toc3d_x3_planes in place); A and every output plain f32.
  *   F32X3P: W and A in planes; the outputs a later GEMM multiplies -- the SwiGLU epilogues' `out`, `out_act` -- are written as planes, all others (bias / GELU /
  *           residual outputs, statistics) stay f32.  toc3d_layernorm_rows / toc3d_rebase_layernorm_rows / toc3d_gather_merge_ln* take this dtype too: f32
- *           arithmetic, output rows written as planes (they produce the A operands).
+ *           arithmetic, output rows written as planes (they produce the A operands).  For these three row kernels the output buffer is 128-byte aligned and
+ *           its leading dimension a multiple of 32 (refused otherwise); C itself need only be a multiple of 4: a last group of C % 32 elements holds their
+ *           hi parts at bytes [0, 2 (C % 32)) and lo parts at [64, 64 + 2 (C % 32)), and nothing else of the row's [C, ld) columns is written.
+ *           Every count these and the other token kernels take (M, rows, N, nW * N, V * h * w) must fit 32 bits; larger ones are refused.
  * toc3d_window_attention on f32 q|k|v: TOC3D_DTYPE_F32 = exact-f32 products, f32 output; F32X3WO = the same with the output rows as planes; F32X3 = both contractions
  * (q.k, p.v) as bf16 x 3 products -- f32 RoPE, softmax and accumulation; 48 instead of 256 matrix-core cycles per 16x16x32 step -- f32 output; F32X3P = those
  * products and the output as planes (what precision="fp32x3" launches). */

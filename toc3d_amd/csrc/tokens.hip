@@ -23,6 +23,9 @@
 namespace {
 
 constexpr float PAD_SCORE = -1.0e6f;        // toc3d_eva_vit.py:415
+// Row, slot and token counts travel into the kernels as int and are rounded up to whole workgroups there: the entry points refuse anything above this
+// (a larger count would wrap in the kernel's int or in the grid size and index out of range).
+constexpr int64_t TOKEN_ROWS_MAX = 0x7fffffffLL - 1024;
 
 // ---------------------------------------------------------------------------------------------------
 // LayerNorm of one row held by one wavefront.  v[i] = float4 #(lane + 64 i) of the row (nvec valid).
@@ -779,6 +782,7 @@ int toc3d_layernorm_rows(int dtype, const float* x, int64_t ldx, const int32_t* 
     TOC3D_REQUIRE(x && gamma && beta && out, "toc3d_layernorm_rows: null buffer");
     TOC3D_REQUIRE(C > 0 && C % 4 == 0 && C <= 2048, "toc3d_layernorm_rows: C=%lld must be a multiple of 4 and <= 2048", (long long)C);
     TOC3D_REQUIRE(ldx >= C && ldo >= C && ldx % 4 == 0 && ldo % 4 == 0, "toc3d_layernorm_rows: bad leading dims");
+    TOC3D_REQUIRE(M <= TOKEN_ROWS_MAX, "toc3d_layernorm_rows: too many rows (M=%lld: the kernel counts rows in 32 bits)", (long long)M);
     if (M <= 0) return TOC3D_OK;
     dim3 grid((unsigned)((M + 3) / 4)), block(256);
     hipStream_t s = as_stream(stream);
@@ -846,6 +850,8 @@ int toc3d_window_topk(const float* scores, int64_t V, int64_t h, int64_t w, int6
     TOC3D_REQUIRE(V > 0 && h > 0 && w > 0 && L > 0 && L <= 64, "toc3d_window_topk: bad dims");
     const int64_t N = L * L;
     TOC3D_REQUIRE(k >= 0 && k < N, "toc3d_window_topk: k=%lld outside [0, %lld) (keep-all is the dense Block path)", (long long)k, (long long)N);
+    // token rows and windows are int32 in every output: V * h * w (>= the window count) must fit, and may not overflow on the way
+    TOC3D_REQUIRE(h <= TOKEN_ROWS_MAX && w <= TOKEN_ROWS_MAX / h && V <= TOKEN_ROWS_MAX / (h * w), "toc3d_window_topk: too many tokens (V * h * w beyond 32 bits)");
     const int nW = (int)(V * ((h + L - 1) / L) * ((w + L - 1) / L));
     const size_t lds = (size_t)((N + 1) & ~(int64_t)1) * 8 + (size_t)N * 12 + 64;
     static Toc3dLdsAttr topk_attr;
@@ -893,6 +899,7 @@ int toc3d_gather_merge_ln_ex(int dtype, const float* x, int64_t C, const int32_t
     TOC3D_REQUIRE(k >= 0 && k < N && lda >= C && lda % 4 == 0 && rows >= nW, "toc3d_gather_merge_ln: bad k / lda / rows");
     // each of the 16 waves prefetches the index / weight of its share of the dropped tokens in its 64 lanes
     TOC3D_REQUIRE(N - k <= 1024, "toc3d_gather_merge_ln: N - k = %lld dropped tokens per window exceed the kernel's 1024", (long long)(N - k));
+    TOC3D_REQUIRE(N <= TOKEN_ROWS_MAX && rows <= TOKEN_ROWS_MAX, "toc3d_gather_merge_ln: too many rows (N, rows: the kernel counts in 32 bits)");
     if (nW <= 0) return TOC3D_OK;
     return launch_gather(dtype, x, C, tok, wgt, crow_tok, rep_row, nW, N, k, rows, gamma, beta, eps, shortcut, a_out, lda, kept_copy, PendingScatter{}, stream);
 }
@@ -917,6 +924,7 @@ int toc3d_gather_merge_ln_split(int dtype, const float* x, int64_t C, const int3
     TOC3D_REQUIRE(scratch && ((uintptr_t)scratch % 256) == 0 && scratch_bytes >= toc3d_gather_merge_ln_scratch_bytes(nW, C),
                   "toc3d_gather_merge_ln_split: scratch of toc3d_gather_merge_ln_scratch_bytes(nW, C) bytes, 256-byte aligned, zeroed once by the caller");
     TOC3D_REQUIRE(nW * 4 <= TOC3D_GATHER_SPLIT_COUNTER_BYTES, "toc3d_gather_merge_ln_split: at most %d windows per launch", TOC3D_GATHER_SPLIT_COUNTER_BYTES / 4);
+    TOC3D_REQUIRE(N <= TOKEN_ROWS_MAX && rows <= TOKEN_ROWS_MAX, "toc3d_gather_merge_ln_split: too many rows (N, rows: the kernel counts in 32 bits)");
     if (nW <= 0) return TOC3D_OK;
     unsigned* counters = reinterpret_cast<unsigned*>(scratch);
     float* partials = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + TOC3D_GATHER_SPLIT_COUNTER_BYTES);
@@ -954,7 +962,9 @@ int toc3d_scatter_update(float* x, int64_t C, const int32_t* tok, const int32_t*
                          toc3d_stream_t stream) {
     TOC3D_REQUIRE(x && tok && prow && slow_out && rep_raw1 && rep_raw2, "toc3d_scatter_update: null buffer");
     TOC3D_REQUIRE((rep_raw3 == nullptr) == (rep_raw4 == nullptr), "toc3d_scatter_update: rep_raw3 and rep_raw4 come as a pair");
-    TOC3D_REQUIRE(C > 0 && C % 4 == 0 && k >= 0 && k < N, "toc3d_scatter_update: bad dims");
+    TOC3D_REQUIRE(C > 0 && C % 4 == 0 && C <= TOKEN_ROWS_MAX && k >= 0 && k < N, "toc3d_scatter_update: bad dims");
+    // one wavefront per window slot, four to a workgroup: nW * N beyond 32 bits would wrap in the grid size (and in the kernel's int nW, N)
+    TOC3D_REQUIRE(N <= TOKEN_ROWS_MAX && (nW <= 0 || nW <= TOKEN_ROWS_MAX / N), "toc3d_scatter_update: too many slots (nW * N beyond 32 bits)");
     if (nW <= 0 || N <= 0) return TOC3D_OK;
     dim3 grid((unsigned)((nW * N + 3) / 4));
     toc3d_launch(scatter_update_kernel, grid, dim3(256), 0, as_stream(stream), x, (int)C, tok, prow, (int)nW, (int)N, (int)k, slow_out, rep_raw1, rep_raw2, rep_raw3, rep_raw4);
@@ -967,6 +977,7 @@ int toc3d_rebase_layernorm_rows(int dtype, float* slow, int64_t C, const int32_t
                                 void* out, int64_t ldo, int64_t rows, toc3d_stream_t stream) {
     TOC3D_REQUIRE(slow && rep_index && tok && wgt && rep_raw1 && rep_raw2 && gamma && beta && out, "toc3d_rebase_layernorm_rows: null buffer");
     TOC3D_REQUIRE(C > 0 && C % 4 == 0 && C <= 2048 && ldo >= C && ldo % 4 == 0 && k >= 0 && k < N, "toc3d_rebase_layernorm_rows: bad dims");
+    TOC3D_REQUIRE(N <= TOKEN_ROWS_MAX && rows <= TOKEN_ROWS_MAX, "toc3d_rebase_layernorm_rows: too many rows (N, rows: the kernel counts in 32 bits)");
     if (rows <= 0) return TOC3D_OK;
     dim3 grid((unsigned)((rows + 3) / 4)), block(256);
     hipStream_t s = as_stream(stream);
