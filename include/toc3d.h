@@ -80,6 +80,11 @@ extern "C" {
 #define TOC3D_EPI_SWIGLU_STATS_LN 7   /* SWIGLU_STATS with a LayerNorm of the A rows folded into the epilogue   (toc3d_linear_fused) */
 #define TOC3D_EPI_CONV3X3 8           /* out(f32) = conv3x3(NHWC act tensor) + bias as an implicit GEMM          (toc3d_conv3x3_nhwc) */
 #define TOC3D_EPI_QKV_ROPE 9          /* out(act) = [rope(q) * scale | rope(k) | v] of the fused q|k|v projection  (toc3d_linear_qkv_rope) */
+/* out(act) = relu(A.W^T + bias), relu(v) = v > 0 ? v : 0 on the f32 accumulator -- a NaN becomes 0 and -0 becomes +0, the bits of EPI_BIAS followed by
+ * toc3d_relu_inplace without the second launch.  Served exactly where EPI_BIAS is (toc3d_linear, toc3d_linear_ex, toc3d_linear_fused; dtypes BF16, F32, F32X3,
+ * F32X6 and the planes family; every tile variant; `out` plain in the act dtype).  A new VALUE of the existing `epilogue` argument: no entry point is added,
+ * removed or re-signed, so TOC3D_ABI_VERSION stays 11 (as it did for the F32X3P value of the token-side row kernels' `dtype`, further down). */
+#define TOC3D_EPI_BIAS_RELU 10
 
 typedef void* toc3d_stream_t;
 
@@ -490,7 +495,11 @@ int toc3d_memory_post_update(const float* emb_in, const float* ref_in, const dou
  *   order, :385-386 -- then the normalised points of the last depth bin and of bin D-30 (:419-420), also as act rows (ld_cone).
  * toc3d_relu_inplace: nn.ReLU between the Linear pairs.  toc3d_nchw_to_rows: neck output NCHW f32 -> [V*hw, ldo] act rows (:629).
  * toc3d_mln_apply: MLN.forward (models/utils/misc.py:181-188): gamma * LayerNorm(x, no affine, eps 1e-5) + beta -> f32 + act copy.
- * toc3d_se_gate: SELayer_Linear (misc.py:151): out = pos * sigmoid(se). */
+ * toc3d_se_gate: SELayer_Linear (misc.py:151): out = pos * sigmoid(se).
+ * dtype: TOC3D_DTYPE_BF16, TOC3D_DTYPE_F32, or -- toc3d_head_frustum_inputs (pos_in, cone_act), toc3d_nchw_to_rows (out), toc3d_mln_apply (out_act) --
+ *   TOC3D_DTYPE_F32X3P: f32 arithmetic unchanged, the act rows written as (hi, lo) planes in the layout toc3d_head_query_inputs writes (the A operand of a
+ *   bf16 x 3 GEMM on planes).  Such a buffer is 128-byte aligned and its leading dimension a multiple of 32 (refused otherwise); only the valid columns'
+ *   hi and lo parts are written (pre-zero once: zero bytes are zero planes).  The f32 outputs `cone` and `out` stay plain. */
 int toc3d_head_frustum_inputs(int dtype, const float* img2lidar, const float* intrinsics, const float* coords_d, const float* position_range,
                               int64_t B, int64_t N, int64_t h, int64_t w, int64_t D, int64_t stride, int64_t pad_h, int64_t pad_w,
                               void* pos_in, int64_t ld_pos, void* cone_act, int64_t ld_cone, float* cone, toc3d_stream_t stream);

@@ -29,7 +29,7 @@ namespace {
 
 int launch_gemm(int is_bf16, int epi, int variant, const GemmArgs& a, hipStream_t s) {
     switch (epi) {
-        case TOC3D_EPI_BIAS: case TOC3D_EPI_GELU: case TOC3D_EPI_CONV3X3: return toc3d_gemm_launch_plain(is_bf16, epi, variant, a, s);
+        case TOC3D_EPI_BIAS: case TOC3D_EPI_GELU: case TOC3D_EPI_BIAS_RELU: case TOC3D_EPI_CONV3X3: return toc3d_gemm_launch_plain(is_bf16, epi, variant, a, s);
         case TOC3D_EPI_RESIDUAL: case TOC3D_EPI_RESIDUAL_LN: case TOC3D_EPI_RESIDUAL_STATS: return toc3d_gemm_launch_residual(is_bf16, epi, variant, a, s);
         case TOC3D_EPI_SWIGLU: case TOC3D_EPI_SWIGLU_STATS: case TOC3D_EPI_SWIGLU_STATS_LN: return toc3d_gemm_launch_swiglu(is_bf16, epi, variant, a, s);
         case TOC3D_EPI_QKV_ROPE: return toc3d_gemm_launch_rope(is_bf16, epi, variant, a, s);
@@ -261,8 +261,8 @@ static int fused_args(GemmArgs& a, int dtype, int epilogue, const void* A, int64
     if (planes) dtype = TOC3D_F32X3;
     const bool x3_fold = dtype == TOC3D_F32X3 && (epilogue == TOC3D_EPI_SWIGLU_STATS || epilogue == TOC3D_EPI_RESIDUAL_LN || epilogue == TOC3D_EPI_RESIDUAL_STATS ||
                                                   epilogue == TOC3D_EPI_SWIGLU_STATS_LN);
-    TOC3D_REQUIRE((dtype != TOC3D_F32X3 && dtype != TOC3D_F32X6) || epilogue <= TOC3D_EPI_GELU || epilogue == TOC3D_EPI_CONV3X3 || x3_fold,
-                  "toc3d_linear: the bf16 x 3 / x 6 product forms serve epilogues 0-3 and the 3x3 conv (x 3 also the folded LayerNorms, epilogues 4-7)");
+    TOC3D_REQUIRE((dtype != TOC3D_F32X3 && dtype != TOC3D_F32X6) || epilogue <= TOC3D_EPI_GELU || epilogue == TOC3D_EPI_CONV3X3 || epilogue == TOC3D_EPI_BIAS_RELU || x3_fold,
+                  "toc3d_linear: the bf16 x 3 / x 6 product forms serve epilogues 0-3, 10 and the 3x3 conv (x 3 also the folded LayerNorms, epilogues 4-7)");
     TOC3D_REQUIRE(A && W && out, "toc3d_linear: null buffer");
     TOC3D_REQUIRE(M >= 0 && N > 0 && K > 0, "toc3d_linear: bad dims M=%lld N=%lld K=%lld", (long long)M, (long long)N, (long long)K);
     const int bk = 64;
@@ -275,8 +275,8 @@ static int fused_args(GemmArgs& a, int dtype, int epilogue, const void* A, int64
     const bool e_ln_in = epilogue == TOC3D_EPI_RESIDUAL_LN || epilogue == TOC3D_EPI_SWIGLU_STATS_LN;
     const bool e_swiglu = epilogue == TOC3D_EPI_SWIGLU || epilogue == TOC3D_EPI_SWIGLU_STATS || epilogue == TOC3D_EPI_SWIGLU_STATS_LN;
     const bool e_residual = epilogue == TOC3D_EPI_RESIDUAL || epilogue == TOC3D_EPI_RESIDUAL_LN || epilogue == TOC3D_EPI_RESIDUAL_STATS;
-    TOC3D_REQUIRE(epilogue >= 0 && epilogue <= TOC3D_EPI_CONV3X3, "toc3d_linear: epilogue %d is not served by this entry point", epilogue);
-    if (epilogue >= TOC3D_EPI_SWIGLU_STATS && epilogue != TOC3D_EPI_CONV3X3) TOC3D_REQUIRE(dtype == TOC3D_BF16 || x3_fold, "toc3d_linear: the folded-LayerNorm epilogues are bf16 only (and bf16 x 3 on f32 buffers)");
+    TOC3D_REQUIRE((epilogue >= 0 && epilogue <= TOC3D_EPI_CONV3X3) || epilogue == TOC3D_EPI_BIAS_RELU, "toc3d_linear: epilogue %d is not served by this entry point", epilogue);
+    if (epilogue >= TOC3D_EPI_SWIGLU_STATS && epilogue != TOC3D_EPI_CONV3X3 && epilogue != TOC3D_EPI_BIAS_RELU) TOC3D_REQUIRE(dtype == TOC3D_BF16 || x3_fold, "toc3d_linear: the folded-LayerNorm epilogues are bf16 only (and bf16 x 3 on f32 buffers)");
     if (e_stats_out) {
         TOC3D_REQUIRE(stats_out && ((uintptr_t)stats_out % 16) == 0, "toc3d_linear: epilogue %d needs a 16-byte aligned stats_out buffer", epilogue);
         const int64_t slot = e_swiglu ? 128 : 64;
@@ -436,7 +436,7 @@ int toc3d_linear_ex(int dtype, int epilogue, int variant, const void* A, int64_t
                     void* out, int64_t ldo, const float* residual, int64_t ldr, int64_t residual_row_mod,
                     float* rep_out, const int32_t* rep_index, int64_t M, int64_t N, int64_t K, int64_t n_valid,
                     toc3d_stream_t stream) {
-    TOC3D_REQUIRE(epilogue < TOC3D_EPI_SWIGLU_STATS, "toc3d_linear_ex: epilogue %d takes the extra arguments of toc3d_linear_fused", epilogue);
+    TOC3D_REQUIRE(epilogue < TOC3D_EPI_SWIGLU_STATS || epilogue == TOC3D_EPI_BIAS_RELU, "toc3d_linear_ex: epilogue %d takes the extra arguments of toc3d_linear_fused", epilogue);
     return toc3d_linear_fused(dtype, epilogue, variant, A, lda, W, ldw, bias, out, ldo, residual, ldr, residual_row_mod, rep_out, rep_index,
                               M, N, K, n_valid, nullptr, 0, nullptr, 0, nullptr, 0, 0.f, nullptr, 0, nullptr, stream);
 }

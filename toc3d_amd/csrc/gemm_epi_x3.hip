@@ -6,6 +6,7 @@ int toc3d_gemm_launch_x3(int epi, int variant, const GemmArgs& a, hipStream_t s)
     switch (epi) {
         case TOC3D_EPI_BIAS: return launch_epi_x<TOC3D_EPI_BIAS, 3>(variant, a, s);
         case TOC3D_EPI_GELU: return launch_epi_x<TOC3D_EPI_GELU, 3>(variant, a, s);
+        case TOC3D_EPI_BIAS_RELU: return launch_epi_x<TOC3D_EPI_BIAS_RELU, 3>(variant, a, s);      // nn.ReLU behind a Linear (the head's token side)
         case TOC3D_EPI_RESIDUAL: return launch_epi_x<TOC3D_EPI_RESIDUAL, 3>(variant, a, s);
         case TOC3D_EPI_SWIGLU: return launch_epi_x<TOC3D_EPI_SWIGLU, 3>(variant, a, s);
         case TOC3D_EPI_CONV3X3: return launch_epi_x<TOC3D_EPI_CONV3X3, 3>(variant, a, s);

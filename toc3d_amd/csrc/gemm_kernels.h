@@ -61,7 +61,7 @@ struct GemmArgs {
 extern thread_local bool g_bad_variant;                // set by a launch_cfg whose tile variant cannot serve the requested epilogue (gemm.hip)
 
 // one entry per group of epilogues (gemm_epi_*.hip); is_bf16 selects the element type
-int toc3d_gemm_launch_plain(int is_bf16, int epi, int variant, const GemmArgs& a, hipStream_t s);      // EPI_BIAS, EPI_GELU, EPI_CONV3X3
+int toc3d_gemm_launch_plain(int is_bf16, int epi, int variant, const GemmArgs& a, hipStream_t s);      // EPI_BIAS, EPI_GELU, EPI_BIAS_RELU, EPI_CONV3X3
 int toc3d_gemm_launch_residual(int is_bf16, int epi, int variant, const GemmArgs& a, hipStream_t s);   // EPI_RESIDUAL, EPI_RESIDUAL_LN, EPI_RESIDUAL_STATS
 int toc3d_gemm_launch_swiglu(int is_bf16, int epi, int variant, const GemmArgs& a, hipStream_t s);     // EPI_SWIGLU, EPI_SWIGLU_STATS, EPI_SWIGLU_STATS_LN
 int toc3d_gemm_launch_rope(int is_bf16, int epi, int variant, const GemmArgs& a, hipStream_t s);       // EPI_QKV_ROPE (bf16)
@@ -426,7 +426,7 @@ TOC3D_DEV void gemm_epilogue(const GemmArgs& a, f32x4 (&acc)[MT][NT], int row0, 
             if (LN_IN) ccol[j][r] = r < nok[j] ? a.c1[col + r] : 0.f;
         }
     }
-    // act-dtype outputs (bias / GELU / rotated q|k|v): the 4 values of row tile i, column tile j
+    // act-dtype outputs (bias / GELU / ReLU / rotated q|k|v): the 4 values of row tile i, column tile j
     auto act4 = [&](int i, int j, T (&o4)[4]) {
         const int col = col0 + j * 16 + g * 4;
         if constexpr (epi_is_rope(EPI)) {
@@ -455,7 +455,8 @@ TOC3D_DEV void gemm_epilogue(const GemmArgs& a, f32x4 (&acc)[MT][NT], int row0, 
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float raw = acc[i][j][r] + bcol[j][r];
-                o4[r] = to_act<T>(EPI == TOC3D_EPI_GELU ? gelu_erf(raw) : raw);
+                // EPI_BIAS_RELU: v > 0 ? v : 0 on the accumulator (a NaN becomes 0, -0 becomes +0): the bits of relu_kernel (head_tokens.hip) on the EPI_BIAS output
+                o4[r] = to_act<T>(EPI == TOC3D_EPI_GELU ? gelu_erf(raw) : EPI == TOC3D_EPI_BIAS_RELU ? (raw > 0.f ? raw : 0.f) : raw);
             }
         }
     };
@@ -1430,7 +1431,7 @@ template <typename T, int EPI, int BM, int BN, int STAGES, int RB = 128, int WM 
 void launch_cfg(const GemmArgs& a, hipStream_t s) {
     // a wave must own whole (w1, w2) 32-column groups; the folded-LayerNorm statistics need N-tiles of whole 128-column slots; the fold is bf16 only
     constexpr bool unsupported = (epi_is_swiglu(EPI) && (BN / WN) % 32 != 0) || (epi_stats_out(EPI) && BN % (epi_is_swiglu(EPI) ? 128 : 64) != 0) ||
-                                 (EPI >= TOC3D_EPI_SWIGLU_STATS && EPI != TOC3D_EPI_CONV3X3 && sizeof(T) != 2 &&
+                                 (EPI >= TOC3D_EPI_SWIGLU_STATS && EPI != TOC3D_EPI_CONV3X3 && EPI != TOC3D_EPI_BIAS_RELU && sizeof(T) != 2 &&
                                   !(X3 == 3 && (EPI == TOC3D_EPI_SWIGLU_STATS || EPI == TOC3D_EPI_RESIDUAL_LN || EPI == TOC3D_EPI_RESIDUAL_STATS ||
                                                 EPI == TOC3D_EPI_SWIGLU_STATS_LN || EPI == TOC3D_EPI_QKV_ROPE)));   // ... and the bf16 x 3 forms of the ffn_ln and norm2 folds (f32 copies, f32 statistics)
     constexpr bool partial_round = (BM * (RB / 16)) % (64 * WM * WN) != 0 || (BN * (RB / 16)) % (64 * WM * WN) != 0;      // 96- / 160-row tiles

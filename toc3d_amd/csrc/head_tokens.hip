@@ -15,6 +15,16 @@ struct FrustumArgs {
     int B, N, h, w, D, stride, pad_h, pad_w;
 };
 
+// one element of an act row: the act dtype's rounding, or -- f32p_t (common.h) -- the element's (hi, lo) pair in the planes layout of store4_planes
+template <typename T> TOC3D_DEV void put1(T* p, float v) { *p = to_act<T>(v); }
+TOC3D_DEV void put1(f32p_t* p, float v) {
+    const bf16_t h = (bf16_t)v;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+    char* g = reinterpret_cast<char*>(a & ~(uintptr_t)127) + ((a & 127) >> 1);
+    *reinterpret_cast<bf16_t*>(g) = h;
+    *reinterpret_cast<bf16_t*>(g + 64) = (bf16_t)(v - (float)h);
+}
+
 TOC3D_DEV float inv_sigmoid(float x) {                                  // mmdet inverse_sigmoid, eps = 1e-5
     x = fminf(fmaxf(x, 0.f), 1.f);
     return logf(fmaxf(x, 1e-5f) / fmaxf(1.f - x, 1e-5f));
@@ -49,9 +59,9 @@ __global__ __launch_bounds__(256) void frustum_kernel(FrustumArgs a, T* __restri
         p[i] = __fdiv_rn(__fsub_rn(s, a.pr[i]), __fsub_rn(a.pr[3 + i], a.pr[i]));
     }
     T* dst = pin + tokg * ld_pin + d * 3;
-    dst[0] = to_act<T>(inv_sigmoid(p[0]));
-    dst[1] = to_act<T>(inv_sigmoid(p[1]));
-    dst[2] = to_act<T>(inv_sigmoid(p[2]));
+    put1(dst, inv_sigmoid(p[0]));
+    put1(dst + 1, inv_sigmoid(p[1]));
+    put1(dst + 2, inv_sigmoid(p[2]));
     // cone (:419-420): [|fx|, |fy|] / 1e3 of camera (token index % N) -- the reference's repeat order (:385-386) --, then the points
     // of the last depth bin and of bin D - 30
     float* cr = cone + tokg * 8;
@@ -59,7 +69,7 @@ __global__ __launch_bounds__(256) void frustum_kernel(FrustumArgs a, T* __restri
     if (d == a.D - 1 || d == a.D - 30) {
         const int o = d == a.D - 1 ? 2 : 5;
 #pragma unroll
-        for (int i = 0; i < 3; ++i) { cr[o + i] = p[i]; ca[o + i] = to_act<T>(p[i]); }
+        for (int i = 0; i < 3; ++i) { cr[o + i] = p[i]; put1(ca + o + i, p[i]); }
     }
     if (d == 0) {
         const int b = view / a.N;
@@ -67,7 +77,7 @@ __global__ __launch_bounds__(256) void frustum_kernel(FrustumArgs a, T* __restri
         const float* K = a.intrinsics + (int64_t)(b * a.N + tok_in_b % a.N) * 16;
         const float fx = __fdiv_rn(fabsf(K[0]), 1e3f), fy = __fdiv_rn(fabsf(K[5]), 1e3f);
         cr[0] = fx; cr[1] = fy;
-        ca[0] = to_act<T>(fx); ca[1] = to_act<T>(fy);
+        put1(ca, fx); put1(ca + 1, fy);
     }
 }
 
@@ -90,7 +100,7 @@ __global__ __launch_bounds__(256) void nchw_rows_kernel(const float* __restrict_
     __syncthreads();
     for (int r = ty; r < 32; r += 8) {
         const int t = t0 + r, c = c0 + tx;
-        if (t < hw && c < C) out[((int64_t)v * hw + t) * ld + c] = to_act<T>(tile[tx][r]);
+        if (t < hw && c < C) put1(out + ((int64_t)v * hw + t) * ld + c, tile[tx][r]);
     }
 }
 
@@ -116,7 +126,7 @@ __global__ __launch_bounds__(256) void mln_kernel(const float* __restrict__ x, c
         if (c < E) {
             const float o = gamma[(int64_t)row * E + c] * ((v[i] - mean) * rstd) + beta[(int64_t)row * E + c];
             out[(int64_t)row * E + c] = o;
-            out_act[(int64_t)row * ld_act + c] = to_act<T>(o);
+            put1(out_act + (int64_t)row * ld_act + c, o);
         }
     }
 }
@@ -126,6 +136,14 @@ __global__ void se_gate_kernel(const float* __restrict__ pos, const float* __res
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = pos[i] * (1.0f / (1.0f + expf(-se[i])));
 }
+
+// an act output [rows, ld] of an entry point that also takes TOC3D_DTYPE_F32X3P: planes rows are whole 128-byte groups on 128-byte boundaries (the refusal of
+// toc3d_head_query_inputs); the other dtypes keep their checks
+bool planes_rows_ok(int dtype, const void* act, int64_t ld) {
+    return dtype != TOC3D_F32X3P || ((reinterpret_cast<uintptr_t>(act) & 127) == 0 && ld % 32 == 0);
+}
+#define TOC3D_PLANES_ROWS(fn, what, act, ld)                                                                                                           \
+    TOC3D_REQUIRE(planes_rows_ok(dtype, act, ld), fn ": " what ": rows of (hi, lo) planes start on 128-byte boundaries (buffer aligned, leading dimension a multiple of 32)")
 
 }  // namespace
 
@@ -137,6 +155,8 @@ int toc3d_head_frustum_inputs(int dtype, const float* img2lidar, const float* in
     TOC3D_REQUIRE(img2lidar && intrinsics && coords_d && position_range && pos_in && cone_act && cone, "toc3d_head_frustum_inputs: null buffer");
     TOC3D_REQUIRE(B > 0 && N > 0 && h > 0 && w > 0 && D >= 30 && stride > 0 && pad_h > 0 && pad_w > 0 && ld_pos >= 3 * D && ld_cone >= 8,
                   "toc3d_head_frustum_inputs: bad dims (depth_num >= 30, ld_pos >= 3*depth_num, ld_cone >= 8)");
+    TOC3D_PLANES_ROWS("toc3d_head_frustum_inputs", "pos_in", pos_in, ld_pos);
+    TOC3D_PLANES_ROWS("toc3d_head_frustum_inputs", "cone_act", cone_act, ld_cone);
     FrustumArgs a;
     a.img2lidar = img2lidar; a.intrinsics = intrinsics; a.coords_d = coords_d;
     for (int i = 0; i < 6; ++i) a.pr[i] = position_range[i];              // host pointer
@@ -145,6 +165,7 @@ int toc3d_head_frustum_inputs(int dtype, const float* img2lidar, const float* in
     dim3 grid((unsigned)((total + 255) / 256));
     if (dtype == TOC3D_BF16) toc3d_launch(frustum_kernel<bf16_t>, grid, dim3(256), 0, as_stream(stream), a, (bf16_t*)pos_in, ld_pos, (bf16_t*)cone_act, ld_cone, cone);
     else if (dtype == TOC3D_F32) toc3d_launch(frustum_kernel<float>, grid, dim3(256), 0, as_stream(stream), a, (float*)pos_in, ld_pos, (float*)cone_act, ld_cone, cone);
+    else if (dtype == TOC3D_F32X3P) toc3d_launch(frustum_kernel<f32p_t>, grid, dim3(256), 0, as_stream(stream), a, (f32p_t*)pos_in, ld_pos, (f32p_t*)cone_act, ld_cone, cone);
     else { toc3d_set_error("toc3d_head_frustum_inputs: bad dtype"); return TOC3D_ERR_ARG; }
     TOC3D_LAUNCH_CHECK("toc3d_head_frustum_inputs");
     return TOC3D_OK;
@@ -164,9 +185,11 @@ int toc3d_relu_inplace(int dtype, void* x, int64_t n, toc3d_stream_t stream) {
 
 int toc3d_nchw_to_rows(int dtype, const float* x, void* out, int64_t ldo, int64_t V, int64_t C, int64_t hw, toc3d_stream_t stream) {
     TOC3D_REQUIRE(x && out && V > 0 && C > 0 && hw > 0 && ldo >= C && V <= 65535, "toc3d_nchw_to_rows: bad arguments");
+    TOC3D_PLANES_ROWS("toc3d_nchw_to_rows", "out", out, ldo);
     dim3 grid((unsigned)((hw + 31) / 32), (unsigned)((C + 31) / 32), (unsigned)V);
     if (dtype == TOC3D_BF16) toc3d_launch(nchw_rows_kernel<bf16_t>, grid, dim3(256), 0, as_stream(stream), x, (bf16_t*)out, ldo, (int)C, (int)hw);
     else if (dtype == TOC3D_F32) toc3d_launch(nchw_rows_kernel<float>, grid, dim3(256), 0, as_stream(stream), x, (float*)out, ldo, (int)C, (int)hw);
+    else if (dtype == TOC3D_F32X3P) toc3d_launch(nchw_rows_kernel<f32p_t>, grid, dim3(256), 0, as_stream(stream), x, (f32p_t*)out, ldo, (int)C, (int)hw);
     else { toc3d_set_error("toc3d_nchw_to_rows: bad dtype"); return TOC3D_ERR_ARG; }
     TOC3D_LAUNCH_CHECK("toc3d_nchw_to_rows");
     return TOC3D_OK;
@@ -175,10 +198,12 @@ int toc3d_nchw_to_rows(int dtype, const float* x, void* out, int64_t ldo, int64_
 int toc3d_mln_apply(int dtype, const float* x, const float* gamma, const float* beta, int64_t M, int64_t E, float* out, void* out_act, int64_t ld_act,
                     toc3d_stream_t stream) {
     TOC3D_REQUIRE(x && gamma && beta && out && out_act && M >= 0 && E > 0 && E <= 1024 && ld_act >= E, "toc3d_mln_apply: bad arguments (E <= 1024)");
+    TOC3D_PLANES_ROWS("toc3d_mln_apply", "out_act", out_act, ld_act);
     if (M == 0) return TOC3D_OK;
     dim3 grid((unsigned)((M + 3) / 4));
     if (dtype == TOC3D_BF16) toc3d_launch(mln_kernel<bf16_t>, grid, dim3(256), 0, as_stream(stream), x, gamma, beta, (int)E, out, (bf16_t*)out_act, ld_act, (int)M);
     else if (dtype == TOC3D_F32) toc3d_launch(mln_kernel<float>, grid, dim3(256), 0, as_stream(stream), x, gamma, beta, (int)E, out, (float*)out_act, ld_act, (int)M);
+    else if (dtype == TOC3D_F32X3P) toc3d_launch(mln_kernel<f32p_t>, grid, dim3(256), 0, as_stream(stream), x, gamma, beta, (int)E, out, (f32p_t*)out_act, ld_act, (int)M);
     else { toc3d_set_error("toc3d_mln_apply: bad dtype"); return TOC3D_ERR_ARG; }
     TOC3D_LAUNCH_CHECK("toc3d_mln_apply");
     return TOC3D_OK;

@@ -177,6 +177,8 @@ def linear(owner, epi, A, W, bias, out, M, N, K, *, lda=None, ldw=None, ldo=None
     """One GEMM of the fused family, arguments named as in include/toc3d.h (leading dimensions default to the tensors' row lengths).  Grouped where the ABI packs
     them: ``stats_out=(buf, cap)``; ``stats_in=(buf, cap, slots_per_row)``; ``conv=(zero_line, h, w)`` of EPI_CONV3X3; ``rope=(rope_rc, rope_tab, rope_side,
     q_scale)`` of EPI_QKV_ROPE (toc3d_linear_qkv_rope).  ``a_planes`` / ``o_planes``: the A rows arrive / the act-dtype output leaves as (hi, lo) planes (fp32x3).
+    ``EPI_BIAS_RELU`` takes what ``EPI_BIAS`` takes (its ``out`` is plain in the act dtype on every precision: a ReLU output that a planes GEMM multiplies
+    goes in as plain f32, ``a_planes=False``).
 
     The tile / pipeline variant is ``variant`` when the caller decides it, else the fastest one for this (epilogue, M, N, K), measured once on the real operands
     the first time the shape is seen (never while a launch plan is being recorded: shapes are warmed up eagerly).  ``owner`` = the owner of that table and of the

@@ -5,6 +5,8 @@ features right behind the backbone -- ``position_embeding`` (``dense_heads/strea
 Sub-module names equal the head's, so the ``pts_bbox_head.*`` keys of a reference checkpoint load unchanged
 (``position_encoder.{0,2}``, ``memory_embed.{0,2}``, ``spatial_alignment.{reduce.0,gamma,beta}``, ``featurized_pe.{conv_reduce,
 conv_expand}``).  Linear layers run on ``toc3d_linear``; geometry / LayerNorm / gates on ``toc3d_head_*`` kernels.  No CPU path.
+``precision="fp32x3"`` (what an assembled :class:`toc3d_amd.StreamPETRHead` runs by default) goes through :func:`toc3d_amd.gemm.linear` instead: weights and the
+row kernels' outputs as (hi, lo) planes, and the four ``nn.ReLU`` folded into their GEMMs (``EPI_BIAS_RELU``) -- nine GEMM launches and no ReLU launch.
 ``torch.linalg.inv`` of the (B*N) 4x4 ``lidar2img`` matrices is plumbing on the device (the reference hops to the CPU for it, :404).
 """
 from __future__ import annotations
@@ -36,7 +38,7 @@ class HeadTokenEmbedding(DerivedState, nn.Module):
     def __init__(self, in_channels=256, embed_dims=256, depth_num=64, depth_start=1.0, LID=True, stride=16,
                  position_range: Sequence[float] = (-61.2, -61.2, -10.0, 61.2, 61.2, 10.0), precision="fp32", **unused):
         super().__init__()
-        assert precision in ("bf16", "fp32") and embed_dims <= 1024 and depth_num >= 30
+        assert precision in ("bf16", "fp32", "fp32x3") and embed_dims <= 1024 and depth_num >= 30
         self.in_channels, self.embed_dims, self.depth_num, self.stride, self.precision = in_channels, embed_dims, depth_num, stride, precision
         E = embed_dims
         self.position_encoder = nn.Sequential(nn.Linear(depth_num * 3, 4 * E), nn.ReLU(), nn.Linear(4 * E, E))       # :262-266
@@ -50,8 +52,15 @@ class HeadTokenEmbedding(DerivedState, nn.Module):
         else:
             cd = depth_start + (pr[3] - depth_start) / depth_num * index
         self.register_buffer("coords_d", cd, persistent=False)
+        self.__dict__["_coords_d_owner"] = None                                         # bind_coords_d: an owner's Parameter that replaces the buffer
         self._pr = pr                                                       # host copy: the C ABI takes position_range from the host
         self._drop_derived()
+
+    def bind_coords_d(self, param):
+        """Read the depth bins from ``param`` (a [depth_num] f32 Parameter of a module that owns this one, which moves and loads with its owner) instead of
+        the buffer computed from the config: the reference keeps ``coords_d`` in its state dict (streampetr_head.py:231), so a checkpoint's values count."""
+        assert tuple(param.shape) == (self.depth_num,)
+        self.__dict__["_coords_d_owner"] = param            # (a plain attribute: the parameter stays its owner's, this module's state dict does not grow)
 
     # packed weights and the workspaces (keyed by shape only: they are the old device's after a move) are derived state
     _DERIVED = dict(_packed=None, _ws={})
@@ -59,7 +68,7 @@ class HeadTokenEmbedding(DerivedState, nn.Module):
     def _pack(self, dev):
         dts = gemm.dtypes(self.precision)
         pack = lambda lin: (gemm.pack_weight(lin.weight, dts, dev), lin.bias.detach().float().contiguous())
-        P = dict(dt=dts.act, tdt=dts.torch, pe0=pack(self.position_encoder[0]), pe2=pack(self.position_encoder[2]), me0=pack(self.memory_embed[0]),
+        P = dict(dts=dts, dt=dts.act, tdt=dts.torch, pe0=pack(self.position_encoder[0]), pe2=pack(self.position_encoder[2]), me0=pack(self.memory_embed[0]),
                  me2=pack(self.memory_embed[2]), red=pack(self.spatial_alignment.reduce[0]), gam=pack(self.spatial_alignment.gamma),
                  bet=pack(self.spatial_alignment.beta), se1=pack(self.featurized_pe.conv_reduce), se2=pack(self.featurized_pe.conv_expand))
         torch.cuda.current_stream().synchronize()
@@ -76,7 +85,7 @@ class HeadTokenEmbedding(DerivedState, nn.Module):
         if self._packed is None:
             self._packed = self._pack(dev)
         P = self._packed
-        dt, tdt = P["dt"], P["tdt"]
+        dt, tdt, rows = P["dt"], P["tdt"], P["dts"].rows         # rows: the row kernels' output dtype -- the act dtype, or (hi, lo) planes on "fp32x3"
         B, N, C, h, w = img_feats.shape
         assert C == self.in_channels
         E, D = self.embed_dims, self.depth_num
@@ -94,27 +103,36 @@ class HeadTokenEmbedding(DerivedState, nn.Module):
         img2lidar = torch.linalg.inv(lidar2img.to(dev).float().reshape(B * N, 4, 4)).contiguous()
         intr = intrinsics.to(dev).float().reshape(B * N, 4, 4).contiguous()
 
-        def linear(x, wb, out, n, k, f32_out=False, relu=False):
-            wgt, b = wb
-            epi = lib.EPI_RESIDUAL if f32_out else lib.EPI_BIAS
-            lib.call("toc3d_linear", dt, epi, x, x.shape[1], wgt, wgt.shape[1], b, out, out.shape[1], None, 0, 0, None, None, M, n, wgt.shape[1], 0, s)
-            if relu:
-                lib.call("toc3d_relu_inplace", dt, out, out.numel(), s)
+        if self.precision == "fp32x3":
+            # the GEMM family's own launcher: W in planes; A in planes for the four Linears a row kernel feeds -- the four with a ReLU behind them, which the
+            # epilogue applies --, plain f32 (the rows that epilogue left) for the Linear behind each.  Tiles by the query side's rule (64x64 below 256 default tiles).
+            def linear(x, wb, out, n, k, f32_out=False, relu=False):
+                wgt, b = wb
+                epi = lib.EPI_RESIDUAL if f32_out else (lib.EPI_BIAS_RELU if relu else lib.EPI_BIAS)
+                gemm.linear(self, epi, x, wgt, b, out, M, n, wgt.shape[1], a_planes=relu, variant=gemm.small_m_variant(M, n, wgt.shape[1], False))
+        else:
+            def linear(x, wb, out, n, k, f32_out=False, relu=False):
+                wgt, b = wb
+                epi = lib.EPI_RESIDUAL if f32_out else lib.EPI_BIAS
+                lib.call("toc3d_linear", dt, epi, x, x.shape[1], wgt, wgt.shape[1], b, out, out.shape[1], None, 0, 0, None, None, M, n, wgt.shape[1], 0, s)
+                if relu:
+                    lib.call("toc3d_relu_inplace", dt, out, out.numel(), s)
 
         # position_embeding :378-416
-        lib.call("toc3d_head_frustum_inputs", dt, img2lidar, intr, self.coords_d, self._pr, B, N, h, w, D, self.stride, int(pad_shape[0]),
+        coords_d = self.coords_d if self._coords_d_owner is None else self._coords_d_owner.detach().float().contiguous()
+        lib.call("toc3d_head_frustum_inputs", rows, img2lidar, intr, coords_d, self._pr, B, N, h, w, D, self.stride, int(pad_shape[0]),
                  int(pad_shape[1]), W["pin"], W["pin"].shape[1], W["cone_a"], 64, W["cone"], s)
         linear(W["pin"], P["pe0"], W["h1"], 4 * E, 3 * D, relu=True)
         linear(W["h1"], P["pe2"], W["pos"], E, 4 * E, f32_out=True)
         # memory_embed :635
-        lib.call("toc3d_nchw_to_rows", dt, img_feats.float().contiguous(), W["feat"], W["feat"].shape[1], B * N, C, h * w, s)
+        lib.call("toc3d_nchw_to_rows", rows, img_feats.float().contiguous(), W["feat"], W["feat"].shape[1], B * N, C, h * w, s)
         linear(W["feat"], P["me0"], W["m1"], E, C, relu=True)
         linear(W["m1"], P["me2"], W["mem_raw"], E, E, f32_out=True)
         # spatial_alignment :638
         linear(W["cone_a"], P["red"], W["c1"], E, 8, relu=True)
         linear(W["c1"], P["gam"], W["gam"], E, E, f32_out=True)
         linear(W["c1"], P["bet"], W["bet"], E, E, f32_out=True)
-        lib.call("toc3d_mln_apply", dt, W["mem_raw"], W["gam"], W["bet"], M, E, memory, W["mem_a"], W["mem_a"].shape[1], s)
+        lib.call("toc3d_mln_apply", rows, W["mem_raw"], W["gam"], W["bet"], M, E, memory, W["mem_a"], W["mem_a"].shape[1], s)
         # featurized_pe :639
         linear(W["mem_a"], P["se1"], W["s1"], E, E, relu=True)
         linear(W["s1"], P["se2"], W["se"], E, E, f32_out=True)

@@ -1,5 +1,5 @@
 """Registry surface: ``ToC3DEVAViT`` / ``EVA_ViT`` on mmdet's BACKBONES, ``CPFPN`` on NECKS, ``PETRTemporalTransformer`` on TRANSFORMER, ``NMSFreeCoder`` on
-BBOX_CODERS.
+BBOX_CODERS, ``StreamPETRHead`` on HEADS (the reference: ``@HEADS.register_module()``, ``dense_heads/streampetr_head.py:32``).
 
 The reference registers its classes with ``@BACKBONES.register_module()`` (``toc3d_eva_vit.py:25``,
 ``eva_vit.py:270``), ``@NECKS.register_module()`` (``cp_fpn.py:15``) and ``@TRANSFORMER.register_module()``
@@ -46,14 +46,20 @@ try:  # pragma: no cover
     from mmdet.core.bbox.builder import BBOX_CODERS
 except Exception:  # noqa: BLE001
     BBOX_CODERS = _ShimRegistry("bbox_coder")
+try:  # pragma: no cover
+    from mmdet.models.builder import HEADS
+except Exception:  # noqa: BLE001
+    HEADS = _ShimRegistry("head")
 
 
 def register_all():
     from .backbone import EVA_ViT, ToC3DEVAViT
     from .decoder import PETRTemporalTransformer
+    from .head import StreamPETRHead
     from .head_outputs import NMSFreeCoder
     from .neck import CPFPN
-    for reg, cls in ((BACKBONES, ToC3DEVAViT), (BACKBONES, EVA_ViT), (NECKS, CPFPN), (TRANSFORMER, PETRTemporalTransformer), (BBOX_CODERS, NMSFreeCoder)):
+    for reg, cls in ((BACKBONES, ToC3DEVAViT), (BACKBONES, EVA_ViT), (NECKS, CPFPN), (TRANSFORMER, PETRTemporalTransformer), (BBOX_CODERS, NMSFreeCoder),
+                     (HEADS, StreamPETRHead)):
         try:
             reg.register_module(name=cls.__name__, force=True, module=cls)
         except TypeError:
@@ -74,3 +80,7 @@ def build_transformer(cfg, **kw):
 
 def build_bbox_coder(cfg, **kw):
     return BBOX_CODERS.build(cfg, **kw) if isinstance(BBOX_CODERS, _ShimRegistry) else BBOX_CODERS.build(dict(cfg, **kw))
+
+
+def build_head(cfg, **kw):
+    return HEADS.build(cfg, **kw) if isinstance(HEADS, _ShimRegistry) else HEADS.build(dict(cfg, **kw))

@@ -533,3 +533,67 @@ def head_queries_bank(sizes: dict, B: int, frame: int, seed: int = 0):
     pose[..., 0, 0], pose[..., 0, 1], pose[..., 1, 0], pose[..., 1, 1] = torch.cos(ang), -torch.sin(ang), torch.sin(ang), torch.cos(ang)
     pose[..., :3, 3] = r(B, n, 3) * torch.tensor([4.0, 1.0, 0.1])
     return dict(memory_embedding=r(B, n, E), memory_reference_point=ref, memory_timestamp=ts, memory_egopose=pose, memory_velo=r(B, n, 2) * 3.0)
+
+
+# ---- the assembled head (toc3d_amd.StreamPETRHead) ---------------------------------------------------------------------------------------------------------
+# the sizes of the end-to-end fixtures (tools/gen_golden_head_e2e.py): the query side and the decoder fix embed_dims = 256 and head_dim = 32
+HEAD_FULL = dict(in_channels=256, num_query=644, memory_len=1024, topk_proposals=256, num_propagated=256, decoder=DECODER_FULL, max_num=300, post_center_range=None)
+HEAD_TINY = dict(in_channels=32, num_query=21, memory_len=27, topk_proposals=9, num_propagated=7,
+                 decoder=dict(embed_dims=256, num_heads=8, feedforward_channels=128, num_layers=2), max_num=20, post_center_range=[-40.0, -40.0, -4.0, 40.0, 40.0, 2.5])
+HEAD_FULL_SHAPE = dict(B=1, N=6, h=20, w=50, frames=2)
+HEAD_TINY_SHAPE = dict(B=2, N=2, h=3, w=4, frames=4)
+
+
+def head_cfg(sizes: dict = None) -> dict:
+    """The ``pts_bbox_head=dict(...)`` block of the shipped configs (projects/configs/ToC3D/ToC3D_faster.py:96-154) at the given sizes (default: as shipped,
+    every key of the block, the training-only ones included)."""
+    sizes = HEAD_FULL if sizes is None else sizes
+    return dict(type="StreamPETRHead", num_classes=10, in_channels=sizes["in_channels"], num_query=sizes["num_query"], memory_len=sizes["memory_len"],
+                topk_proposals=sizes["topk_proposals"], num_propagated=sizes["num_propagated"], with_ego_pos=True, match_with_velo=False, scalar=10, noise_scale=1.0,
+                dn_weight=1.0, split=0.75, LID=True, with_position=True, position_range=[-61.2, -61.2, -10.0, 61.2, 61.2, 10.0],
+                code_weights=[2.0, 2.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0], transformer=decoder_cfg(**sizes["decoder"]),
+                bbox_coder=bbox_coder_cfg(max_num=sizes["max_num"], post_center_range=sizes["post_center_range"]),
+                loss_cls=dict(type="FocalLoss", use_sigmoid=True, gamma=2.0, alpha=0.25, loss_weight=2.0), loss_bbox=dict(type="L1Loss", loss_weight=0.25),
+                loss_iou=dict(type="GIoULoss", loss_weight=0.0))
+
+
+def head_state_dict(sizes: dict = None, seed: int = 0):
+    """Seeded weights of the whole ``pts_bbox_head.*`` slice under the reference's names, composed from the per-module helpers (same seeds, same tensors), plus
+    ``pseudo_reference_points`` and the five frozen parameters by the reference's expressions (streampetr_head.py:207-231)."""
+    sizes = HEAD_FULL if sizes is None else sizes
+    cfg = head_cfg(sizes)
+    E, D = 256, 64
+    sd = OrderedDict()
+    sd.update(head_tokens_state_dict(dict(in_channels=sizes["in_channels"], embed_dims=E, depth_num=D), seed=seed))
+    sd.update(head_queries_state_dict(dict(sizes, embed_dims=E), seed=seed))
+    sd.update({"transformer." + k: v for k, v in decoder_state_dict(sizes["decoder"], seed=seed).items()})
+    sd.update(head_outputs_state_dict(dict(HEAD_OUTPUTS_FULL, embed_dims=E), seed=seed))
+    sd["pseudo_reference_points.weight"] = torch.rand(sizes["num_propagated"], 3, generator=torch.Generator().manual_seed(13000 + seed))
+    pr = torch.tensor(cfg["position_range"])
+    index = torch.arange(start=0, end=D, step=1).float()
+    sd["code_weights"] = torch.tensor(cfg["code_weights"])
+    sd["match_costs"] = torch.tensor(cfg["code_weights"])
+    sd["pc_range"], sd["position_range"] = torch.tensor(PC_RANGE), pr
+    sd["coords_d"] = 1 + (pr[3] - 1) / (D * (1 + D)) * index * (index + 1)
+    return sd
+
+
+def head_inputs(sizes: dict = None, shape: dict = None, seed: int = 0):
+    """Per frame the ``data`` dict of ``StreamPETRHead.forward`` -- neck features, camera matrices (``head_tokens_inputs``, a seed per frame), ``prev_exists``,
+    f64 timestamps and ego poses (``memory_inputs``) -- and ``img_metas``.  Frame 0 starts every scene; with more than one sample, frame 2 starts a new scene
+    for sample 1 alone."""
+    sizes, shape = (HEAD_FULL if sizes is None else sizes), (HEAD_FULL_SHAPE if shape is None else shape)
+    B, N, h, w, F = shape["B"], shape["N"], shape["h"], shape["w"], shape["frames"]
+    mem = memory_inputs(dict(num_propagated=sizes["num_propagated"], embed_dims=8), B, sizes["num_query"], 10, F, seed=seed)
+    tok_cfg = dict(in_channels=sizes["in_channels"], stride=16)
+    frames = []
+    for f in range(F):
+        data = dict(mem["frames"][f]["data"])
+        prev = torch.ones(B) if f > 0 else torch.zeros(B)
+        if f == 2 and B > 1:
+            prev[1] = 0.0
+        data["prev_exists"] = prev
+        tok = head_tokens_inputs(tok_cfg, B, N, h, w, seed=100 * seed + f)
+        data.update(img_feats=tok["feats"], intrinsics=tok["intrinsics"], lidar2img=tok["lidar2img"])
+        frames.append(data)
+    return dict(frames=frames, img_metas=[dict(pad_shape=[(h * 16, w * 16, 3)]) for _ in range(B)])
