@@ -1,0 +1,334 @@
+"""CPU: every refusal of the entry points of csrc/scorer.hip (toc3d_pack_motion_weights, toc3d_motion_queries, toc3d_collapse_query_scorer, toc3d_score_tokens,
+toc3d_score_head, toc3d_global_mean_half, toc3d_gumbel_noise, toc3d_gumbel_from_bits, toc3d_abs_pos_bicubic, toc3d_im2col_3x3) is reached once and names its
+reason in toc3d_last_error().  The checks run before any launch, so the pointers are made-up aligned addresses that are never dereferenced; only refusing calls
+and the empty ones that return before the launch are made.  Misaligned and oversized arguments are tested ONLY here.
+
+Second half: the references tests/test_gpu_scorer_kernels.py holds the kernels to (tests/scorer_cases.py) are checked for their own invariants."""
+import os
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import scorer_cases as SC
+from oracle import toc3d_oracle as O
+from toc3d_amd import configs, lib, synth
+
+A = 0x10000                                  # 256-byte aligned stand-in for a device buffer
+ERR_ARG = -1
+I31 = (1 << 31) - 1                          # the largest count the kernels' 32-bit indices hold
+
+
+def _call(name, *args):
+    l = lib.load()
+    rc = getattr(l, name)(*args)
+    return rc, l.toc3d_last_error().decode()
+
+
+def _refused(name, args, reason):
+    rc, msg = _call(name, *args)
+    assert rc == ERR_ARG and name in msg and reason in msg, (rc, msg)
+
+
+# ---- toc3d_pack_motion_weights / toc3d_motion_queries ------------------------------------------------------
+@pytest.mark.parametrize("null_at", [0, 11, 22, 23])
+def test_pack_motion_weights_refuses_null(null_at):
+    ptrs = [A] * 24
+    ptrs[null_at] = None
+    _refused("toc3d_pack_motion_weights", (*ptrs, None), "null buffer")
+
+
+MOTION_PTRS = ("w", "queries", "ref", "vel", "ts", "pose", "pose_inv", "out")
+
+
+def _motion(**o):
+    a = dict({p: A for p in MOTION_PTRS}, n_stages=1, w_stride=0, f64=1, B=1, Q=64)
+    a.update(o)
+    return (a["w"], a["n_stages"], a["w_stride"], a["queries"], a["ref"], a["vel"], a["ts"], a["f64"], a["pose"], a["pose_inv"], a["B"], a["Q"], a["out"], None)
+
+
+@pytest.mark.parametrize("over,reason", [
+    *[({p: None}, "null buffer") for p in MOTION_PTRS],
+    (dict(n_stages=0), "bad n_stages / w_stride"), (dict(n_stages=3, w_stride=0), "bad n_stages / w_stride"),
+    (dict(n_stages=2, w_stride=-1), "bad n_stages / w_stride"),
+    (dict(B=1 << 31), "too many queries"), (dict(Q=1 << 31), "too many queries"), (dict(B=1 << 16, Q=1 << 15), "too many queries"), (dict(B=1 << 40, Q=1 << 40), "too many queries"),
+    (dict(n_stages=9, w_stride=1 << 20, B=1, Q=I31), "too many workgroups"), (dict(n_stages=1 << 62, w_stride=1 << 20), "too many workgroups"),
+])
+def test_motion_queries_refusals(over, reason):
+    _refused("toc3d_motion_queries", _motion(**over), reason)
+
+
+def test_motion_stride_bound_is_the_packed_size():
+    n = int(lib.load().toc3d_motion_weights_floats())
+    _refused("toc3d_motion_queries", _motion(n_stages=2, w_stride=n - 1), "bad n_stages / w_stride")
+    assert n == 384 * 256 + 2 * 180 * 256 + 6 * 256 * 256 + 11 * 256 + 8 + 128 + 256
+
+
+# ---- toc3d_collapse_query_scorer ------------------------------------------------------------------------------
+COLLAPSE_PTRS = ("mq", "w_in", "b_in", "w_agg", "b_agg", "wc", "bc")
+
+
+def _collapse(**o):
+    a = dict({p: A for p in COLLAPSE_PTRS}, B=1, Q=64, C=128)
+    a.update(o)
+    return (a["mq"], a["w_in"], a["b_in"], a["w_agg"], a["b_agg"], a["B"], a["Q"], a["C"], 0.0625, a["wc"], a["bc"], None)
+
+
+@pytest.mark.parametrize("over,reason", [
+    *[({p: None}, "null buffer") for p in COLLAPSE_PTRS],
+    (dict(Q=0), "must be positive"), (dict(C=0), "must be positive"), (dict(Q=-1), "must be positive"), (dict(C=-256, B=0), "must be positive"),
+    (dict(Q=1 << 31), "too large"), (dict(C=1 << 31), "too large"), (dict(C=(1 << 32) + 128), "too large"),
+    (dict(B=65536), "too many samples"),
+])
+def test_collapse_query_scorer_refusals(over, reason):
+    _refused("toc3d_collapse_query_scorer", _collapse(**over), reason)
+
+
+# ---- toc3d_score_tokens ---------------------------------------------------------------------------------------
+TOKENS_PTRS = ("x", "wc", "bc", "pred", "score", "mask_out")
+
+
+def _tokens(**o):
+    a = dict({p: A for p in TOKENS_PTRS}, mask=A, gumbel=A, C=128, V=2, T=1000, vpf=2)
+    a.update(o)
+    return (a["x"], a["C"], a["mask"], a["wc"], a["bc"], a["gumbel"], a["V"], a["T"], a["vpf"], a["pred"], a["score"], a["mask_out"], None)
+
+
+@pytest.mark.parametrize("over,reason", [
+    *[({p: None}, "null buffer") for p in TOKENS_PTRS],
+    (dict(C=126), "bad dims"), (dict(vpf=0), "bad dims"), (dict(vpf=-2), "bad dims"), (dict(V=3), "bad dims"),
+    (dict(C=0), "counted in 32 bits"), (dict(C=1 << 31), "counted in 32 bits"), (dict(vpf=1 << 31, V=1 << 32), "counted in 32 bits"),
+    (dict(x=A + 4), "16-byte aligned"), (dict(x=A + 8), "16-byte aligned"), (dict(wc=A + 8), "16-byte aligned"), (dict(wc=A + 12), "16-byte aligned"),
+    (dict(T=1 << 31), "too many tokens"), (dict(V=1 << 31, vpf=1), "too many tokens"), (dict(V=1 << 18, T=1 << 16), "too many tokens"), (dict(V=1 << 30, vpf=1, T=I31), "too many tokens"),
+])
+def test_score_tokens_refusals(over, reason):
+    _refused("toc3d_score_tokens", _tokens(**over), reason)
+
+
+# ---- toc3d_score_head -------------------------------------------------------------------------------------------
+HEAD_PTRS = ("f", "w", "b", "pred", "score", "mask_out")
+
+
+def _head(dtype=lib.F32, **o):
+    a = dict({p: A for p in HEAD_PTRS}, gumbel=None, ld=64, kdim=32, M=2000)
+    a.update(o)
+    return (dtype, a["f"], a["ld"], a["kdim"], a["w"], a["b"], a["gumbel"], a["M"], a["pred"], a["score"], a["mask_out"], None)
+
+
+@pytest.mark.parametrize("dtype,over,reason", [
+    *[(lib.F32, {p: None}, "null buffer") for p in HEAD_PTRS],
+    (lib.F32, dict(kdim=36), "multiples of 8"), (lib.BF16, dict(ld=68), "multiples of 8"), (lib.F32, dict(ld=24), "multiples of 8"),
+    (lib.F32, dict(kdim=-8), "bad kdim"), (lib.BF16, dict(kdim=1 << 31, ld=1 << 31), "bad kdim"),
+    (lib.F32, dict(f=A + 8), "16-byte aligned"), (lib.BF16, dict(f=A + 8), "16-byte aligned"), (lib.BF16, dict(f=A + 2), "16-byte aligned"),
+    (lib.F32, dict(M=4 * I31 + 1), "too many rows"), (lib.BF16, dict(M=1 << 40), "too many rows"),
+    (99, {}, "bad dtype"), (lib.F32X3, {}, "bad dtype"),
+])
+def test_score_head_refusals(dtype, over, reason):
+    _refused("toc3d_score_head", _head(dtype, **over), reason)
+
+
+# ---- toc3d_global_mean_half -------------------------------------------------------------------------------------
+def _mean(dtype=lib.F32, **o):
+    a = dict(t=A, ld=128, V=2, T=1000, C=128)
+    a.update(o)
+    return (dtype, a["t"], a["ld"], a["V"], a["T"], a["C"], None)
+
+
+@pytest.mark.parametrize("dtype,over,reason", [
+    (lib.F32, dict(t=None), "bad arguments"), (lib.F32, dict(C=127), "bad arguments"), (lib.BF16, dict(ld=126), "bad arguments"),
+    (lib.F32, dict(C=0), "bad C"), (lib.F32, dict(C=-2), "bad C"), (lib.BF16, dict(C=1 << 31, ld=1 << 31), "bad C"),
+    (lib.F32, dict(T=1 << 31), "too many tokens per view"), (lib.BF16, dict(V=65536), "too many views"),
+    (99, {}, "bad dtype"), (lib.F32X3P, {}, "bad dtype"),
+])
+def test_global_mean_half_refusals(dtype, over, reason):
+    _refused("toc3d_global_mean_half", _mean(dtype, **over), reason)
+
+
+# ---- toc3d_gumbel_noise / toc3d_gumbel_from_bits ------------------------------------------------------------------
+@pytest.mark.parametrize("args,reason", [
+    ((None, 8, 1, A), "bad arguments"), ((A, 8, 1, None), "bad arguments"), ((A, -1, 1, A), "bad arguments"),
+    ((A + 4, 8, 1, A), "16-byte, state 8-byte aligned"), ((A + 8, 8, 1, A), "16-byte, state 8-byte aligned"), ((A, 8, 1, A + 4), "16-byte, state 8-byte aligned"),
+    ((A, 1024 * I31 + 1, 1, A), "n too large"),
+])
+def test_gumbel_noise_refusals(args, reason):
+    _refused("toc3d_gumbel_noise", (*args, None), reason)
+
+
+@pytest.mark.parametrize("args", [(None, 8, A), (A, 8, None), (A, -1, A)])
+def test_gumbel_from_bits_refusals(args):
+    _refused("toc3d_gumbel_from_bits", (*args, None), "bad arguments")
+
+
+# ---- toc3d_abs_pos_bicubic / toc3d_im2col_3x3 ---------------------------------------------------------------------
+def _bicubic(**o):
+    a = dict(pos=A, S=14, C=128, out=A, h=20, w=50)
+    a.update(o)
+    return (a["pos"], a["S"], a["C"], a["out"], a["h"], a["w"], None)
+
+
+@pytest.mark.parametrize("over,reason", [
+    (dict(pos=None), "bad arguments"), (dict(out=None), "bad arguments"), (dict(S=0), "bad arguments"), (dict(C=0), "bad arguments"), (dict(h=0), "bad arguments"),
+    (dict(w=-1), "bad arguments"),
+    (dict(S=1 << 31), "grid too large"), (dict(C=1 << 31), "grid too large"), (dict(h=1 << 31), "grid too large"), (dict(h=1 << 16, w=1 << 15), "grid too large"),
+    (dict(h=1 << 40, w=1 << 40), "grid too large"),
+])
+def test_abs_pos_bicubic_refusals(over, reason):
+    _refused("toc3d_abs_pos_bicubic", _bicubic(**over), reason)
+
+
+@pytest.mark.parametrize("dtype,args,reason", [
+    (lib.F32, (None, A, 288, 2, 20, 50, 32), "bad arguments"), (lib.F32, (A, None, 288, 2, 20, 50, 32), "bad arguments"), (lib.BF16, (A, A, 287, 2, 20, 50, 32), "bad arguments"),
+    (99, (A, A, 288, 2, 20, 50, 32), "bad dtype"), (lib.F32X3, (A, A, 288, 2, 20, 50, 32), "bad dtype"),
+])
+def test_im2col_3x3_refusals(dtype, args, reason):
+    _refused("toc3d_im2col_3x3", (dtype, *args, None), reason)
+
+
+def test_empty_calls_return_before_the_launch():
+    ok = lambda name, args: _call(name, *args)[0] == 0
+    assert ok("toc3d_motion_queries", _motion(B=0)) and ok("toc3d_motion_queries", _motion(Q=0)) and ok("toc3d_motion_queries", _motion(B=-1, Q=1 << 40))
+    assert ok("toc3d_collapse_query_scorer", _collapse(B=0)) and ok("toc3d_collapse_query_scorer", _collapse(B=-5))
+    assert ok("toc3d_score_tokens", _tokens(V=0)) and ok("toc3d_score_tokens", _tokens(T=0)) and ok("toc3d_score_tokens", _tokens(V=-2, T=-3, mask=None, gumbel=None))
+    assert ok("toc3d_score_head", _head(M=0)) and ok("toc3d_score_head", _head(lib.BF16, M=-1))
+    assert ok("toc3d_global_mean_half", _mean(V=0)) and ok("toc3d_global_mean_half", _mean(lib.BF16, T=0))
+    assert ok("toc3d_gumbel_noise", (A, 0, 1, A, None)) and ok("toc3d_gumbel_from_bits", (A, 0, A, None))
+    assert ok("toc3d_im2col_3x3", (lib.F32, A, A, 288, 0, 20, 50, 32, None))
+
+
+# ---- the references of tests/test_gpu_scorer_kernels.py -------------------------------------------------------------
+def test_philox_known_answer_vectors():
+    """The three published Philox4x32-10 vectors (Random123's kat_vectors: zeros, all ones, the digits of pi)."""
+    for ctr, key, want in SC.PHILOX_KAT:
+        got = SC.philox4x32_10(np.array(ctr, dtype=np.uint32), key)
+        assert tuple(int(v) for v in got) == want, [hex(int(v)) for v in got]
+    batch = SC.philox4x32_10(np.array([c for c, _, _ in SC.PHILOX_KAT[:1]] * 3, dtype=np.uint32), (0, 0))
+    assert batch.shape == (3, 4) and (batch == np.array(SC.PHILOX_KAT[0][2], dtype=np.uint32)).all()
+
+
+def test_gumbel_words_counter_layout():
+    """Element 4 q + e is word e of the block with counter (q, 0, frame lo, frame hi) and key (seed lo, seed hi); a shorter draw is a prefix of a longer one;
+    both halves of the seed and of the frame counter matter."""
+    seed, frame = SC.GUMBEL_SEEDS[1], SC.GUMBEL_FRAMES[2]
+    w = SC.gumbel_words(4099, seed, frame)
+    assert w.dtype == np.uint32 and w.shape == (4099,)
+    for q in (0, 1, 1024):
+        blk = SC.philox4x32_10(np.array([q, 0, frame & 0xFFFFFFFF, frame >> 32], dtype=np.uint32), (seed & 0xFFFFFFFF, seed >> 32))
+        assert (w[4 * q:4 * q + 4] == blk[:len(w[4 * q:4 * q + 4])]).all()
+    for n in SC.GUMBEL_N:
+        assert (SC.gumbel_words(n, seed, frame) == w[:n]).all()
+    for other in ((seed & 0xFFFFFFFF, frame), (seed, frame & 0xFFFFFFFF), (seed ^ 1, frame), (seed, frame + 1)):
+        assert not (SC.gumbel_words(8, *other) == w[:8]).any()
+    assert all(s >> 32 for s in SC.GUMBEL_SEEDS[1:]) and SC.GUMBEL_FRAMES[2] >> 32
+    assert {n % 4 for n in SC.GUMBEL_N} == {0, 1, 2, 3} and max(SC.GUMBEL_N) > 4 * 1024
+
+
+def test_motion_reference_stands_next_to_the_real_reference(golden_dir):
+    """ref64 on the toc3d_tiny synthetic inputs against the REAL reference's f32 output (the fixture): the same operation, to f32 evaluation error."""
+    g = np.load(os.path.join(golden_dir, "scorer_toc3d_tiny.npz"))
+    cfg = configs.get("toc3d_tiny")
+    sd = synth.make_state_dict(cfg)
+    for epoch, fl in ((False, "u01"), (True, "epoch")):
+        inp = synth.make_inputs(cfg, views_per_frame=2, epoch_timestamps=epoch)
+        i = dict(queries=inp["temp_queries"], ref_points=inp["temp_ref_points"], vel=inp["temp_vel"], timestamp=inp["temp_timestamp"],
+                 ego_pose=inp["temp_ego_pose"], ego_pose_inv=inp["ego_pose_inv"])
+        with torch.no_grad():
+            ref = SC.motion_ref64(sd, i, pre="score_predictor.1.")
+        err = float((torch.from_numpy(g[f"{fl}.mq"]).double() - ref).abs().max())
+        assert err <= SC.MOTION_CONDITION * float(ref.abs().max()), (fl, err)
+
+
+@pytest.mark.parametrize("ts_kind", SC.MOTION_TS)
+def test_motion_cases_meet_their_condition(ts_kind):
+    """E_cpu <= 2e-6 max|ref64| at every case and stage before anything goes to the GPU; stages and samples really differ; f32 timestamps are small."""
+    for (B, Q) in SC.MOTION_BQ:
+        refs = []
+        for s in range(3):
+            inp, ref, e_cpu = SC.motion_case(B, Q, ts_kind, s)
+            assert ref.dtype == torch.float64 and ref.shape == (B, Q, 256) and bool(torch.isfinite(ref).all())
+            assert 0 < e_cpu <= SC.MOTION_CONDITION * float(ref.abs().max()), (B, Q, s, e_cpu)
+            refs.append(ref)
+        assert float((refs[0] - refs[1]).abs().max()) > 0.1 and float((refs[1] - refs[2]).abs().max()) > 0.1
+        ts = inp["timestamp"]
+        assert ts.dtype == (torch.float32 if ts_kind == "f32_small" else torch.float64)
+        assert float(ts.abs().max()) <= 10 or ts_kind == "f64_epoch"
+        if B > 1:
+            # a kernel that read sample 0's ego_pose_inv for every query would be off by far more than the bound
+            wrong = dict(inp, ego_pose_inv=inp["ego_pose_inv"][:1].expand(B, -1, -1).contiguous())
+            with torch.no_grad():
+                off = float((SC.motion_ref64(SC.motion_state_dict(2), wrong) - refs[2])[1:].abs().max())
+            assert off > 1e3 * SC.MOTION_FACTOR * e_cpu, (B, Q, off)
+    assert any(B * Q % 8 for B, Q in SC.MOTION_BQ) and any(Q % 8 and B > 1 and Q < 8 for B, Q in SC.MOTION_BQ)
+
+
+def test_collapse_reference_is_the_oracles_scorer():
+    """log_softmax((x * mask) . wc + bc) from collapse_ref64 == oracle.query_based_score in f64 (B = 2 samples x 2 views each, Q = 17, C = 12)."""
+    B, Q, C, V, T = 2, 17, 12, 4, 6
+    i = SC.collapse_inputs(B, Q, C)
+    wc, bc, wc_tol, bc_tol = SC.collapse_ref64(i)
+    assert bool((wc_tol > 0).all()) and bool((bc_tol > 0).all()) and float((wc_tol / wc.abs().clamp_min(1e-3)).max()) < 1e-2
+    pre = "p."
+    sd = {pre + "input_proj.0.weight": i["w_in"].double(), pre + "input_proj.0.bias": i["b_in"].double(),
+          pre + "aggregate.0.weight": i["w_agg"].double(), pre + "aggregate.0.bias": i["b_agg"].double()}
+    g = torch.Generator().manual_seed(1)
+    x, m = torch.randn(V, T, 1, C, generator=g, dtype=torch.float64), torch.rand(V, T, 1, 1, generator=g, dtype=torch.float64)
+    want = O.query_based_score(x, m, i["mq"].double(), sd, pre)
+    b = torch.arange(V) // (V // B)
+    got = torch.log_softmax(torch.einsum("vtc,vcj->vtj", (x * m).flatten(1, 2), wc[b]) + bc[b][:, None], -1)
+    assert float((got - want).abs().max()) < 1e-12
+    assert {c[0] for c in SC.COLLAPSE_CASES} == {1, 3} and {c[1] for c in SC.COLLAPSE_CASES} == {1, 15, 16, 17, 64, 100}
+    assert {c[2] for c in SC.COLLAPSE_CASES} == {1, 255, 256, 257, 1024}
+
+
+def test_token_score_references():
+    """Logits, log-softmax and the soft mask against plain torch in f64; every sample's weights are its own; the scaled rows and the noise extremes are there; the
+    measured libm figures stay below their sanity ceiling (asserted inside tail_ref64)."""
+    for (V, T, vpf) in SC.TOKENS_VT:
+        i = SC.tokens_inputs(132, V, T, vpf, True)
+        logits, delta = SC.tokens_logits64(i)
+        M, B = V * T, V // vpf
+        assert i["wc"].shape == (B, 132, 2) and i["b"].tolist() == [(r // T) // vpf for r in range(M)] and (B == 1 or int(i["b"].max()) == B - 1)
+        want = torch.stack([F.linear(i["x"][r].double() * i["mask"][r].double(), i["wc"][i["b"][r]].double().T, i["bc"][i["b"][r]].double()) for r in range(min(M, 40))])
+        assert float((logits[:40] - want).abs().max()) < 1e-12
+        gum = SC.gumbel_rows(M, 5)
+        r = SC.tail_ref64(logits, delta, gum)
+        assert float((r["pred"].exp().sum(1) - 1).abs().max()) < 1e-12 and bool(((r["mask"] >= 0) & (r["mask"] <= 1)).all())
+        assert float((r["mask"] - torch.softmax(r["pred"] + gum.double(), -1)[:, 0]).abs().max()) == 0
+        assert bool((r["pred_tol"] > 0).all()) and bool((r["mask_tol"] > 0).all()) and 1 <= r["k_pred"] <= SC.LIBM_SANITY and 1 <= r["k_mask"] <= SC.LIBM_SANITY
+        r0 = SC.tail_ref64(logits, delta, None)
+        assert float((r0["mask"] - torch.softmax(logits, -1)[:, 0]).abs().max()) < 1e-15
+        if B > 1:
+            swapped = dict(i, b=torch.zeros_like(i["b"]))
+            assert float((SC.tokens_logits64(swapped)[0] - logits)[i["b"] > 0].abs().median()) > 1e3 * float(delta.max())
+    dl = (logits[:, 0] - logits[:, 1]).abs()
+    assert int(((dl > 15) & (dl < 25)).sum()) > 100 and int(((dl > 90) & (dl < 110)).sum()) > 50 and float(dl.median()) < 5
+    sat = r0["mask"][dl > 90]
+    assert bool(((sat < 1e-30) | (sat > 1 - 1e-15)).all()), "at |l0 - l1| ~ 100 the mask is 0 or 1"
+    assert torch.equal(gum[0], torch.tensor([SC.G_MIN, SC.G_MAX])) and torch.equal(gum[1], torch.tensor([SC.G_MAX, SC.G_MIN]))
+    assert abs(SC.G_MIN + 2.8113) < 1e-3 and abs(SC.G_MAX - 16.6355) < 1e-3
+
+
+def test_head_score_reference_reads_the_rounded_values():
+    for bf16 in (False, True):
+        i = SC.head_inputs(520, 528, 9, bf16)
+        assert i["f"].dtype == (torch.bfloat16 if bf16 else torch.float32) and bool(i["f"][:, 520:].isnan().all()) and bool(torch.isfinite(i["f"][:, :520].float()).all())
+        logits, delta = SC.head_logits64(i)
+        want = F.linear(i["f"][:, :520].double(), i["w"].double(), i["b"].double())
+        assert float((logits - want).abs().max()) < 1e-12 and bool((delta > 0).all()) and float(delta.max()) < 1e-3
+
+
+def test_mean_and_bicubic_references():
+    for bf16 in (False, True):
+        t = SC.mean_inputs(3, 5, 130, 138, bf16)
+        mean, tol = SC.mean_ref64(t, 3, 5, 130, bf16)
+        assert mean.shape == (3, 65) and float((mean[1] - t[5:10, 65:130].double().mean(0)).abs().max()) < 1e-15 and bool((tol > 0).all())
+    for (S, h, w) in SC.BICUBIC_CASES:
+        pos = torch.randn(S * S, 3, generator=torch.Generator().manual_seed(S + h + w))
+        ref, tol, own = SC.bicubic_ref64(pos, S, h, w)
+        assert ref.shape == (h * w, 3) and float((ref - own).abs().max()) < 1e-12, (S, h, w)
+        want = O.abs_pos(pos.double()[None], False, (h, w)).reshape(h * w, 3)
+        assert float((ref - want).abs().max()) == 0
+        assert (S == h == w) or (bool((tol > 0).all()) and float(tol.max()) < 1e-3)
+    t = torch.linspace(0, 1, 1001, dtype=torch.float64)
+    c = SC._cubic(t)
+    assert float((c.sum(1) - 1).abs().max()) < 1e-14 and float(((c[1:] - c[:-1]).abs() / 1e-3).max()) <= 1.5, "the coefficients' slope stays below 1.5"

@@ -485,6 +485,11 @@ __global__ __launch_bounds__(256) void gumbel_noise_kernel(float* __restrict__ o
     }
 }
 
+constexpr int64_t kMaxCount = 0x7fffffff;     // the kernels index rows, columns and workgroups in 32 bits
+constexpr int64_t kMaxGridY = 65535;
+
+inline bool aligned16(const void* p) { return ((uintptr_t)p % 16) == 0; }
+
 }  // namespace
 
 extern "C" {
@@ -524,7 +529,9 @@ int toc3d_motion_queries(const float* w, int64_t n_stages, int64_t w_stride, con
     TOC3D_REQUIRE(w && queries && ref_points && vel && timestamp && ego_pose && ego_pose_inv && out, "toc3d_motion_queries: null buffer");
     TOC3D_REQUIRE(n_stages >= 1 && (n_stages == 1 || w_stride >= MW::total), "toc3d_motion_queries: bad n_stages / w_stride");
     if (B <= 0 || Q <= 0) return TOC3D_OK;
+    TOC3D_REQUIRE(B <= kMaxCount && Q <= kMaxCount && B * Q <= kMaxCount, "toc3d_motion_queries: too many queries (B * Q is counted in 32 bits)");
     const int64_t groups = (B * Q + QB - 1) / QB;
+    TOC3D_REQUIRE(n_stages <= kMaxCount / groups, "toc3d_motion_queries: too many workgroups (n_stages * ceil(B * Q / 8) is counted in 32 bits)");
     toc3d_launch(motion_queries_kernel, dim3((unsigned)(n_stages * groups)), dim3(1024), 0, as_stream(stream), w, w_stride, queries, ref_points, vel,
                        timestamp, timestamp_is_f64, ego_pose, ego_pose_inv, (int)Q, (int)(B * Q), (int)groups, out);
     TOC3D_LAUNCH_CHECK("toc3d_motion_queries");
@@ -534,7 +541,10 @@ int toc3d_motion_queries(const float* w, int64_t n_stages, int64_t w_stride, con
 int toc3d_collapse_query_scorer(const float* mq, const float* w_in, const float* b_in, const float* w_agg, const float* b_agg,
                                 int64_t B, int64_t Q, int64_t C, float scale, float* wc, float* bc, toc3d_stream_t stream) {
     TOC3D_REQUIRE(mq && w_in && b_in && w_agg && b_agg && wc && bc, "toc3d_collapse_query_scorer: null buffer");
+    TOC3D_REQUIRE(Q > 0 && C > 0, "toc3d_collapse_query_scorer: Q and C must be positive");
+    TOC3D_REQUIRE(Q <= kMaxCount && C <= kMaxCount, "toc3d_collapse_query_scorer: Q / C too large (counted in 32 bits)");
     if (B <= 0) return TOC3D_OK;
+    TOC3D_REQUIRE(B <= kMaxGridY, "toc3d_collapse_query_scorer: too many samples (B is a grid dimension, at most 65535)");
     dim3 grid((unsigned)((C + 255) / 256), (unsigned)B);
     toc3d_launch(collapse_kernel, grid, dim3(256), 0, as_stream(stream), mq, w_in, b_in, w_agg, b_agg, (int)Q, (int)C, scale, wc, bc);
     TOC3D_LAUNCH_CHECK("toc3d_collapse_query_scorer");
@@ -546,8 +556,12 @@ int toc3d_score_tokens(const float* x, int64_t C, const float* mask, const float
                        toc3d_stream_t stream) {
     TOC3D_REQUIRE(x && wc && bc && pred && score && mask_out, "toc3d_score_tokens: null buffer");
     TOC3D_REQUIRE(C % 4 == 0 && views_per_frame > 0 && V % views_per_frame == 0, "toc3d_score_tokens: bad dims");
+    TOC3D_REQUIRE(C > 0 && C <= kMaxCount && views_per_frame <= kMaxCount, "toc3d_score_tokens: C / views_per_frame too large or C not positive (counted in 32 bits)");
+    // float4 loads of x + row * C and of wc + b * 2 C: with C % 4 == 0 every row is 16-byte aligned when its base is
+    TOC3D_REQUIRE(aligned16(x) && aligned16(wc), "toc3d_score_tokens: x and wc must be 16-byte aligned");
+    if (V <= 0 || T <= 0) return TOC3D_OK;
+    TOC3D_REQUIRE(V <= kMaxCount && T <= kMaxCount && (V * T + 3) / 4 <= kMaxCount, "toc3d_score_tokens: too many tokens (T, V and ceil(V * T / 4) are counted in 32 bits)");
     const int64_t M = V * T;
-    if (M <= 0) return TOC3D_OK;
     toc3d_launch(score_tokens_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, as_stream(stream), x, (int)C, mask, wc, bc, gumbel, M, (int)T,
                        (int)views_per_frame, pred, score, mask_out);
     TOC3D_LAUNCH_CHECK("toc3d_score_tokens");
@@ -577,7 +591,11 @@ int toc3d_score_head(int dtype, const void* f, int64_t ld, int64_t kdim, const f
                      int64_t M, float* pred, float* score, float* mask_out, toc3d_stream_t stream) {
     TOC3D_REQUIRE(f && w && b && pred && score && mask_out, "toc3d_score_head: null buffer");
     TOC3D_REQUIRE(kdim % 8 == 0 && ld >= kdim && ld % 8 == 0, "toc3d_score_head: kdim / ld must be multiples of 8");
+    TOC3D_REQUIRE(kdim >= 0 && kdim <= kMaxCount, "toc3d_score_head: bad kdim (counted in 32 bits)");
+    // eight elements per load: two float4 (f32) or one 16-byte bf16x8; ld % 8 == 0 keeps every row of either type 16-byte aligned when f is
+    TOC3D_REQUIRE(aligned16(f), "toc3d_score_head: f must be 16-byte aligned");
     if (M <= 0) return TOC3D_OK;
+    TOC3D_REQUIRE(M <= 4 * kMaxCount, "toc3d_score_head: too many rows (ceil(M / 4) is counted in 32 bits)");
     dim3 grid((unsigned)((M + 3) / 4));
     if (dtype == TOC3D_BF16)
         toc3d_launch(score_head_kernel<bf16_t>, grid, dim3(256), 0, as_stream(stream), (const bf16_t*)f, ld, (int)kdim, w, b, gumbel, M, pred, score, mask_out);
@@ -590,7 +608,10 @@ int toc3d_score_head(int dtype, const void* f, int64_t ld, int64_t kdim, const f
 
 int toc3d_global_mean_half(int dtype, void* t, int64_t ld, int64_t V, int64_t T, int64_t C, toc3d_stream_t stream) {
     TOC3D_REQUIRE(t && C % 2 == 0 && ld >= C, "toc3d_global_mean_half: bad arguments");
+    TOC3D_REQUIRE(C > 0 && C <= kMaxCount, "toc3d_global_mean_half: bad C (positive, counted in 32 bits)");
     if (V <= 0 || T <= 0) return TOC3D_OK;
+    TOC3D_REQUIRE(T <= kMaxCount, "toc3d_global_mean_half: too many tokens per view (T is counted in 32 bits)");
+    TOC3D_REQUIRE(V <= kMaxGridY, "toc3d_global_mean_half: too many views (V is a grid dimension, at most 65535)");
     dim3 grid((unsigned)((C / 2 + 63) / 64), (unsigned)V);
     if (dtype == TOC3D_BF16) toc3d_launch(global_mean_half_kernel<bf16_t>, grid, dim3(256), 0, as_stream(stream), (bf16_t*)t, ld, (int)T, (int)C);
     else if (dtype == TOC3D_F32) toc3d_launch(global_mean_half_kernel<float>, grid, dim3(256), 0, as_stream(stream), (float*)t, ld, (int)T, (int)C);
@@ -601,6 +622,8 @@ int toc3d_global_mean_half(int dtype, void* t, int64_t ld, int64_t V, int64_t T,
 
 int toc3d_abs_pos_bicubic(const float* pos, int64_t S, int64_t C, float* out, int64_t h, int64_t w, toc3d_stream_t stream) {
     TOC3D_REQUIRE(pos && out && S > 0 && C > 0 && h > 0 && w > 0, "toc3d_abs_pos_bicubic: bad arguments");
+    TOC3D_REQUIRE(S <= kMaxCount && C <= kMaxCount && h <= kMaxCount && w <= kMaxCount && h * w <= kMaxCount,
+                  "toc3d_abs_pos_bicubic: grid too large (S, C and h * w are counted in 32 bits)");
     if (S == h && S == w) {
         hipError_t e = hipMemcpyAsync(out, pos, (size_t)S * S * C * 4, hipMemcpyDeviceToDevice, as_stream(stream));
         if (e != hipSuccess) { toc3d_set_error("toc3d_abs_pos_bicubic: copy failed: %s", hipGetErrorString(e)); return TOC3D_ERR_LAUNCH; }
