@@ -30,6 +30,7 @@ import torch.nn as nn
 from . import gemm, lib
 from .gemm import DEFAULT_PRECISION, round_up              # (DEFAULT_PRECISION: re-exported, the configs and tests read it from here)
 from .plan import MODES, DerivedState, EagerExec, run_frame
+from .staged import MLN, dim_t
 from .synth import MOTION_DIM, QUERY_DIM, rope_tables
 
 
@@ -106,20 +107,6 @@ class _Block(nn.Module):
         self.mlp = _SwiGLU(dim, int(dim * mlp_ratio), norm_layer)
 
 
-class _MLN(nn.Module):
-    """utils/misc.py:154-188 (parameters + its reset_parameters init)."""
-
-    def __init__(self, c_dim, f_dim=QUERY_DIM):
-        super().__init__()
-        self.reduce = nn.Sequential(nn.Linear(c_dim, f_dim), nn.ReLU())
-        self.gamma = nn.Linear(f_dim, f_dim)
-        self.beta = nn.Linear(f_dim, f_dim)
-        nn.init.zeros_(self.gamma.weight)
-        nn.init.zeros_(self.beta.weight)
-        nn.init.ones_(self.gamma.bias)
-        nn.init.zeros_(self.beta.bias)
-
-
 class _Scorer(nn.Module):
     """MotionAwareQueryGuidedTokenSelector parameters (toc3d_utils.py:99-112,216-224,321-332)."""
 
@@ -135,8 +122,8 @@ class _Scorer(nn.Module):
         self.aggregate = nn.Sequential(nn.Linear(num_queries, 2), nn.LogSoftmax(dim=-1))
         self.pc_range = nn.Parameter(torch.tensor(pc_range, dtype=torch.float32), requires_grad=False)
         self.query_embedding = nn.Sequential(nn.Linear(q * 3 // 2, q), nn.ReLU(), nn.Linear(q, q))
-        self.ego_pose_pe = _MLN(MOTION_DIM)
-        self.ego_pose_queries = _MLN(MOTION_DIM)
+        self.ego_pose_pe = MLN(MOTION_DIM, q, reset_parameters=True)
+        self.ego_pose_queries = MLN(MOTION_DIM, q, reset_parameters=True)
         self.time_embedding = nn.Sequential(nn.Linear(q, q), nn.LayerNorm(q))
 
 
@@ -790,10 +777,7 @@ class ToC3DEVAViT(_BackboneBase):
         torch.cuda.current_stream().synchronize()
         nfl = lib.load().toc3d_motion_weights_floats()
         # positional_encoding.py:18,32 -- same torch expression as the reference, evaluated on the host
-        d3 = torch.arange(128, dtype=torch.float32)
-        d3 = (10000 ** (2 * torch.div(d3, 2, rounding_mode="floor") / 128)).to(dev)
-        d1 = torch.arange(256, dtype=torch.float32)
-        d1 = (10000 ** (2 * torch.div(d1, 2, rounding_mode="floor") / 256)).to(dev)
+        d3, d1 = dim_t(128).to(dev), dim_t(256).to(dev)
         f, pack = self._f32, partial(gemm.pack_weight, dts=self._dts)
         P["scorers"] = []
         keep = []

@@ -19,11 +19,10 @@ import torch
 import torch.nn as nn
 
 from . import gemm, lib
-from . import plan as _plan
 from .gemm import DEFAULT_PRECISION
+from .staged import StagedModule, require_cuda
 
 _ORDER = ("self_attn", "norm", "cross_attn", "norm", "ffn", "norm")
-_SUPPORTED = ("bf16", "fp32x3")
 
 
 class _Attention(nn.Module):                # parameter container: PETRMultiheadAttention / mmcv MultiheadAttention keep an nn.MultiheadAttention under `.attn`
@@ -56,7 +55,7 @@ class _Decoder(nn.Module):
         self.embed_dims = embed_dims
 
 
-SPLITK_VARIANT, _tile_variant = gemm.SPLITK_VARIANT, gemm.small_m_variant      # the tile choice for query-side GEMMs, shared with head_outputs.py
+SPLITK_VARIANT, _tile_variant = gemm.SPLITK_VARIANT, gemm.small_m_variant      # re-exported: tests read the query-side tile rule from here
 
 
 def _parse(encoder, decoder):
@@ -129,21 +128,18 @@ def _parse(encoder, decoder):
     return num_layers, E, H, F
 
 
-class PETRTemporalTransformer(_plan.DerivedState, nn.Module):
+class PETRTemporalTransformer(StagedModule):
+    _NAME, _RUNS, _SUPPORTED = "toc3d_amd.PETRTemporalTransformer", "the decoder runs", ("bf16", "fp32x3")
+    _INSTANCE = dict(StagedModule._INSTANCE, capture=None)
+
     def __init__(self, encoder=None, decoder=None, init_cfg=None, cross=False, precision=DEFAULT_PRECISION, launch_mode="plan"):
         super().__init__()
         L, E, H, F = _parse(encoder, decoder)
-        if precision not in _SUPPORTED:
-            raise NotImplementedError(f"toc3d_amd.PETRTemporalTransformer: precision {precision!r} is not implemented; the decoder runs in "
-                                      f"{' or '.join(repr(p) for p in _SUPPORTED)}")
-        assert launch_mode in _plan.MODES, launch_mode
+        self._init_staged(precision, launch_mode)
         self.encoder = None
         self.decoder = _Decoder(L, E, H, F)
-        self.embed_dims, self.num_heads, self.feedforward_channels, self.num_layers = E, H, F, L
-        self.cross, self.precision, self.launch_mode = cross, precision, launch_mode
+        self.embed_dims, self.num_heads, self.feedforward_channels, self.num_layers, self.cross = E, H, F, L, cross
         self.capture = None                    # test instrument: a dict here receives clones of every norm's output (eager launches only)
-        self._pool = []
-        self._drop_derived()
 
     def init_weights(self):                    # petr_transformer.py:461-466
         for m in self.modules():
@@ -151,15 +147,9 @@ class PETRTemporalTransformer(_plan.DerivedState, nn.Module):
                 nn.init.xavier_uniform_(m.weight)
         self._drop_derived()
 
-    # packed weights, workspaces (the split-K ones of gemm.linear included) and recorded plans, which point into both, are derived state
-    _DERIVED = dict(_packed=None, _ws={}, _states={}, _sk_ws={}, _sk_ws_old=[])
-    _INSTANCE = dict(_pool=[], capture=None)
-
     # ------------------------------------------------------------------------------------------------------------------------------
-    def _pack(self, dev):
-        dts = gemm.dtypes(self.precision)                          # (fp32x3: weights as (hi, lo) planes)
-        f32 = lambda t: t.detach().float().contiguous().to(dev)
-        pack = lambda w, b: (gemm.pack_weight(w, dts, dev), f32(b))
+    def _pack(self, pk):
+        dts, pack = pk.dts, pk.wb                                  # (fp32x3: weights as (hi, lo) planes)
         layers = []
         thirds = lambda a: (a.attn.in_proj_weight.detach().chunk(3), a.attn.in_proj_bias.detach().chunk(3))
         ck, cv, tk, tv = [], [], [], []
@@ -169,20 +159,14 @@ class PETRTemporalTransformer(_plan.DerivedState, nn.Module):
             ck.append((ckw, cbk)); cv.append((cvw, cbv)); tk.append((sk, sbk)); tv.append((sv, sbv))
             f0, f1 = lay.ffns[0].layers[0][0], lay.ffns[0].layers[1]
             layers.append(dict(s_qk=pack(torch.cat([sq, sk]), torch.cat([sbq, sbk])), s_v=pack(sv, sbv),
-                               s_o=pack(lay.attentions[0].attn.out_proj.weight, lay.attentions[0].attn.out_proj.bias),
-                               c_q=pack(cq, cbq), c_o=pack(lay.attentions[1].attn.out_proj.weight, lay.attentions[1].attn.out_proj.bias),
-                               f0=pack(f0.weight, f0.bias), f1=pack(f1.weight, f1.bias),
-                               norms=[(f32(n.weight), f32(n.bias), float(n.eps)) for n in lay.norms]))
+                               s_o=pk.linear(lay.attentions[0].attn.out_proj), c_q=pack(cq, cbq), c_o=pk.linear(lay.attentions[1].attn.out_proj),
+                               f0=pk.linear(f0), f1=pk.linear(f1), norms=[pk.layernorm(n) for n in lay.norms]))
         cat = lambda ps: pack(torch.cat([w for w, _ in ps]), torch.cat([b for _, b in ps]))
         # (the attention reads and writes plain rows: bf16 x 3 products on fp32x3, no planes)
-        P = dict(dt=dts.act, tdt=dts.torch, dta=gemm.attn_dtype(self.precision, x3_attention=True, planes_out=False), layers=layers,
-                 ck=cat(ck), cv=cat(cv), tk=cat(tk), tv=cat(tv), post=(f32(self.decoder.post_norm.weight), f32(self.decoder.post_norm.bias)))
-        torch.cuda.current_stream().synchronize()
-        return P
+        return dict(dt=dts.act, tdt=dts.torch, dta=gemm.attn_dtype(self.precision, x3_attention=True, planes_out=False), layers=layers,
+                    ck=cat(ck), cv=cat(cv), tk=cat(tk), tv=cat(tv), post=pk.layernorm(self.decoder.post_norm)[:2])
 
-    def _workspace(self, key, dev):
-        if key in self._ws:
-            return self._ws[key]
+    def _alloc(self, key, dev):
         B, Nq, Nk, Nm = key
         E, F, L, tdt = self.embed_dims, self.feedforward_channels, self.num_layers, self._packed["tdt"]
         z = lambda r, c, d=tdt: torch.zeros(r, c, dtype=d, device=dev)
@@ -193,71 +177,64 @@ class PETRTemporalTransformer(_plan.DerivedState, nn.Module):
                  att=z(B * Nq, E), qc=z(B * Nq, E), h=z(B * Nq, F), outs=torch.zeros(L, B * Nq, E, dtype=f, device=dev))
         if Nm:
             W.update(tmem=z(B * Nm, E, f), tpos=z(B * Nm, E, f), tm_a=z(B * Nm, E), tm_pa=z(B * Nm, E), tk=z(B * Nm, L * E), tv=z(B * Nm, L * E))
-        self._ws[key] = W
         return W
 
-    def _frame(self, key, W, ex):
+    def _frame(self, key, W):
         """The launch sequence of one frame on the staged inputs of workspace ``W`` (eager or being recorded)."""
         P, (B, Nq, Nk, Nm) = self._packed, key
         E, F, L, H = self.embed_dims, self.feedforward_channels, self.num_layers, self.num_heads
         dt, dta = P["dt"], P["dta"]
         Mq = B * Nq
         cap = None if lib.recording() else self.capture
-        with ex.lane(0):
-            s = lib.stream_ptr()
+        s, linear = lib.stream_ptr(), self._linear
 
-            def linear(a, wb, out, M, N, K, residual=None):
-                wgt, b = wb
-                gemm.linear(self, lib.EPI_BIAS if residual is None else lib.EPI_RESIDUAL, a, wgt, b, out, M, N, K, residual=residual,
-                            ldr=0 if residual is None else residual.shape[1], variant=_tile_variant(M, N, K, residual is not None))
+        def norm(nrm, x_out, act=None, act_pos=None, post=None, out2=None):
+            g, b, eps = nrm
+            lib.call("toc3d_add_layernorm_pos", dt, W["y"], E, g, b, eps, W["qpos"], E, x_out, E, act, E, act_pos, E,
+                     None if post is None else post[0], None if post is None else post[1], out2, E, Mq, E, s)
 
-            def norm(nrm, x_out, act=None, act_pos=None, post=None, out2=None):
-                g, b, eps = nrm
-                lib.call("toc3d_add_layernorm_pos", dt, W["y"], E, g, b, eps, W["qpos"], E, x_out, E, act, E, act_pos, E,
-                         None if post is None else post[0], None if post is None else post[1], out2, E, Mq, E, s)
+        def attention(q, ldq, k, ldk, v, ldv, nk, k2=None, v2=None, ld2=0, nk2=0):
+            lib.call("toc3d_mha_attention_ex", dta, q, ldq, k, ldk, v, ldv, k2, ld2, v2, ld2, W["att"], E, B, Nq, nk, nk2, H, E // H,
+                     float(E // H) ** -0.5, s)
 
-            def attention(q, ldq, k, ldk, v, ldv, nk, k2=None, v2=None, ld2=0, nk2=0):
-                lib.call("toc3d_mha_attention_ex", dta, q, ldq, k, ldk, v, ldv, k2, ld2, v2, ld2, W["att"], E, B, Nq, nk, nk2, H, E // H,
-                         float(E // H) ** -0.5, s)
-
-            off = lambda t, l: t.data_ptr() + l * E * t.element_size()       # layer l's E columns of a [rows, L * E] buffer
-            # once per frame: the inputs in the form the projections read, and the layer-independent keys / values of all layers
-            lib.call("toc3d_add_pos_rows", dt, W["memory"], E, W["pos"], E, W["mem_a"], E, W["mem_pa"], E, B * Nk, E, s)
-            linear(W["mem_pa"], P["ck"], W["ck"], B * Nk, L * E, E)
-            linear(W["mem_a"], P["cv"], W["cv"], B * Nk, L * E, E)
+        off = lambda t, l: t.data_ptr() + l * E * t.element_size()       # layer l's E columns of a [rows, L * E] buffer
+        # once per frame: the inputs in the form the projections read, and the layer-independent keys / values of all layers
+        lib.call("toc3d_add_pos_rows", dt, W["memory"], E, W["pos"], E, W["mem_a"], E, W["mem_pa"], E, B * Nk, E, s)
+        linear(W["mem_pa"], P["ck"], W["ck"], B * Nk, L * E, E)
+        linear(W["mem_a"], P["cv"], W["cv"], B * Nk, L * E, E)
+        if Nm:
+            lib.call("toc3d_add_pos_rows", dt, W["tmem"], E, W["tpos"], E, W["tm_a"], E, W["tm_pa"], E, B * Nm, E, s)
+            linear(W["tm_pa"], P["tk"], W["tk"], B * Nm, L * E, E)
+            linear(W["tm_a"], P["tv"], W["tv"], B * Nm, L * E, E)
+        lib.call("toc3d_add_pos_rows", dt, W["tgt"], E, W["qpos"], E, W["xa"], E, W["xpa"], E, Mq, E, s)
+        x = W["tgt"]
+        x1, x2, x3 = W["x"]
+        for l, lp in enumerate(P["layers"]):
+            # self_attn (:715-734): q, k from query + query_pos, v from query; keys = [query; temp_memory]
+            linear(W["xpa"], lp["s_qk"], W["qk"], Mq, 2 * E, E)
+            linear(W["xa"], lp["s_v"], W["v"], Mq, E, E)
+            k_self = W["qk"].data_ptr() + E * W["qk"].element_size()          # the k half of the fused q | k rows
             if Nm:
-                lib.call("toc3d_add_pos_rows", dt, W["tmem"], E, W["tpos"], E, W["tm_a"], E, W["tm_pa"], E, B * Nm, E, s)
-                linear(W["tm_pa"], P["tk"], W["tk"], B * Nm, L * E, E)
-                linear(W["tm_a"], P["tv"], W["tv"], B * Nm, L * E, E)
-            lib.call("toc3d_add_pos_rows", dt, W["tgt"], E, W["qpos"], E, W["xa"], E, W["xpa"], E, Mq, E, s)
-            x = W["tgt"]
-            x1, x2, x3 = W["x"]
-            for l, lp in enumerate(P["layers"]):
-                # self_attn (:715-734): q, k from query + query_pos, v from query; keys = [query; temp_memory]
-                linear(W["xpa"], lp["s_qk"], W["qk"], Mq, 2 * E, E)
-                linear(W["xa"], lp["s_v"], W["v"], Mq, E, E)
-                k_self = W["qk"].data_ptr() + E * W["qk"].element_size()          # the k half of the fused q | k rows
-                if Nm:
-                    attention(W["qk"], 2 * E, k_self, 2 * E, W["v"], E, Nq, off(W["tk"], l), off(W["tv"], l), L * E, Nm)
-                else:
-                    attention(W["qk"], 2 * E, k_self, 2 * E, W["v"], E, Nq)
-                linear(W["att"], lp["s_o"], W["y"], Mq, E, E, residual=x)
-                norm(lp["norms"][0], x1, act_pos=W["xpa"])
-                # cross_attn (:741-754)
-                linear(W["xpa"], lp["c_q"], W["qc"], Mq, E, E)
-                attention(W["qc"], E, off(W["ck"], l), L * E, off(W["cv"], l), L * E, Nk)
-                linear(W["att"], lp["c_o"], W["y"], Mq, E, E, residual=x1)
-                norm(lp["norms"][1], x2, act=W["xa"])
-                # ffn (:756-759)
-                linear(W["xa"], lp["f0"], W["h"], Mq, F, E)
-                lib.call("toc3d_relu_inplace", dt, W["h"], W["h"].numel(), s)
-                linear(W["h"], lp["f1"], W["y"], Mq, E, F, residual=x2)
-                last = l == L - 1
-                norm(lp["norms"][2], x3, act=None if last else W["xa"], act_pos=None if last else W["xpa"], post=P["post"], out2=W["outs"][l])
-                x = x3
-                if cap is not None:
-                    for n, t in enumerate((x1, x2, x3)):
-                        cap[f"l{l}_norm{n}"] = t.clone().view(B, Nq, E)
+                attention(W["qk"], 2 * E, k_self, 2 * E, W["v"], E, Nq, off(W["tk"], l), off(W["tv"], l), L * E, Nm)
+            else:
+                attention(W["qk"], 2 * E, k_self, 2 * E, W["v"], E, Nq)
+            linear(W["att"], lp["s_o"], W["y"], Mq, E, E, residual=x)
+            norm(lp["norms"][0], x1, act_pos=W["xpa"])
+            # cross_attn (:741-754)
+            linear(W["xpa"], lp["c_q"], W["qc"], Mq, E, E)
+            attention(W["qc"], E, off(W["ck"], l), L * E, off(W["cv"], l), L * E, Nk)
+            linear(W["att"], lp["c_o"], W["y"], Mq, E, E, residual=x1)
+            norm(lp["norms"][1], x2, act=W["xa"])
+            # ffn (:756-759)
+            linear(W["xa"], lp["f0"], W["h"], Mq, F, E)
+            lib.call("toc3d_relu_inplace", dt, W["h"], W["h"].numel(), s)
+            linear(W["h"], lp["f1"], W["y"], Mq, E, F, residual=x2)
+            last = l == L - 1
+            norm(lp["norms"][2], x3, act=None if last else W["xa"], act_pos=None if last else W["xpa"], post=P["post"], out2=W["outs"][l])
+            x = x3
+            if cap is not None:
+                for n, t in enumerate((x1, x2, x3)):
+                    cap[f"l{l}_norm{n}"] = t.clone().view(B, Nq, E)
 
     @torch.no_grad()
     def forward(self, memory, tgt, query_pos, pos_embed, attn_masks, temp_memory=None, temp_pos=None, mask=None, reg_branch=None):
@@ -268,8 +245,7 @@ class PETRTemporalTransformer(_plan.DerivedState, nn.Module):
         Returns ``(outs_dec (L, B, Nq, E) f32, memory, None)``.  The reference's third element is the stack of head-averaged cross-attention maps; at
         eval nothing but ``TokenSelectionLoss`` reads them, so an inference library returns ``None`` there.  ``outs_dec`` is freshly allocated (it aliases no
         workspace); ``memory`` is the caller's tensor."""
-        if not isinstance(memory, torch.Tensor) or not memory.is_cuda:
-            raise RuntimeError("toc3d_amd.PETRTemporalTransformer: inputs must be CUDA/HIP tensors -- the HIP extension is the only compute path (no CPU fallback)")
+        require_cuda(self._NAME, memory)
         if mask is not None:
             raise NotImplementedError("toc3d_amd.PETRTemporalTransformer: key_padding_mask is not implemented (the head passes None)")
         if attn_masks is not None and bool(torch.as_tensor(attn_masks).any()):
@@ -283,8 +259,6 @@ class PETRTemporalTransformer(_plan.DerivedState, nn.Module):
         assert E == self.embed_dims and query_pos.shape == (B, Nq, E) and pos_embed.shape == (B, Nk, E) and (tgt is None or tgt.shape == (B, Nq, E))
         assert Nm == 0 or (temp_memory.shape == (B, Nm, E) and temp_pos.shape == (B, Nm, E))
         with torch.cuda.device(dev):
-            if self._packed is None:
-                self._packed = self._pack(dev)
             key = (B, Nq, Nk, Nm)
             W = self._workspace(key, dev)
             # inputs -> the fixed buffers the (recorded) launches read
@@ -297,7 +271,6 @@ class PETRTemporalTransformer(_plan.DerivedState, nn.Module):
             if Nm:
                 pairs += [(W["tmem"], c(temp_memory)), (W["tpos"], c(temp_pos))]
             lib.copy_segments(pairs, lib.stream_ptr())
-            mode = "eager" if self.capture is not None else self.launch_mode
-            _plan.run_frame(self._states.setdefault(key, {}), mode, 1, lambda ex: self._frame(key, W, ex), self._pool)
+            self._run(key, lambda: self._frame(key, W), mode="eager" if self.capture is not None else None)
             outs = W["outs"].clone().view(self.num_layers, B, Nq, E)
         return outs, memory, None

@@ -87,6 +87,27 @@ def pack_weight(w: torch.Tensor, dts: Dtypes, device=None):
     return planes(out, dts)
 
 
+class Packer:
+    """What a module's ``_pack`` turns parameters into device operands with, for one precision (``dts``) and device."""
+
+    def __init__(self, dts: Dtypes, dev):
+        self.dts, self.dev = dts, dev
+
+    def f32(self, t):
+        return t.detach().float().contiguous().to(self.dev)
+
+    def wb(self, w, b):
+        """f32 [N, K] weight and [N] bias -> (packed weight, f32 bias)."""
+        return pack_weight(w, self.dts, self.dev), self.f32(b)
+
+    def linear(self, *layers):
+        """``nn.Linear`` layers of one K, concatenated along N -> (packed weight, f32 bias)."""
+        return self.wb(torch.cat([l.weight.detach() for l in layers]), torch.cat([l.bias.detach() for l in layers]))
+
+    def layernorm(self, m):
+        return self.f32(m.weight), self.f32(m.bias), float(m.eps)
+
+
 # ------------------------------------------------------------------------------------------------
 # the launcher
 SPLITK_VARIANT = 4014     # four K slices on 64x64 tiles, added in slice order (include/toc3d.h, the fused GEMM's split-K entry point)

@@ -20,11 +20,10 @@ from typing import Optional, Sequence
 import torch
 import torch.nn as nn
 
-from . import gemm, lib
-from . import plan as _plan
+from . import lib
 from .gemm import DEFAULT_PRECISION
+from .staged import StagedModule, host_range, require_cuda
 
-_SUPPORTED = ("bf16", "fp32x3")
 _NAME = "toc3d_amd.HeadOutputs"
 DECODE_MAX_SLOTS, DECODE_MAX_NUM = 16384, 2048          # csrc/head_outputs.hip: num_query * num_classes keys in registers, max_num entries in LDS
 
@@ -52,12 +51,10 @@ class NMSFreeCoder:
         ``StreamPETRHead.get_bboxes`` (:1066)."""
         if self.post_center_range is None:
             raise NotImplementedError("Need to reorganize output as a batch, only support post_center_range is not None for now!")
-        if not isinstance(cls_scores, torch.Tensor) or not isinstance(bbox_preds, torch.Tensor):
-            raise RuntimeError("toc3d_amd.NMSFreeCoder: inputs must be CUDA/HIP tensors -- the HIP extension is the only compute path (no CPU fallback)")
+        require_cuda("toc3d_amd.NMSFreeCoder", cls_scores, bbox_preds, on_device=False)
         if cls_scores.dim() != 3 or bbox_preds.dim() != 3 or cls_scores.shape[-1] != self.num_classes or bbox_preds.shape[:2] != cls_scores.shape[:2]:
             raise ValueError(f"toc3d_amd.NMSFreeCoder: cls_scores {tuple(cls_scores.shape)} / bbox_preds {tuple(bbox_preds.shape)} do not fit num_classes={self.num_classes}")
-        if not cls_scores.is_cuda:
-            raise RuntimeError("toc3d_amd.NMSFreeCoder: inputs must be CUDA/HIP tensors -- the HIP extension is the only compute path (no CPU fallback)")
+        require_cuda("toc3d_amd.NMSFreeCoder", cls_scores)
         B, Q, NC = cls_scores.shape
         CS = bbox_preds.shape[-1]
         dev = cls_scores.device
@@ -70,7 +67,7 @@ class NMSFreeCoder:
             scores = torch.empty(B, K, dtype=torch.float32, device=dev)
             labels, qidx = (torch.empty(B, K, dtype=torch.int64, device=dev) for _ in range(2))
             counts = torch.empty(B, dtype=torch.int64, device=dev)
-            pcr = torch.tensor([float(v) for v in self.post_center_range], dtype=torch.float32)          # host: the C ABI reads it at call time
+            pcr = host_range(self.post_center_range)                  # (the C ABI reads it at call time)
             thr = self.score_threshold
             lib.call("toc3d_nms_free_decode", cls, NC, box, CS, B, Q, NC, CS, K, pcr, int(bool(thr)), float(thr) if thr else 0.0, int(bool(sub_half_height)),
                      boxes, scores, labels, qidx, counts, lib.stream_ptr())
@@ -90,7 +87,9 @@ class NMSFreeCoder:
         return self._listed(preds_dicts["all_cls_scores"][-1], preds_dicts["all_bbox_preds"][-1])
 
 
-class HeadOutputs(_plan.DerivedState, nn.Module):
+class HeadOutputs(StagedModule):
+    _NAME, _RUNS, _SUPPORTED = _NAME, "the branches run", ("bf16", "fp32x3")
+
     def __init__(self, num_classes=10, embed_dims=256, num_reg_fcs=2, code_size=10, num_pred=6, normedlinear=False,
                  pc_range: Sequence[float] = (-51.2, -51.2, -5.0, 51.2, 51.2, 3.0), bbox_coder=None, precision=DEFAULT_PRECISION, launch_mode="plan",
                  levels="all"):
@@ -99,8 +98,7 @@ class HeadOutputs(_plan.DerivedState, nn.Module):
             _no("normedlinear=True (NormedLinear)")
         if num_reg_fcs != 2:
             _no(f"num_reg_fcs={num_reg_fcs}")
-        if precision not in _SUPPORTED:
-            raise NotImplementedError(f"{_NAME}: precision {precision!r} is not implemented; the branches run in {' or '.join(repr(p) for p in _SUPPORTED)}")
+        self._init_staged(precision, launch_mode)
         if levels not in ("all", "last"):
             _no(f"levels={levels!r} (use 'all' or 'last')")
         E = embed_dims
@@ -110,10 +108,9 @@ class HeadOutputs(_plan.DerivedState, nn.Module):
             _no(f"code_size={code_size} (8, or >= 10 with the velocity in columns 8, 9)")
         if num_classes < 1 or num_classes > 64 or code_size > 64 or num_pred < 1:
             _no(f"num_classes={num_classes} / code_size={code_size} / num_pred={num_pred}")
-        assert launch_mode in _plan.MODES, launch_mode
         self.num_classes, self.cls_out_channels, self.embed_dims, self.num_reg_fcs = num_classes, num_classes, E, num_reg_fcs
         self.code_size, self.num_pred, self.normedlinear = code_size, num_pred, False
-        self.precision, self.launch_mode, self.levels = precision, launch_mode, levels
+        self.levels = levels
         # _init_layers :239-260 -- the SAME module num_pred times
         cls_branch, reg_branch = [], []
         for _ in range(num_reg_fcs):
@@ -123,69 +120,51 @@ class HeadOutputs(_plan.DerivedState, nn.Module):
         fc_reg = nn.Sequential(*reg_branch, nn.Linear(E, code_size))
         self.cls_branches = nn.ModuleList([fc_cls for _ in range(num_pred)])
         self.reg_branches = nn.ModuleList([fc_reg for _ in range(num_pred)])
-        self._pc = torch.tensor([float(v) for v in pc_range], dtype=torch.float32)      # host copy: the C ABI takes pc_range from the host
-        assert self._pc.numel() == 6
+        self._pc = host_range(pc_range)
         self.pc_range = [float(v) for v in pc_range]
         if isinstance(bbox_coder, dict):
             from .registry import build_bbox_coder
             bbox_coder = build_bbox_coder(bbox_coder)
         self.bbox_coder: Optional[NMSFreeCoder] = bbox_coder
-        self._pool = []
-        self._drop_derived()
 
     def init_weights(self):                    # :309-312
         for m in self.cls_branches:
             nn.init.constant_(m[-1].bias, -4.59511985013459)          # bias_init_with_prob(0.01)
         self._drop_derived()
 
-    _DERIVED = dict(_packed=None, _ws={}, _states={}, _sk_ws={}, _sk_ws_old=[])
-    _INSTANCE = dict(_pool=[])
-
     # ------------------------------------------------------------------------------------------------------------------------------
-    def _pack(self, dev):
-        dts = gemm.dtypes(self.precision)                          # (fp32x3: weights and the GEMMs' A rows as (hi, lo) planes)
-        f32 = lambda t: t.detach().float().contiguous().to(dev)
+    def _pack(self, pk):
+        dts, f32 = pk.dts, pk.f32                                  # (fp32x3: weights and the GEMMs' A rows as (hi, lo) planes)
         c, r = self.cls_branches[0], self.reg_branches[0]
-        pack = lambda w, b: (gemm.pack_weight(w, dts, dev), f32(b))
-        P = dict(rows=dts.rows, tdt=dts.torch, planes=dts.x3p,
-                 l1=pack(torch.cat([c[0].weight.detach(), r[0].weight.detach()]), torch.cat([c[0].bias.detach(), r[0].bias.detach()])),
-                 l2c=pack(c[3].weight, c[3].bias), l2r=pack(r[2].weight, r[2].bias),
-                 ln1=(f32(c[1].weight), f32(c[1].bias), float(c[1].eps)), ln2=(f32(c[4].weight), f32(c[4].bias), float(c[4].eps)),
-                 wc=f32(c[6].weight), bc=f32(c[6].bias), wr=f32(r[4].weight), br=f32(r[4].bias))
-        torch.cuda.current_stream().synchronize()
-        return P
+        return dict(rows=dts.rows, tdt=dts.torch, planes=dts.x3p, l1=pk.linear(c[0], r[0]), l2c=pk.linear(c[3]), l2r=pk.linear(r[2]),
+                    ln1=pk.layernorm(c[1]), ln2=pk.layernorm(c[4]), wc=f32(c[6].weight), bc=f32(c[6].bias), wr=f32(r[4].weight), br=f32(r[4].bias))
 
-    def _workspace(self, key, dev):
-        if key in self._ws:
-            return self._ws[key]
+    def _alloc(self, key, dev):
         Lc, B, Q = key
         M, E, tdt, f = Lc * B * Q, self.embed_dims, self._packed["tdt"], torch.float32
         z = lambda r, c, d=f: torch.zeros(r, c, dtype=d, device=dev)
-        W = dict(x=z(M, E), clean=z(M, E), a0=z(M, E, tdt), h1=z(M, 2 * E), a1=z(M, 2 * E, tdt), h2=z(M, 2 * E), ref=z(B * Q, 3),
-                 cls=z(M, self.cls_out_channels), box=z(M, self.code_size))
-        self._ws[key] = W
-        return W
+        return dict(x=z(M, E), clean=z(M, E), a0=z(M, E, tdt), h1=z(M, 2 * E), a1=z(M, 2 * E, tdt), h2=z(M, 2 * E), ref=z(B * Q, 3),
+                    cls=z(M, self.cls_out_channels), box=z(M, self.code_size))
 
-    def _frame(self, key, W, ex):
+    def _frame(self, key, W):
         """The launch sequence of one frame on the staged inputs of workspace ``W`` (eager or being recorded)."""
         P, (Lc, B, Q) = self._packed, key
         M, E, NC, CS = Lc * B * Q, self.embed_dims, self.cls_out_channels, self.code_size
-        with ex.lane(0):
-            s = lib.stream_ptr()
+        s = lib.stream_ptr()
 
-            def linear(a, wb, out, N, lda, ldo):               # f32 rows out (the LayerNorm statistics are taken on unrounded sums in both precisions)
-                gemm.linear(self, lib.EPI_RESIDUAL, a, wb[0], wb[1], out, M, N, E, lda=lda, ldo=ldo, a_planes=P["planes"], variant=gemm.small_m_variant(M, N, E, False))
+        def linear(a, wb, out, N, lda, ldo):               # f32 rows out (the LayerNorm statistics are taken on unrounded sums in both precisions)
+            self._linear(a, wb, out, M, N, E, f32_out=True, lda=lda, ldo=ldo, a_planes=P["planes"])
 
-            lib.call("toc3d_head_nan_to_num_rows", P["rows"], W["x"], E, W["clean"], E, W["a0"], E, M, E, s)
-            linear(W["a0"], P["l1"], W["h1"], 2 * E, E, 2 * E)                                   # class tower | box tower, first layers
-            g, b, eps = P["ln1"]
-            lib.call("toc3d_head_ln_relu_rows", P["rows"], W["h1"], 2 * E, g, b, eps, W["a1"], 2 * E, M, E, E, s)
-            half = lambda t: t.data_ptr() + E * t.element_size()                               # the box tower's E columns of a [M, 2E] buffer
-            linear(W["a1"], P["l2c"], W["h2"], E, 2 * E, 2 * E)
-            linear(half(W["a1"]), P["l2r"], half(W["h2"]), E, 2 * E, 2 * E)
-            g, b, eps = P["ln2"]
-            lib.call("toc3d_head_outputs", W["h2"], 2 * E, g, b, eps, P["wc"], P["bc"], P["wr"], P["br"], W["ref"], B * Q, self._pc,
-                     W["cls"], NC, W["box"], CS, M, E, NC, CS, s)
+        lib.call("toc3d_head_nan_to_num_rows", P["rows"], W["x"], E, W["clean"], E, W["a0"], E, M, E, s)
+        linear(W["a0"], P["l1"], W["h1"], 2 * E, E, 2 * E)                                   # class tower | box tower, first layers
+        g, b, eps = P["ln1"]
+        lib.call("toc3d_head_ln_relu_rows", P["rows"], W["h1"], 2 * E, g, b, eps, W["a1"], 2 * E, M, E, E, s)
+        half = lambda t: t.data_ptr() + E * t.element_size()                               # the box tower's E columns of a [M, 2E] buffer
+        linear(W["a1"], P["l2c"], W["h2"], E, 2 * E, 2 * E)
+        linear(half(W["a1"]), P["l2r"], half(W["h2"]), E, 2 * E, 2 * E)
+        g, b, eps = P["ln2"]
+        lib.call("toc3d_head_outputs", W["h2"], 2 * E, g, b, eps, P["wc"], P["bc"], P["wr"], P["br"], W["ref"], B * Q, self._pc,
+                 W["cls"], NC, W["box"], CS, M, E, NC, CS, s)
 
     @torch.no_grad()
     def forward(self, outs_dec, reference_points):
@@ -193,23 +172,19 @@ class HeadOutputs(_plan.DerivedState, nn.Module):
         all_cls_scores, all_bbox_preds)``: the ``nan_to_num``-cleaned copy of ``outs_dec`` (L, B, Q, E), class logits (L, B, Q, num_classes) and boxes
         (L, B, Q, code_size) with centres in ``pc_range`` -- all three freshly allocated (none aliases a workspace).  With ``levels="last"`` only the last level
         is computed and returned (leading dimension 1): ``[-1]`` is all that ``post_update_memory``, ``decode`` and evaluation read."""
-        if not isinstance(outs_dec, torch.Tensor) or not isinstance(reference_points, torch.Tensor):
-            raise RuntimeError(f"{_NAME}: inputs must be CUDA/HIP tensors -- the HIP extension is the only compute path (no CPU fallback)")
+        require_cuda(_NAME, outs_dec, reference_points, on_device=False)
         if outs_dec.dim() != 4 or outs_dec.shape[-1] != self.embed_dims or tuple(reference_points.shape) != (*outs_dec.shape[1:3], 3):
             raise ValueError(f"{_NAME}: outs_dec {tuple(outs_dec.shape)} / reference_points {tuple(reference_points.shape)} do not fit embed_dims={self.embed_dims}")
-        if not outs_dec.is_cuda:
-            raise RuntimeError(f"{_NAME}: inputs must be CUDA/HIP tensors -- the HIP extension is the only compute path (no CPU fallback)")
+        require_cuda(_NAME, outs_dec)
         L, B, Q, E = outs_dec.shape
         src = outs_dec if self.levels == "all" else outs_dec[-1:]
         Lc, dev = src.shape[0], outs_dec.device
         with torch.cuda.device(dev):
-            if self._packed is None:
-                self._packed = self._pack(dev)
             key = (Lc, B, Q)
             W = self._workspace(key, dev)
             c = lambda t, w: t.detach().to(device=dev, dtype=torch.float32).reshape(-1, w).contiguous()
             lib.copy_segments([(W["x"], c(src, E)), (W["ref"], c(reference_points, 3))], lib.stream_ptr())
-            _plan.run_frame(self._states.setdefault(key, {}), self.launch_mode, 1, lambda ex: self._frame(key, W, ex), self._pool)
+            self._run(key, lambda: self._frame(key, W))
             return (W["clean"].clone().view(Lc, B, Q, E), W["cls"].clone().view(Lc, B, Q, self.cls_out_channels),
                     W["box"].clone().view(Lc, B, Q, self.code_size))
 

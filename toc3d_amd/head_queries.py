@@ -22,69 +22,49 @@ import torch
 import torch.nn as nn
 
 from . import gemm, lib
-from . import plan as _plan
 from .gemm import DEFAULT_PRECISION
-from .head_tokens import _MLN
+from .staged import MLN, StagedModule, dim_t, host_range, require_cuda          # (dim_t: re-exported, tests and a tool read it from here)
 
-_SUPPORTED = ("bf16", "fp32x3", "fp32")
-_NAME = "toc3d_amd.HeadQueries"
 _MAX_STATES = 8                      # recorded plans kept per module: a plan names its input buffers (a TemporalMemory alternates between two banks)
 
 
-def dim_t(num_pos_feats: int, temperature: float = 10000) -> torch.Tensor:
-    """The reference's expression for ``dim_t`` (``positional_encoding.py:17-18`` / :31-32), on the host: the kernels take the table, they do not recompute it."""
-    t = torch.arange(num_pos_feats, dtype=torch.float32)
-    return temperature ** (2 * torch.div(t, 2, rounding_mode="floor") / num_pos_feats)
+class HeadQueries(StagedModule):
+    _NAME, _RUNS, _SUPPORTED = "toc3d_amd.HeadQueries", "the query side runs", ("bf16", "fp32x3", "fp32")
+    _DERIVED = dict(StagedModule._DERIVED, _fresh=None)
 
-
-class HeadQueries(_plan.DerivedState, nn.Module):
     def __init__(self, num_query=644, memory_len=1024, num_propagated=256, embed_dims=256, with_ego_pos=True,
                  pc_range: Sequence[float] = (-51.2, -51.2, -5.0, 51.2, 51.2, 3.0), precision=DEFAULT_PRECISION, launch_mode="plan"):
         super().__init__()
         if embed_dims != 256:
-            raise NotImplementedError(f"{_NAME}: embed_dims={embed_dims} is not implemented: the reference fixes 256 (pos2posemb3d yields 3 * 128 = embed_dims * 3 // 2 "
+            raise NotImplementedError(f"{self._NAME}: embed_dims={embed_dims} is not implemented: the reference fixes 256 (pos2posemb3d yields 3 * 128 = embed_dims * 3 // 2 "
                                       "columns, pos2posemb1d 256, MLN(180) has f_dim 256)")
-        if precision not in _SUPPORTED:
-            raise NotImplementedError(f"{_NAME}: precision {precision!r} is not implemented; the query side runs in {' or '.join(repr(p) for p in _SUPPORTED)}")
+        self._init_staged(precision, launch_mode)
         if not (num_query > 0 and memory_len > 0 and 0 <= num_propagated <= memory_len):
-            raise ValueError(f"{_NAME}: num_query={num_query}, memory_len={memory_len}, num_propagated={num_propagated} (need 0 <= num_propagated <= memory_len)")
-        assert launch_mode in _plan.MODES, launch_mode
+            raise ValueError(f"{self._NAME}: num_query={num_query}, memory_len={memory_len}, num_propagated={num_propagated} (need 0 <= num_propagated <= memory_len)")
         E = embed_dims
         self.num_query, self.memory_len, self.num_propagated, self.embed_dims, self.with_ego_pos = num_query, memory_len, num_propagated, E, bool(with_ego_pos)
-        self.precision, self.launch_mode = precision, launch_mode
         self.reference_points = nn.Embedding(num_query, 3)                                                  # :277
         self.query_embedding = nn.Sequential(nn.Linear(E * 3 // 2, E), nn.ReLU(), nn.Linear(E, E))          # :282-286
         self.time_embedding = nn.Sequential(nn.Linear(E, E), nn.LayerNorm(E))                               # :290-293
         if self.with_ego_pos:                                                                               # :296-298
-            self.ego_pose_pe, self.ego_pose_memory = _MLN(180, E), _MLN(180, E)
-        self._pc = torch.tensor([float(v) for v in pc_range], dtype=torch.float32)      # host copy: the C ABI takes pc_range from the host
-        assert self._pc.numel() == 6
+            self.ego_pose_pe, self.ego_pose_memory = MLN(180, E), MLN(180, E)
+        self._pc = host_range(pc_range)
         self._unit = torch.tensor([0.0, 0.0, 0.0, 1.0, 1.0, 1.0], dtype=torch.float32)    # the learned points are already normalised: (p - 0) / 1 = p
         self.pc_range = [float(v) for v in pc_range]
         self.fresh_builds = 0                       # how often the learned queries' half was computed (once per set of weights and device)
-        self._pool = []
-        self._drop_derived()
 
     def init_weights(self):                         # :303
         nn.init.uniform_(self.reference_points.weight.data, 0, 1)
         self._drop_derived()
 
-    _DERIVED = dict(_packed=None, _fresh=None, _ws={}, _states={}, _sk_ws={}, _sk_ws_old=[])
-    _INSTANCE = dict(_pool=[])
-
     # ------------------------------------------------------------------------------------------------------------------------------
-    def _pack(self, dev):
-        dts = gemm.dtypes(self.precision)                          # (fp32x3: weights and the input kernel's rows as (hi, lo) planes)
-        f32 = lambda t: t.detach().float().contiguous().to(dev)
-        pack = lambda w, b: (gemm.pack_weight(w, dts, dev), f32(b))
-        cat = lambda *ls: pack(torch.cat([l.weight.detach() for l in ls]), torch.cat([l.bias.detach() for l in ls]))
-        te_ln = self.time_embedding[1]
-        P = dict(dts=dts, qe0=cat(self.query_embedding[0]), qe2=cat(self.query_embedding[2]), te=cat(self.time_embedding[0]),
-                 te_ln=(f32(te_ln.weight), f32(te_ln.bias), float(te_ln.eps)), dimt3=dim_t(128).to(dev), dimt1=dim_t(256).to(dev))
+    def _pack(self, pk):
+        cat = pk.linear                                            # (fp32x3: weights and the input kernel's rows as (hi, lo) planes)
+        P = dict(dts=pk.dts, qe0=cat(self.query_embedding[0]), qe2=cat(self.query_embedding[2]), te=cat(self.time_embedding[0]),
+                 te_ln=pk.layernorm(self.time_embedding[1]), dimt3=dim_t(128).to(pk.dev), dimt1=dim_t(256).to(pk.dev))
         if self.with_ego_pos:
             pe, mem = self.ego_pose_pe, self.ego_pose_memory
             P.update(red=cat(pe.reduce[0], mem.reduce[0]), gb_pe=cat(pe.gamma, pe.beta), gb_mem=cat(mem.gamma, mem.beta))
-        torch.cuda.current_stream().synchronize()
         return P
 
     def _scratch(self, M, dev):
@@ -104,8 +84,7 @@ class HeadQueries(_plan.DerivedState, nn.Module):
         (ref, ref_s), (vel, vel_s), (ts, ts_s), (pose, pose_s), (emb, emb_s), pc = src
 
         def linear(a, wb, out, N, K, lda, ldo, f32_out, planes):
-            gemm.linear(self, lib.EPI_RESIDUAL if f32_out else lib.EPI_BIAS, a, wb[0], wb[1], out, M, N, K, lda=lda, ldo=ldo, a_planes=planes and dts.x3p,
-                        variant=gemm.small_m_variant(M, N, K, False))
+            self._linear(a, wb, out, M, N, K, f32_out=f32_out, lda=lda, ldo=ldo, a_planes=planes and dts.x3p)
 
         lib.call("toc3d_head_query_inputs", dts.rows, ref, ref_s, vel, vel_s, ts, ts_s, pose, pose_s, pc, P["dimt3"], P["dimt1"], S["pos3d"], 384,
                  S["nerf"] if ego else None, 192, S["t1d"], 256, dst["ref_tail"], dst["ref_stride"], B, n, np_, E, s)
@@ -138,10 +117,10 @@ class HeadQueries(_plan.DerivedState, nn.Module):
         self.fresh_builds += 1
         return dict(query_pos=qpos, tgt=tgt, reference_points=ref)
 
-    def _workspace(self, key, dev):
+    def _alloc(self, key, dev):
         """Scratch rows and ONE flat buffer that holds the six outputs; its learned-query rows and ``rec_ego_pose`` are written here, once."""
-        if key in self._ws:
-            return self._ws[key]
+        if self._fresh is None:
+            self._fresh = self._build_fresh(dev)
         B, n = key
         nq, np_, E = self.num_query, self.num_propagated, self.embed_dims
         Q, nt = nq + np_, n - np_
@@ -161,9 +140,7 @@ class HeadQueries(_plan.DerivedState, nn.Module):
         dst = dict(ref_tail=tail(out["reference_points"], 3) if np_ else None, ref_stride=Q * 3, qpos_tail=tail(out["query_pos"], E) if np_ else None,
                    tgt_tail=tail(out["tgt"], E) if np_ else None, tail_stride=Q * E, temp_pos=out["temp_pos"] if nt else None,
                    temp_mem=out["temp_memory"] if nt else None)
-        W = dict(S=self._scratch(B * n, dev), flat=flat, shapes=shapes, view=view, dst=dst)
-        self._ws[key] = W
-        return W
+        return dict(S=self._scratch(B * n, dev), flat=flat, shapes=shapes, view=view, dst=dst)
 
     @staticmethod
     def _strided(t):
@@ -184,35 +161,21 @@ class HeadQueries(_plan.DerivedState, nn.Module):
         ``rec_ego_pose`` from ``query_pos`` after the concatenation (:447, :449) and so returns ``num_propagated`` surplus identities that nothing can index; they
         are not returned here."""
         ins = (memory_embedding, memory_reference_point, memory_timestamp, memory_egopose, memory_velo)
-        if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in ins):
-            raise RuntimeError(f"{_NAME}: inputs must be CUDA/HIP tensors -- the HIP extension is the only compute path (no CPU fallback)")
+        require_cuda(self._NAME, *ins)
         B, n, E = memory_embedding.shape[0], self.memory_len, self.embed_dims
         if (tuple(memory_embedding.shape) != (B, n, E) or tuple(memory_reference_point.shape) != (B, n, 3) or tuple(memory_timestamp.shape) != (B, n, 1)
                 or tuple(memory_egopose.shape) != (B, n, 4, 4) or tuple(memory_velo.shape) != (B, n, 2)):
-            raise ValueError(f"{_NAME}: bank tensors {[tuple(t.shape) for t in ins]} do not fit memory_len={n}, embed_dims={E}")
+            raise ValueError(f"{self._NAME}: bank tensors {[tuple(t.shape) for t in ins]} do not fit memory_len={n}, embed_dims={E}")
         if memory_timestamp.dtype != torch.float64 or any(t.dtype != torch.float32 for t in (memory_embedding, memory_reference_point, memory_egopose, memory_velo)):
-            raise TypeError(f"{_NAME}: the bank is f32 with f64 timestamps (as toc3d_amd.TemporalMemory keeps it), got {[t.dtype for t in ins]}")
+            raise TypeError(f"{self._NAME}: the bank is f32 with f64 timestamps (as toc3d_amd.TemporalMemory keeps it), got {[t.dtype for t in ins]}")
         dev = memory_embedding.device
         with torch.cuda.device(dev):
-            if self._packed is None:
-                self._packed = self._pack(dev)
-            if self._fresh is None:
-                self._fresh = self._build_fresh(dev)
             W = self._workspace((B, n), dev)
             emb, ref, ts, pose, vel = (self._strided(t.detach()) for t in ins)
             src = (ref, vel, ts, pose, emb, self._pc)
             # a recorded plan names its input buffers: one state per (shape, buffers, strides); the bank alternates between two
             key = (B, n) + tuple((t.data_ptr(), st) for t, st in (ref, vel, ts, pose, emb))
-            state = self._states.get(key)
-            if state is None:
-                while len(self._states) >= _MAX_STATES:
-                    self._states.pop(next(iter(self._states)))
-                state = self._states[key] = {}
-
-            def frame(ex):
-                with ex.lane(0):
-                    self._launches(W["S"], src, W["dst"], B, n, self.num_propagated)
-            _plan.run_frame(state, self.launch_mode, 1, frame, self._pool)
+            self._run(key, lambda: self._launches(W["S"], src, W["dst"], B, n, self.num_propagated), max_states=_MAX_STATES)
             out = W["flat"].clone()
             o = {k: W["view"](out, k, *shp) for k, shp in W["shapes"].items()}
             return o["tgt"], o["query_pos"], o["reference_points"], o["temp_memory"], o["temp_pos"], o["rec_ego_pose"]

@@ -16,16 +16,9 @@ from typing import Sequence
 import torch
 import torch.nn as nn
 
-from . import gemm, lib
+from . import lib
 from .gemm import round_up as _ru
-from .plan import DerivedState
-
-
-class _MLN(nn.Module):                      # parameter container: models/utils/misc.py:161-172
-    def __init__(self, c_dim, f_dim):
-        super().__init__()
-        self.reduce = nn.Sequential(nn.Linear(c_dim, f_dim), nn.ReLU())
-        self.gamma, self.beta = nn.Linear(f_dim, f_dim), nn.Linear(f_dim, f_dim)
+from .staged import MLN, StagedModule, host_range, require_cuda
 
 
 class _SE(nn.Module):                       # models/utils/misc.py:140-145
@@ -34,18 +27,22 @@ class _SE(nn.Module):                       # models/utils/misc.py:140-145
         self.conv_reduce, self.conv_expand = nn.Linear(ch, ch), nn.Linear(ch, ch)
 
 
-class HeadTokenEmbedding(DerivedState, nn.Module):
+class HeadTokenEmbedding(StagedModule):
+    _NAME, _RUNS, _SUPPORTED = "toc3d_amd.HeadTokenEmbedding", "the token side runs", ("bf16", "fp32", "fp32x3")
+
     def __init__(self, in_channels=256, embed_dims=256, depth_num=64, depth_start=1.0, LID=True, stride=16,
                  position_range: Sequence[float] = (-61.2, -61.2, -10.0, 61.2, 61.2, 10.0), precision="fp32", **unused):
         super().__init__()
-        assert precision in ("bf16", "fp32", "fp32x3") and embed_dims <= 1024 and depth_num >= 30
-        self.in_channels, self.embed_dims, self.depth_num, self.stride, self.precision = in_channels, embed_dims, depth_num, stride, precision
+        self._init_staged(precision)                                        # (launched eagerly: the token side is not recorded into a plan)
+        if embed_dims > 1024 or depth_num < 30:
+            raise NotImplementedError(f"{self._NAME}: embed_dims={embed_dims} / depth_num={depth_num} is not implemented (embed_dims <= 1024, depth_num >= 30)")
+        self.in_channels, self.embed_dims, self.depth_num, self.stride = in_channels, embed_dims, depth_num, stride
         E = embed_dims
         self.position_encoder = nn.Sequential(nn.Linear(depth_num * 3, 4 * E), nn.ReLU(), nn.Linear(4 * E, E))       # :262-266
         self.memory_embed = nn.Sequential(nn.Linear(in_channels, E), nn.ReLU(), nn.Linear(E, E))                      # :268-272
-        self.spatial_alignment = _MLN(8, E)                                                                           # :288
+        self.spatial_alignment = MLN(8, E)                                                                            # :288
         self.featurized_pe = _SE(E)                                                                                   # :275
-        pr = torch.tensor(list(position_range), dtype=torch.float32)
+        self._pr = pr = host_range(position_range)
         index = torch.arange(0, depth_num, 1).float()                                                                 # :221-232
         if LID:
             cd = depth_start + (pr[3] - depth_start) / (depth_num * (1 + depth_num)) * index * (index + 1)
@@ -53,8 +50,6 @@ class HeadTokenEmbedding(DerivedState, nn.Module):
             cd = depth_start + (pr[3] - depth_start) / depth_num * index
         self.register_buffer("coords_d", cd, persistent=False)
         self.__dict__["_coords_d_owner"] = None                                         # bind_coords_d: an owner's Parameter that replaces the buffer
-        self._pr = pr                                                       # host copy: the C ABI takes position_range from the host
-        self._drop_derived()
 
     def bind_coords_d(self, param):
         """Read the depth bins from ``param`` (a [depth_num] f32 Parameter of a module that owns this one, which moves and loads with its owner) instead of
@@ -62,79 +57,69 @@ class HeadTokenEmbedding(DerivedState, nn.Module):
         assert tuple(param.shape) == (self.depth_num,)
         self.__dict__["_coords_d_owner"] = param            # (a plain attribute: the parameter stays its owner's, this module's state dict does not grow)
 
-    # packed weights and the workspaces (keyed by shape only: they are the old device's after a move) are derived state
-    _DERIVED = dict(_packed=None, _ws={})
+    def _pack(self, pk):
+        dts, pack = pk.dts, pk.linear
+        return dict(dts=dts, dt=dts.act, tdt=dts.torch, pe0=pack(self.position_encoder[0]), pe2=pack(self.position_encoder[2]), me0=pack(self.memory_embed[0]),
+                    me2=pack(self.memory_embed[2]), red=pack(self.spatial_alignment.reduce[0]), gam=pack(self.spatial_alignment.gamma),
+                    bet=pack(self.spatial_alignment.beta), se1=pack(self.featurized_pe.conv_reduce), se2=pack(self.featurized_pe.conv_expand))
 
-    def _pack(self, dev):
-        dts = gemm.dtypes(self.precision)
-        pack = lambda lin: (gemm.pack_weight(lin.weight, dts, dev), lin.bias.detach().float().contiguous())
-        P = dict(dts=dts, dt=dts.act, tdt=dts.torch, pe0=pack(self.position_encoder[0]), pe2=pack(self.position_encoder[2]), me0=pack(self.memory_embed[0]),
-                 me2=pack(self.memory_embed[2]), red=pack(self.spatial_alignment.reduce[0]), gam=pack(self.spatial_alignment.gamma),
-                 bet=pack(self.spatial_alignment.beta), se1=pack(self.featurized_pe.conv_reduce), se2=pack(self.featurized_pe.conv_expand))
-        torch.cuda.current_stream().synchronize()
-        return P
+    def _alloc(self, key, dev):
+        (B, N, h, w), C, E, D, tdt, f = key, self.in_channels, self.embed_dims, self.depth_num, self._packed["tdt"], torch.float32
+        M = B * N * h * w
+        z = lambda r, c, d=tdt: torch.zeros(r, c, dtype=d, device=dev)
+        return dict(pin=z(M, _ru(3 * D, 64)), cone_a=z(M, 64), cone=z(M, 8, f), h1=z(M, _ru(4 * E, 64)), feat=z(M, _ru(C, 64)), m1=z(M, _ru(E, 64)),
+                    c1=z(M, _ru(E, 64)), mem_a=z(M, _ru(E, 64)), s1=z(M, _ru(E, 64)), pos=z(M, E, f), mem_raw=z(M, E, f), gam=z(M, E, f), bet=z(M, E, f), se=z(M, E, f))
 
     @torch.no_grad()
     def forward(self, img_feats: torch.Tensor, intrinsics: torch.Tensor, lidar2img: torch.Tensor, pad_shape):
         """img_feats (B, N, C, h, w) f32 (neck level 0, ``data['img_feats']`` :626); intrinsics / lidar2img (B, N, 4, 4);
         pad_shape = (pad_h, pad_w[, 3]) of ``img_metas[0]['pad_shape'][0]``.  Returns (memory, pos_embed, cone): memory and pos_embed
         f32 (B, N*h*w, embed_dims), cone f32 (B, N*h*w, 8) (:419-421) -- all three freshly allocated, none aliases a workspace."""
-        if not isinstance(img_feats, torch.Tensor) or not img_feats.is_cuda:
-            raise RuntimeError("toc3d_amd.HeadTokenEmbedding: inputs must be CUDA/HIP tensors -- the HIP extension is the only compute path")
-        dev = img_feats.device
-        if self._packed is None:
-            self._packed = self._pack(dev)
-        P = self._packed
-        dt, tdt, rows = P["dt"], P["tdt"], P["dts"].rows         # rows: the row kernels' output dtype -- the act dtype, or (hi, lo) planes on "fp32x3"
+        require_cuda(self._NAME, img_feats)
         B, N, C, h, w = img_feats.shape
-        assert C == self.in_channels
-        E, D = self.embed_dims, self.depth_num
-        M, s = B * N * h * w, lib.stream_ptr()
-        key = (B, N, h, w)
-        if key not in self._ws:
-            z = lambda r, c, d=tdt: torch.zeros(r, c, dtype=d, device=dev)
-            self._ws[key] = dict(pin=z(M, _ru(3 * D, 64)), cone_a=z(M, 64), cone=z(M, 8, torch.float32), h1=z(M, _ru(4 * E, 64)), feat=z(M, _ru(C, 64)),
-                                 m1=z(M, _ru(E, 64)), c1=z(M, _ru(E, 64)), mem_a=z(M, _ru(E, 64)), s1=z(M, _ru(E, 64)),
-                                 pos=z(M, E, torch.float32), mem_raw=z(M, E, torch.float32), gam=z(M, E, torch.float32), bet=z(M, E, torch.float32),
-                                 se=z(M, E, torch.float32))
-        W = self._ws[key]
-        memory = torch.empty(M, E, dtype=torch.float32, device=dev)
-        pos_embed = torch.empty(M, E, dtype=torch.float32, device=dev)
-        img2lidar = torch.linalg.inv(lidar2img.to(dev).float().reshape(B * N, 4, 4)).contiguous()
-        intr = intrinsics.to(dev).float().reshape(B * N, 4, 4).contiguous()
+        if C != self.in_channels:
+            raise ValueError(f"{self._NAME}: img_feats {tuple(img_feats.shape)} do not fit in_channels={self.in_channels}")
+        dev = img_feats.device
+        with torch.cuda.device(dev):
+            W = self._workspace((B, N, h, w), dev)
+            P = self._packed
+            dt, rows = P["dt"], P["dts"].rows           # rows: the row kernels' output dtype -- the act dtype, or (hi, lo) planes on "fp32x3"
+            E, D = self.embed_dims, self.depth_num
+            M, s = B * N * h * w, lib.stream_ptr()
+            memory = torch.empty(M, E, dtype=torch.float32, device=dev)
+            pos_embed = torch.empty(M, E, dtype=torch.float32, device=dev)
+            img2lidar = torch.linalg.inv(lidar2img.to(dev).float().reshape(B * N, 4, 4)).contiguous()
+            intr = intrinsics.to(dev).float().reshape(B * N, 4, 4).contiguous()
 
-        if self.precision == "fp32x3":
-            # the GEMM family's own launcher: W in planes; A in planes for the four Linears a row kernel feeds -- the four with a ReLU behind them, which the
-            # epilogue applies --, plain f32 (the rows that epilogue left) for the Linear behind each.  Tiles by the query side's rule (64x64 below 256 default tiles).
             def linear(x, wb, out, n, k, f32_out=False, relu=False):
                 wgt, b = wb
-                epi = lib.EPI_RESIDUAL if f32_out else (lib.EPI_BIAS_RELU if relu else lib.EPI_BIAS)
-                gemm.linear(self, epi, x, wgt, b, out, M, n, wgt.shape[1], a_planes=relu, variant=gemm.small_m_variant(M, n, wgt.shape[1], False))
-        else:
-            def linear(x, wb, out, n, k, f32_out=False, relu=False):
-                wgt, b = wb
-                epi = lib.EPI_RESIDUAL if f32_out else lib.EPI_BIAS
-                lib.call("toc3d_linear", dt, epi, x, x.shape[1], wgt, wgt.shape[1], b, out, out.shape[1], None, 0, 0, None, None, M, n, wgt.shape[1], 0, s)
+                if self.precision == "fp32x3":
+                    # the GEMM family's own launcher: W in planes; A in planes for the four Linears a row kernel feeds -- the four with a ReLU behind them, which
+                    # the epilogue applies --, plain f32 (the rows that epilogue left) for the Linear behind each.  Tiles by the query side's rule.
+                    return self._linear(x, wb, out, M, n, wgt.shape[1], f32_out=f32_out, relu=relu, a_planes=relu)
+                lib.call("toc3d_linear", dt, lib.EPI_RESIDUAL if f32_out else lib.EPI_BIAS, x, x.shape[1], wgt, wgt.shape[1], b, out, out.shape[1], None, 0, 0, None, None,
+                         M, n, wgt.shape[1], 0, s)
                 if relu:
                     lib.call("toc3d_relu_inplace", dt, out, out.numel(), s)
 
-        # position_embeding :378-416
-        coords_d = self.coords_d if self._coords_d_owner is None else self._coords_d_owner.detach().float().contiguous()
-        lib.call("toc3d_head_frustum_inputs", rows, img2lidar, intr, coords_d, self._pr, B, N, h, w, D, self.stride, int(pad_shape[0]),
-                 int(pad_shape[1]), W["pin"], W["pin"].shape[1], W["cone_a"], 64, W["cone"], s)
-        linear(W["pin"], P["pe0"], W["h1"], 4 * E, 3 * D, relu=True)
-        linear(W["h1"], P["pe2"], W["pos"], E, 4 * E, f32_out=True)
-        # memory_embed :635
-        lib.call("toc3d_nchw_to_rows", rows, img_feats.float().contiguous(), W["feat"], W["feat"].shape[1], B * N, C, h * w, s)
-        linear(W["feat"], P["me0"], W["m1"], E, C, relu=True)
-        linear(W["m1"], P["me2"], W["mem_raw"], E, E, f32_out=True)
-        # spatial_alignment :638
-        linear(W["cone_a"], P["red"], W["c1"], E, 8, relu=True)
-        linear(W["c1"], P["gam"], W["gam"], E, E, f32_out=True)
-        linear(W["c1"], P["bet"], W["bet"], E, E, f32_out=True)
-        lib.call("toc3d_mln_apply", rows, W["mem_raw"], W["gam"], W["bet"], M, E, memory, W["mem_a"], W["mem_a"].shape[1], s)
-        # featurized_pe :639
-        linear(W["mem_a"], P["se1"], W["s1"], E, E, relu=True)
-        linear(W["s1"], P["se2"], W["se"], E, E, f32_out=True)
-        lib.call("toc3d_se_gate", W["pos"], W["se"], pos_embed, M * E, s)
-        return memory.view(B, N * h * w, E), pos_embed.view(B, N * h * w, E), W["cone"].clone().view(B, N * h * w, 8)
+            # position_embeding :378-416
+            coords_d = self.coords_d if self._coords_d_owner is None else self._coords_d_owner.detach().float().contiguous()
+            lib.call("toc3d_head_frustum_inputs", rows, img2lidar, intr, coords_d, self._pr, B, N, h, w, D, self.stride, int(pad_shape[0]),
+                     int(pad_shape[1]), W["pin"], W["pin"].shape[1], W["cone_a"], 64, W["cone"], s)
+            linear(W["pin"], P["pe0"], W["h1"], 4 * E, 3 * D, relu=True)
+            linear(W["h1"], P["pe2"], W["pos"], E, 4 * E, f32_out=True)
+            # memory_embed :635
+            lib.call("toc3d_nchw_to_rows", rows, img_feats.float().contiguous(), W["feat"], W["feat"].shape[1], B * N, C, h * w, s)
+            linear(W["feat"], P["me0"], W["m1"], E, C, relu=True)
+            linear(W["m1"], P["me2"], W["mem_raw"], E, E, f32_out=True)
+            # spatial_alignment :638
+            linear(W["cone_a"], P["red"], W["c1"], E, 8, relu=True)
+            linear(W["c1"], P["gam"], W["gam"], E, E, f32_out=True)
+            linear(W["c1"], P["bet"], W["bet"], E, E, f32_out=True)
+            lib.call("toc3d_mln_apply", rows, W["mem_raw"], W["gam"], W["bet"], M, E, memory, W["mem_a"], W["mem_a"].shape[1], s)
+            # featurized_pe :639
+            linear(W["mem_a"], P["se1"], W["s1"], E, E, relu=True)
+            linear(W["s1"], P["se2"], W["se"], E, E, f32_out=True)
+            lib.call("toc3d_se_gate", W["pos"], W["se"], pos_embed, M * E, s)
+            cone = W["cone"].clone()
+        return memory.view(B, N * h * w, E), pos_embed.view(B, N * h * w, E), cone.view(B, N * h * w, 8)
