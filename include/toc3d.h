@@ -109,20 +109,17 @@ int toc3d_linear(int dtype, int epilogue, const void* A, int64_t lda, const void
                  float* rep_out, const int32_t* rep_index, int64_t M, int64_t N, int64_t K, int64_t n_valid,
                  toc3d_stream_t stream);
 
-/* Same with an explicit tile / pipeline variant (0 = the heuristic toc3d_linear uses): 1 = 128x128 tile, 2-deep
- * LDS ring; 2 = 128x128, 3-deep; 3 = 128x128, 4-deep; 4 = 128x64, 3-deep; 5 = 128x64, 4-deep; 6 = 64x128, 3-deep;
- * 7 = 64x64, 4-deep; 8 = 128x128 single LDS buffer; 9 = 128x64, 2-deep; 10 = 64x128, 2-deep; 11/12 = 128x128 with 32-wide
- * K tiles, 2-/3-deep (bf16 only); 13 = 128x64 single buffer; 14 = 64x64, 2-deep; 15 = variant 8 limited to 128 registers;
- * 16/17 = 128x128 on 8 wavefronts, single / double buffer; 18/19 = 256x128 on 8 wavefronts, double / single buffer;
- * 20 = 128x256, 21 = 256x256 (8 wavefronts, double buffer); 22-27 = K tiles of 128 / 256 elements (22: 128x128 K128,
- * 23: 128x128 K256, 24: 64x128 K256, 25: 128x128 K128 double buffer, 26: 64x128 K128, 27: 64x64 K256).  (1-7, 9-14, 27:
- * 4 wavefronts); 28/29 = 128x128 on 8 wavefronts with a 3-/4-deep ring, 30/31 = the same with 32-wide K tiles 4-/6-deep
- * (bf16), 32 = 256x128 3-deep, 33 = 128x64 on 8 wavefronts 4-deep; 34-37 = 16-wavefront 256x128 / 256x256 / 128x256 tiles;
- * 38/39 = 128x128 on 8 wavefronts with 32-wide K tiles 2-/3-deep, 40-42 = 128x256 / 256x128 single buffer and K32 rings;
- * 43-48 = 128x192 and 128x96 tiles (43/44 single buffer, 45/46 double buffer, 47 = 128x192 with 32x96 per wavefront so that
- * it serves SWIGLU, 48 = 3-deep); 49/50 = 192x128 double / single buffer; 51 = variant 16 compiled for 64 registers (four workgroups per CU); 52/53 = 192x192 single / double buffer;
- * 60-63 = phased 256x256 / 256x128 / 128x256 / 128x128 tiles (bf16, one or two workgroups per CU, four phases per K-tile); 64-66 = register-pipelined 128x128 rings (bf16; 4- and 3-deep with
- * 8 wavefronts, 4-deep with 4: the next K step's fragments are read while the current one multiplies -- for launches that run one workgroup per CU).  A variant whose per-wavefront column slab is not a
+/* Same with an explicit tile / pipeline variant (0 = the heuristic toc3d_linear uses).  The tiles, with their shapes, ring depths and the dtypes each serves, are the
+ * rows of ONE table, TOC3D_GEMM_TILES in toc3d_amd/csrc/gemm_kernels.h (toc3d_amd/lib.py TILES is its host-side twin); in short:
+ *   1, 8, 9, 10, 13, 14, 15, 27 = 4 wavefronts: 128x128 (1: 2-deep LDS ring, 8: single buffer, 15: 8 limited to 128 registers), 128x64 (9: 2-deep, 13: single),
+ *   64x128 (10), 64x64 (14: 2-deep, 27: K tiles of 256 elements);  16, 17, 28, 29, 51 = 128x128 on 8 wavefronts (single buffer, 2- / 3- / 4-deep ring, 51 = 16 compiled
+ *   for 64 registers: four workgroups per CU), 30 = the same 4-deep with 32-wide K tiles (bf16), 19 = 256x128 single buffer, 33 = 128x64 4-deep;
+ *   22, 24, 26 = K tiles of 128 / 256 elements (22: 128x128 K128, 24: 64x128 K256, 26: 64x128 K128);  45, 47 = 128x192 double buffer (47: 32x96 per wavefront, so that
+ *   it serves SWIGLU), 49 = 192x128 double buffer, 52 / 53 = 192x192 single / double buffer;  54-56 = 96x128 (single, 2-, 4-deep), 57 / 58 = 160x128 (single, 2-deep),
+ *   59 = 192x128 3-deep;  60-63 = phased 256x256 / 256x128 / 128x256 / 128x128 tiles (bf16, and bf16 x 3 on planes; one or two workgroups per CU, four phases per
+ *   K-tile);  64-66 = register-pipelined 128x128 rings (bf16; 4- and 3-deep with 8 wavefronts, 4-deep with 4: the next K step's fragments are read while the current one
+ *   multiplies -- for launches that run one workgroup per CU).  Any other id is an error (TOC3D_ERR_ARG), as is an id the dtype is not served on.
+ * A variant whose per-wavefront column slab is not a
  * multiple of 32 cannot serve EPI_SWIGLU (error TOC3D_ERR_UNSUPPORTED).  variant + 100 = the same tile with the per-XCD band
  * order (each XCD keeps its A row band in L2 and walks the W panels once); variant + 200 / + 300 = a 2-D partition of the tiles over the XCDs (4 row bands x 2 column
  * halves / 2 row bands x 4 column quarters: an XCD streams half / a quarter of W instead of all of it -- the wide-N and long-K GEMMs are bound by the L2-miss traffic
@@ -168,7 +165,7 @@ int toc3d_linear_fused(int dtype, int epilogue, int variant, const void* A, int6
 /* Deterministic split-K for the residual epilogues (TOC3D_EPI_RESIDUAL, _RESIDUAL_LN, _RESIDUAL_STATS: attn.proj eva_vit.py:115,262 / toc3d_eva_vit.py:514,379 and
  * mlp.w3 eva_vit.py:49,263 / toc3d_eva_vit.py:384 -- N = C = 1024 outputs per row, i.e. 136-376 tiles of 128x128 for a 6-view frame on a 256-CU chip).
  *   variant = 1000 * split + tile variant: `split` (2 .. TOC3D_SPLITK_MAX) workgroups per output tile, each multiplying its own range of K (cuts at multiples of
- *   128 elements, the same for every tile variant); tile variants with a split-K form: 1, 9, 10, 14, 16, 17, 19, 22, 26, 28, 29, 55, 56 (bf16; f32 / bf16 x 3: not 29, 55, 56).
+ *   128 elements, the same for every tile variant); tile variants with a split-K form: 1, 9, 10, 14, 16, 17, 19, 22, 26, 28, 29, 55, 56 (bf16 and f32; bf16 x 3: not 29, 55, 56).
  *   The partial accumulators meet in `workspace`; the workgroup that arrives last at a tile's ticket adds them IN SLICE ORDER (its own from registers) and runs the
  *   epilogue -- no atomics on data, no workgroup waits for another: outputs are bit-reproducible from run to run and identical for every tile variant of one
  *   `split` (they differ from the unsplit variants in the last bits: another order of the K sum).

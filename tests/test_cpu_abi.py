@@ -351,6 +351,45 @@ def test_header_constants_match_the_python_binding():
     assert abs(lib.load().toc3d_attn_rot_q_scale(64) - lib.ATTN_ROT_Q_SCALE) < 1e-7 * lib.ATTN_ROT_Q_SCALE
 
 
+def test_python_tile_table_matches_the_cpp_tile_table():
+    """The GEMM tiles are one table on each side: TOC3D_GEMM_TILES in csrc/gemm_kernels.h (what the three dispatchers and the split-K workspace are generated
+    from) and lib.TILES (what PRODUCT_VARIANTS and the tuner's geometric exclusions are read from).  The C++ rows are parsed out of the source, as the header's
+    constants are above: same ids, shapes and family membership; what the C++ serves on planes only is inside X3_PLANES_ONLY_VARIANTS (which stays the wider,
+    literal policy: it also holds 59); every tuning candidate names a tile its dtype's family has; the split-K ids the error text spells are the table's."""
+    from toc3d_amd import gemm
+    csrc = os.path.join(os.path.dirname(os.path.abspath(toc3d_amd.__file__)), "csrc")
+    rows = [[f.strip() for f in m.group(1).split(",")] for m in re.finditer(r"\bROW\(\s*(\d+,[^)]*)\)", open(os.path.join(csrc, "gemm_kernels.h")).read())]
+    assert len(rows) == 37 and all(len(r) == 14 for r in rows)
+    cpp, planes_only = {}, set()
+    for ident, bm, bn, stages, rb, wm, wn, form, main, _, xf, _, skf, _ in rows:
+        bm, bn, rb, wm, wn = int(bm), int(bn), int(rb), int(wm), int(wn)
+        assert form in ("F_RING", "F_PHASED", "F_PIPE") and main in ("S_ALL", "S_BF16") and xf in ("S_NONE", "S_X3", "S_X36") and skf in ("S_NONE", "S_SK", "S_SK_NOX")
+        assert int(ident) not in cpp, f"tile {ident} has two rows"
+        cpp[int(ident)] = (bm, bn, wm, wn, (main[2:], xf[2:], skf[2:]))
+        partial_round = (bm * (rb // 16)) % (64 * wm * wn) != 0 or (bn * (rb // 16)) % (64 * wm * wn) != 0          # launch_cfg's rule: 96- / 160-row tiles
+        if xf != "S_NONE" and (partial_round or form == "F_PHASED"):
+            planes_only.add(int(ident))
+    assert cpp == lib.TILES
+    assert lib.PRODUCT_VARIANTS == tuple(sorted(cpp)) and all(0 < v < 100 for v in cpp)
+    assert planes_only == {54, 55, 56, 57, 58, 60, 61, 62, 63} and planes_only <= set(lib.X3_PLANES_ONLY_VARIANTS)
+    x3 = (lib.F32X3, lib.F32X3W, lib.F32X3P, lib.F32X3WO, lib.F32X3WA)
+    assert set(gemm._VARIANTS) == {lib.BF16, lib.F32, lib.F32X6, *x3}
+    for dt, cands in gemm._VARIANTS.items():
+        for v in cands:
+            assert lib.has_variant(v) and v < 400, (dt, v)
+            main, xf, _ = lib.TILES[v % 100][4]
+            # (F32X6 shares the bf16 x 3 tuple: the tiles only x3 has are refused by the library and drop out of the timing)
+            assert dt == lib.BF16 or (main == "ALL" if dt == lib.F32 else xf != "NONE"), (dt, v)
+            if v % 100 in planes_only:
+                assert dt in (lib.BF16, lib.F32X3P), (dt, v)
+    sk = sorted(v for v, t in lib.TILES.items() if t[4][2] != "NONE")
+    assert gemm.SPLITK_VARIANT % 1000 in sk
+    assert f"tile variants {', '.join(map(str, sk))})" in open(os.path.join(csrc, "gemm.hip")).read()
+    L = lib.load()
+    for v, (bm, bn, _, _, fam) in lib.TILES.items():
+        assert L.toc3d_linear_splitk_workspace_bytes(2000 + v, 1, 1) == (65536 + 2 * bm * bn * 4 if fam[2] != "NONE" else -1), v
+
+
 def test_backbone_survives_pickles_written_before_gumbel_seed_became_a_property():
     """a whole-module pickle from before the property carries `gumbel_seed` in __dict__ and no `_gumbel_seed`; reading the property then raised through
     nn.Module.__getattr__.  __setstate__ migrates the entry; the class carries defaults."""

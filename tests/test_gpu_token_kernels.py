@@ -32,8 +32,6 @@ Rebase (representative rows, in place), reference in f64 from the device's wgt /
 Selection weights: wgt = s / sum(s) with a same-sign f32 sum of N - k terms and one division: |dev - ref| <= ((N - k) + 2) u |ref|.
 
 toc3d_scatter_update only copies and adds f32 in a fixed order ((x + r1) + r2, then (. + r3) + r4): the reference is f32 torch on the CPU, bit for bit.
-
-Dead code, not tested: the PENDING instantiation of gather_merge_ln_kernel and token_inverse_map_kernel are never instantiated / launched.
 """
 import math
 

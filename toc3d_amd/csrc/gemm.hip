@@ -305,9 +305,8 @@ static int fused_args(GemmArgs& a, int dtype, int epilogue, const void* A, int64
     const int64_t osz = e_residual ? 4 : (dtype == TOC3D_BF16 ? 2 : 4);
     const bool vec = ldo % 4 == 0 && (uintptr_t)out % (4 * osz) == 0 && (!residual || (ldr % 4 == 0 && (uintptr_t)residual % 16 == 0)) &&
                      (!rep_out || (N % 4 == 0 && (uintptr_t)rep_out % 16 == 0));
-    // wide (16-byte) bf16 stores need 16-byte aligned rows in the output's own element size (TOC3D_WIDE_STORES=0 disables them: A/B runs)
-    static const bool wide_ok = [] { const char* e = getenv("TOC3D_WIDE_STORES"); return !(e && e[0] == '0'); }();
-    const bool vec8 = wide_ok && vec && dtype == TOC3D_BF16 && !e_residual && epilogue != TOC3D_EPI_CONV3X3 && ldo % 8 == 0 && (uintptr_t)out % 16 == 0;
+    // wide (16-byte) bf16 stores need 16-byte aligned rows in the output's own element size
+    const bool vec8 = vec && dtype == TOC3D_BF16 && !e_residual && epilogue != TOC3D_EPI_CONV3X3 && ldo % 8 == 0 && (uintptr_t)out % 16 == 0;
     a = GemmArgs{A, lda, W, ldw, bias, out, ldo, residual, ldr, (int)residual_row_mod, residual_index, rep_out, rep_index,
                (int)M, (int)N, (int)K, (int)n_valid, 0, vec ? 1 : 0, vec8 ? 1 : 0,
                stats_out, (int)stats_out_cap, stats_in, (int)(stats_in_cap & 0xffffffff), (int)(stats_in_cap >> 32), col_sums, ln_n > 0 ? (float)(1.0 / (double)ln_n) : 0.f, ln_eps, out_act, ld_act,
@@ -418,8 +417,7 @@ int toc3d_linear_qkv_rope(int dtype, int variant, const void* A, int64_t lda, co
     if (x3) TOC3D_REQUIRE(ldo % 32 == 0 && ((uintptr_t)out % 128) == 0 && (dtype != TOC3D_F32X3P || lda % 32 == 0), "toc3d_linear_qkv_rope: rows of (hi, lo) planes are whole 32-element groups on 128-byte boundaries");
     if (M == 0) return TOC3D_OK;
     const bool vec = ldo % 4 == 0 && (uintptr_t)out % (4 * esz) == 0;
-    static const bool wide_ok = [] { const char* e = getenv("TOC3D_WIDE_STORES"); return !(e && e[0] == '0'); }();
-    const bool vec8 = !x3 && wide_ok && vec && ldo % 8 == 0 && (uintptr_t)out % 16 == 0;
+    const bool vec8 = !x3 && vec && ldo % 8 == 0 && (uintptr_t)out % 16 == 0;
     GemmArgs a{A, lda, W, ldw, bias, out, ldo, nullptr, 0, 0, nullptr, nullptr, nullptr, (int)M, (int)N, (int)K, 0, 0, vec ? 1 : 0, vec8 ? 1 : 0,
                nullptr, 0, nullptr, 0, 0, nullptr, 0.f, 0.f, nullptr, 0, 0, 0, nullptr, rope_rc, rope_tab, (int)rope_side, q_scale,
                dtype == TOC3D_F32X3P ? 1 : 0, x3 ? 1 : 0, x3 ? 1 : 0};

@@ -94,9 +94,6 @@ __device__ unsigned long long* toc3d_trace_buf;       // [grid][4]
 namespace {
 
 // RB = bytes of K per LDS row per stage: 128 (64 bf16 / 32 f32 per K-tile) or 64 (32 bf16, bf16 only)
-
-
-
 constexpr bool epi_is_swiglu(int epi) { return epi == TOC3D_EPI_SWIGLU || epi == TOC3D_EPI_SWIGLU_STATS || epi == TOC3D_EPI_SWIGLU_STATS_LN; }
 constexpr bool epi_is_residual(int epi) { return epi == TOC3D_EPI_RESIDUAL || epi == TOC3D_EPI_RESIDUAL_LN || epi == TOC3D_EPI_RESIDUAL_STATS || epi == TOC3D_EPI_CONV3X3; }
 constexpr bool epi_ln_stats_in(int epi) { return epi == TOC3D_EPI_RESIDUAL_LN || epi == TOC3D_EPI_SWIGLU_STATS_LN; }      // LayerNorm of the A rows folded into the epilogue, its statistics left by the producing GEMM
@@ -117,7 +114,7 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 template <int RB> TOC3D_DEV int swz(int r) { return RB >= 256 ? (r & 15) : (RB == 128 ? (r & 7) : ((4 - ((r >> 2) & 3)) & 3)); }
 
 // stage one R-row x RB-byte operand tile with 16-byte global_load_lds: R*RB/16 chunks over 256 threads.
-template <typename T, int R, int RB, int NTHR, int AUX = 0>
+template <typename T, int R, int RB, int NTHR>
 TOC3D_DEV void stage_tile(const T* __restrict__ g, int64_t ld, int row0, int max_row, int k0, char* lds_tile, int wave, int lane) {
     constexpr int CPR = RB / 16;                        // chunks per row
     // Tiles whose chunk count is not a multiple of the workgroup size (96- / 160-row tiles on 512 threads): the wavefronts past the end of the last round
@@ -134,7 +131,7 @@ TOC3D_DEV void stage_tile(const T* __restrict__ g, int64_t ld, int row0, int max
         int gr = row0 + r;
         gr = gr < max_row ? gr : max_row;
         const char* src = reinterpret_cast<const char*>(g + (int64_t)gr * ld + k0) + ((p ^ swz<RB>(r)) << 4);
-        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(lds_tile + base * 16), 16, 0, AUX);
+        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(lds_tile + base * 16), 16, 0, 0);
     }
 }
 
@@ -184,42 +181,6 @@ TOC3D_DEV void lds_barrier() {
     tile_barrier();
 }
 
-// Epilogue stores.  TOC3D_WT_STORES (experiment, profiles/r02_write_through_stores.txt): write-through (sc1) stores, so the output does not sit
-// dirty in the XCD's L2 until the end-of-kernel release writes it back in one burst.
-#ifdef TOC3D_WT_STORES
-TOC3D_DEV void epi_store4(bf16_t* p, const bf16_t (&v)[4]) {
-    typedef bf16_t bf16x4_t __attribute__((ext_vector_type(4)));
-    const bf16x4_t x = bf16x4_t{v[0], v[1], v[2], v[3]};
-    __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), __builtin_bit_cast(unsigned long long, x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-TOC3D_DEV void epi_store4(float* p, const float (&v)[4]) {
-#if TOC3D_WT_STORES >= 2
-    const f32x2 lo = f32x2{v[0], v[1]}, hi = f32x2{v[2], v[3]};
-    __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), __builtin_bit_cast(unsigned long long, lo), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(reinterpret_cast<unsigned long long*>(p) + 1, __builtin_bit_cast(unsigned long long, hi), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-    store4(p, v);
-#endif
-}
-#elif defined(TOC3D_NT_STORES)
-// experiment (round 5, profiles/r05_nt_stores.txt): non-temporal epilogue stores (1: act-dtype outputs, 2: f32 outputs too)
-TOC3D_DEV void epi_store4(bf16_t* p, const bf16_t (&v)[4]) {
-    typedef bf16_t bf16x4_t __attribute__((ext_vector_type(4)));
-    const bf16x4_t x = bf16x4_t{v[0], v[1], v[2], v[3]};
-    __builtin_nontemporal_store(__builtin_bit_cast(unsigned long long, x), reinterpret_cast<unsigned long long*>(p));
-}
-TOC3D_DEV void epi_store4(float* p, const float (&v)[4]) {
-#if TOC3D_NT_STORES >= 2
-    __builtin_nontemporal_store(f32x4{v[0], v[1], v[2], v[3]}, reinterpret_cast<f32x4*>(p));
-#else
-    store4(p, v);
-#endif
-}
-#else
-TOC3D_DEV void epi_store4(bf16_t* p, const bf16_t (&v)[4]) { store4(p, v); }
-TOC3D_DEV void epi_store4(float* p, const float (&v)[4]) { store4(p, v); }
-#endif
-
 // Wide bf16 epilogue stores (cdna_hip_programming.md T21, re-derived for the 16x16 C^T layout).  The epilogues of the single-round launches
 // are store-ISSUE bound (all workgroups store at once; ~7 B/clk/CU whatever the byte count, profiles/r03_gemm_timeline_*.txt), and a bf16
 // tile leaves as 8 bytes per lane.  Two row tiles i, i + 1 of the same columns are therefore merged into ONE 16-byte store per lane:
@@ -242,11 +203,7 @@ TOC3D_DEV void store_pair_wide(bf16_t* dst_a, bf16_t* dst_b, Pack4 pa, Pack4 pb,
     const auto ry = __builtin_amdgcn_permlane16_swap(pa.y, pb.y, false, false);
     // even group: row tile i, columns start at its own; odd group: row tile i + 1, columns start 4 to the left (the left neighbour's)
     bf16_t* dst = (g & 1) ? dst_b - 4 : dst_a;
-#ifdef TOC3D_NT_STORES
-    if ((g & 1) ? ok_b : ok_a) __builtin_nontemporal_store(u32x4{rx[0], ry[0], rx[1], ry[1]}, reinterpret_cast<u32x4*>(dst));
-#else
     if ((g & 1) ? ok_b : ok_a) *reinterpret_cast<u32x4*>(dst) = u32x4{rx[0], ry[0], rx[1], ry[1]};
-#endif
 }
 TOC3D_DEV void store_pair_wide(float*, float*, Pack4, Pack4, bool, bool, int) {}
 
@@ -356,8 +313,8 @@ TOC3D_DEV void gemm_epilogue(const GemmArgs& a, f32x4 (&acc)[MT][NT], int row0, 
                             // a lane's own in-flag stands for its neighbour's too: both share the row, and the columns are all inside
                             store_pair_wide(da, da + 16 * a.ldo, pack4(ha), pack4(hb), ia, ib, g);
                         } else {
-                            if (ia) epi_store4(da, ha);
-                            if (ib) epi_store4(da + 16 * a.ldo, hb);
+                            if (ia) store4(da, ha);
+                            if (ib) store4(da + 16 * a.ldo, hb);
                         }
                     }
                 return;
@@ -400,7 +357,7 @@ TOC3D_DEV void gemm_epilogue(const GemmArgs& a, f32x4 (&acc)[MT][NT], int row0, 
                         if (a.out_planes) { store_planes4(reinterpret_cast<float*>(dst - unit0), unit0, hs); planes = true; }
                     }
                     if (planes) {}
-                    else if (a.vec) epi_store4(dst, hs);
+                    else if (a.vec) store4(dst, hs);
                     else { dst[0] = hs[0]; dst[1] = hs[1]; dst[2] = hs[2]; dst[3] = hs[3]; }
                 }
                 if (epi_stats_out(EPI)) { gs[i * G + jp] = ssum; gq[i * G + jp] = sq; }
@@ -472,7 +429,7 @@ TOC3D_DEV void gemm_epilogue(const GemmArgs& a, f32x4 (&acc)[MT][NT], int row0, 
                 // bf16 x 3 on planes: the rotated q | k | v rows leave as (hi, lo) planes -- what toc3d_window_attention_rot stages by DMA (N = 3C, C % 64 == 0: whole groups of 4)
                 if (a.out_planes) { store_planes4(reinterpret_cast<float*>(orow), col, o4); continue; }
             }
-            if (a.vec && nok[j] == 4) epi_store4(orow + col, o4);
+            if (a.vec && nok[j] == 4) store4(orow + col, o4);
             else for (int r = 0; r < nok[j]; ++r) orow[col + r] = o4[r];
         }
     };
@@ -572,7 +529,7 @@ TOC3D_DEV void gemm_epilogue(const GemmArgs& a, f32x4 (&acc)[MT][NT], int row0, 
                     f32x4 rv = resrow ? *reinterpret_cast<const f32x4*>(resrow + col) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                     for (int r = 0; r < 4; ++r) sum4[r] = rv[r] + raw[r];
-                    epi_store4(orow + col, sum4);
+                    store4(orow + col, sum4);
                     if (reprow) *reinterpret_cast<f32x4*>(reprow + col) = f32x4{raw[0], raw[1], raw[2], raw[3]};
                 } else {
                     for (int r = 0; r < nok[j]; ++r) {
@@ -617,7 +574,7 @@ TOC3D_DEV void gemm_epilogue(const GemmArgs& a, f32x4 (&acc)[MT][NT], int row0, 
                         }
                     }
                     if (planes) {}
-                    else if (nok[j] == 4) epi_store4(arow, o4);
+                    else if (nok[j] == 4) store4(arow, o4);
                     else for (int r = 0; r < nok[j]; ++r) arow[r] = o4[r];
                     if (EPI == TOC3D_EPI_RESIDUAL_STATS) {
                         gs[i * G + j] = ssum;
@@ -919,10 +876,7 @@ TOC3D_DEV void gemm_tile(const GemmArgs& a, const int m0, const int n0, char* sm
         } else {
             stage_tile<T, BM, RB, NTHR>(A, a.lda, m0, a.M - 1, k_base + t * BK, slot, wave, lane);
         }
-#ifndef TOC3D_W_AUX
-#define TOC3D_W_AUX 0                                   // experiment (round 5, profiles/r05_nt_stores.txt): cache policy bits of the W operand's DMA loads (2 = nt: stream past the L2's LRU)
-#endif
-        stage_tile<T, BN, RB, NTHR, TOC3D_W_AUX>(W, a.ldw, n0, w_max, k_base + t * BK, slot + A_BYTES, wave, lane);
+        stage_tile<T, BN, RB, NTHR>(W, a.ldw, n0, w_max, k_base + t * BK, slot + A_BYTES, wave, lane);
     };
     auto multiply = [&](int t) {
         const char* sA = smem + (t % STAGES) * STAGE_BYTES;
@@ -1091,7 +1045,6 @@ TOC3D_DEV void gemm_tile(const GemmArgs& a, const int m0, const int n0, char* sm
         };
         using F0 = std::integral_constant<int, 0>;
         using F1 = std::integral_constant<int, 1>;
-        using F2 = std::integral_constant<int, 2>;
         using S0 = std::integral_constant<int, 0>;
         using S1 = std::integral_constant<int, 1>;
 #pragma unroll
@@ -1465,38 +1418,6 @@ void launch_cfg_sk(const GemmArgs& a, hipStream_t s) {
     const int tm = (a.M + BM - 1) / BM, tn = (a.N + BN - 1) / BN;
     toc3d_launch((gemm_kernel<T, EPI, BM, BN, STAGES, RB, WM, WN, OCC, X3, 1>), dim3(tm * tn * a.split), dim3(64 * WM * WN), lds, s, a);
 }
-// tile variants that have a split-K form (variant mod 1000 of toc3d_linear_fused_ws; variant / 1000 = the split): BM * BN, or 0
-// (BM << 16 | BN, the shape launch_epi_sk below instantiates -- the host sizes the workspace from the SAME table: variants 9 (128x64) and 10 / 26 (64x128) have equal
-// element counts and different tile grids)
-constexpr int sk_tile_dims(int v) {
-    return (v == 16 || v == 17 || v == 28 || v == 29 || v == 1 || v == 22) ? (128 << 16 | 128) : (v == 55 || v == 56) ? (96 << 16 | 128) : v == 19 ? (256 << 16 | 128)
-           : (v == 10 || v == 26) ? (64 << 16 | 128) : v == 9 ? (128 << 16 | 64) : v == 14 ? (64 << 16 | 64) : 0;
-}
-constexpr int64_t sk_tile_elems(int v) { return (int64_t)(sk_tile_dims(v) >> 16) * (sk_tile_dims(v) & 0xffff); }
-template <typename T, int EPI, int X3 = 0>
-int launch_epi_sk(int variant, const GemmArgs& a, hipStream_t s) {
-    constexpr bool B = sizeof(T) == 2;
-    static_assert(sk_tile_dims(9) == (128 << 16 | 64) && sk_tile_dims(10) == (64 << 16 | 128) && sk_tile_dims(26) == (64 << 16 | 128) && sk_tile_dims(19) == (256 << 16 | 128) &&
-                  sk_tile_dims(55) == (96 << 16 | 128) && sk_tile_dims(14) == (64 << 16 | 64) && sk_tile_dims(22) == (128 << 16 | 128), "sk_tile_dims must name the tiles instantiated below");
-    switch (variant) {
-        case 1: launch_cfg_sk<T, EPI, 128, 128, 2, 128, 2, 2, 1, X3>(a, s); break;
-        case 9: launch_cfg_sk<T, EPI, 128, 64, 2, 128, 2, 2, 1, X3>(a, s); break;
-        case 10: launch_cfg_sk<T, EPI, 64, 128, 2, 128, 2, 2, 1, X3>(a, s); break;
-        case 14: launch_cfg_sk<T, EPI, 64, 64, 2, 128, 2, 2, 1, X3>(a, s); break;
-        case 16: launch_cfg_sk<T, EPI, 128, 128, 1, 128, 2, 4, (B ? 6 : 1), X3>(a, s); break;
-        case 17: launch_cfg_sk<T, EPI, 128, 128, 2, 128, 2, 4, 1, X3>(a, s); break;
-        case 19: launch_cfg_sk<T, EPI, 256, 128, 1, 128, 4, 2, 1, X3>(a, s); break;
-        case 22: launch_cfg_sk<T, EPI, 128, 128, 1, 256, 2, 4, 1, X3>(a, s); break;
-        case 26: launch_cfg_sk<T, EPI, 64, 128, 1, 256, 2, 4, 1, X3>(a, s); break;
-        case 28: launch_cfg_sk<T, EPI, 128, 128, 3, 128, 2, 4, 1, X3>(a, s); break;
-        case 29: if constexpr (X3 == 0) launch_cfg_sk<T, EPI, 128, 128, 4, 128, 2, 4, 1, X3>(a, s); else return TOC3D_ERR_ARG; break;
-        case 55: if constexpr (X3 == 0) launch_cfg_sk<T, EPI, 96, 128, 2, 128, 2, 4, 1, X3>(a, s); else return TOC3D_ERR_ARG; break;
-        case 56: if constexpr (X3 == 0) launch_cfg_sk<T, EPI, 96, 128, 4, 128, 2, 4, 1, X3>(a, s); else return TOC3D_ERR_ARG; break;
-        default: return TOC3D_ERR_ARG;
-    }
-    return TOC3D_OK;
-}
-
 template <int EPI, int BM, int BN, int WM, int WN, bool X3 = false>
 void launch_phased(const GemmArgs& a, hipStream_t s) {
     // round 5: every linear epilogue (the folded LayerNorms' statistics in and out, the rotating q|k|v epilogue); not the conv gather (its own operand loader)
@@ -1515,122 +1436,145 @@ void launch_phased(const GemmArgs& a, hipStream_t s) {
     }
 }
 
-// tile / pipeline variants (toc3d_linear_ex `variant`); 0 = heuristic
-template <typename T, int EPI>
-int launch_epi(int variant, GemmArgs a, hipStream_t s) {
-    if (variant >= 300) { a.order = 3; variant -= 300; }      // variant + 300: 2 row bands x 4 column quarters per XCD
-    else if (variant >= 200) { a.order = 2; variant -= 200; } // variant + 200: 4 row bands x 2 column halves
-    else if (variant >= 100) { a.order = 1; variant -= 100; } // variant + 100: same tile shape, per-XCD band order
+// ---- The tile table: one row per tile id (`variant` mod 100 of toc3d_linear_ex; mod 1000 of toc3d_linear_fused_ws).  Everything that has to know what a
+// tile IS reads it from here: the three dispatchers below, sk_tile_dims (the split-K workspace), and -- by parsing this text -- tests/test_cpu_abi.py, which
+// holds toc3d_amd/lib.py TILES to it.  A NEW TILE IS ONE NEW ROW HERE (and one in lib.py TILES).
+//   BM x BN tile, STAGES-deep LDS ring of RB-byte K rows (256 / 512 fall back to 128 when K is not whole K-tiles), WM x WN wavefronts
+//   form     F_RING = gemm_kernel; F_PHASED = gemm_phased_kernel (512 threads, its own two 128-byte K-tiles: STAGES / RB are not template arguments there);
+//            F_PIPE = gemm_kernel with the register-pipelined K loop (X3 = 1; bf16, not the conv gather)
+//   then, per family, who is served and the OCC template argument (registers held to 512 / OCC per lane; B = the element type is bf16, ROPE = EPI_QKV_ROPE):
+//   bf16|f32 (launch_epi)     S_ALL | S_BF16 (bf16 only)
+//   x3|x6    (launch_epi_x)   S_NONE | S_X3 (bf16 x 3 only) | S_X36.  A 96- / 160-row tile (launch_cfg, partial_round) or a phased one is served on planes only
+//   split-K  (launch_epi_sk)  S_NONE | S_SK (bf16, f32, bf16 x 3) | S_SK_NOX (bf16 and f32)
+enum { F_RING, F_PHASED, F_PIPE };
+enum { S_NONE, S_ALL, S_BF16, S_X3, S_X36, S_SK, S_SK_NOX };
+#define TOC3D_GEMM_TILES(ROW)                                                                                                                            \
+    /*  id   BM   BN  ST   RB WM WN  form      bf16|f32  OCC         x3|x6   OCC           split-K    OCC */                                          \
+    ROW( 1, 128, 128, 2, 128, 2, 2, F_RING,   S_ALL,  1,          S_X36,  1,            S_SK,     1)          /* 4 waves, 64x64 per wave */           \
+    ROW( 8, 128, 128, 1, 128, 2, 2, F_RING,   S_ALL,  1,          S_X36,  1,            S_NONE,   1)          /* single LDS buffer */                 \
+    ROW( 9, 128,  64, 2, 128, 2, 2, F_RING,   S_ALL,  1,          S_X36,  1,            S_SK,     1)                                                  \
+    ROW(10,  64, 128, 2, 128, 2, 2, F_RING,   S_ALL,  1,          S_X36,  1,            S_SK,     1)                                                  \
+    ROW(13, 128,  64, 1, 128, 2, 2, F_RING,   S_ALL,  1,          S_NONE, 1,            S_NONE,   1)                                                  \
+    ROW(14,  64,  64, 2, 128, 2, 2, F_RING,   S_ALL,  1,          S_X36,  1,            S_SK,     1)                                                  \
+    ROW(15, 128, 128, 1, 128, 2, 2, F_RING,   S_ALL,  4,          S_NONE, 1,            S_NONE,   1)          /* 8 held to 128 registers: 4 workgroups / CU */ \
+    /* 8 waves, 64x32 per wave; bf16 held to 80 registers (6 waves / SIMD = 3 workgroups / CU; the SwiGLU epilogue would take 82) */                   \
+    ROW(16, 128, 128, 1, 128, 2, 4, F_RING,   S_ALL,  B ? 6 : 1,  S_X36,  1,            S_SK,     B ? 6 : 1)                                          \
+    ROW(17, 128, 128, 2, 128, 2, 4, F_RING,   S_ALL,  1,          S_X36,  1,            S_SK,     1)          /* 8 waves, double buffered (64 KiB) */ \
+    /* (the rotating q|k|v epilogue of the bf16 x 3 form is held to 128 registers on the 8-wave tiles that share a CU between two workgroups: unconstrained, 49 took 148 -- */ \
+    /* ONE workgroup per CU, 137 instead of ~75 us for q|k|v at M = 6000) */                                                                           \
+    ROW(19, 256, 128, 1, 128, 4, 2, F_RING,   S_ALL,  1,          S_X36,  ROPE ? 4 : 1, S_SK,     1)          /* 8 waves, single buffer (48 KiB) */   \
+    /* big K-tiles for latency-bound launches (about one tile per CU): fewer, fatter load rounds */                                                    \
+    ROW(22, 128, 128, 1, 256, 2, 4, F_RING,   S_ALL,  1,          S_X36,  ROPE ? 4 : 1, S_SK,     1)          /* K-tile 128 bf16 / 64 f32, 64 KiB */  \
+    ROW(24,  64, 128, 1, 512, 2, 4, F_RING,   S_ALL,  1,          S_NONE, 1,            S_NONE,   1)          /* K-tile 256, 96 KiB */                \
+    ROW(26,  64, 128, 1, 256, 2, 4, F_RING,   S_ALL,  1,          S_X36,  1,            S_SK,     1)          /* K-tile 128, 48 KiB */                \
+    ROW(27,  64,  64, 1, 512, 2, 2, F_RING,   S_ALL,  1,          S_NONE, 1,            S_NONE,   1)          /* 4 waves, K-tile 256, 64 KiB */       \
+    /* deep LDS rings on 8 wavefronts: more bytes continuously in flight per CU (counted vmcnt, one barrier per K-tile) */                             \
+    ROW(28, 128, 128, 3, 128, 2, 4, F_RING,   S_ALL,  1,          S_X36,  1,            S_SK,     1)          /* 96 KiB */                            \
+    ROW(29, 128, 128, 4, 128, 2, 4, F_RING,   S_ALL,  1,          S_X3,   1,            S_SK_NOX, 1)          /* 128 KiB */                           \
+    ROW(30, 128, 128, 4,  64, 2, 4, F_RING,   S_BF16, 1,          S_NONE, 1,            S_NONE,   1)          /* K-tile 32, 64 KiB */                 \
+    ROW(33, 128,  64, 4, 128, 2, 4, F_RING,   S_ALL,  1,          S_X3,   1,            S_NONE,   1)          /* 96 KiB */                            \
+    /* N-tiles that are not powers of two (the vendor library's answer to tile-count quantisation on N = 3072 / 1024) */                               \
+    ROW(45, 128, 192, 2, 128, 2, 4, F_RING,   S_ALL,  1,          S_X3,   ROPE ? 4 : 1, S_NONE,   1)          /* 80 KiB */                            \
+    ROW(47, 128, 192, 2, 128, 4, 2, F_RING,   S_ALL,  1,          S_X3,   ROPE ? 4 : 1, S_NONE,   1)          /* 32x96 per wave (serves SwiGLU) */    \
+    ROW(49, 192, 128, 2, 128, 2, 4, F_RING,   S_ALL,  1,          S_X36,  ROPE ? 4 : 1, S_NONE,   1)          /* 96x32 per wave (serves SwiGLU), 80 KiB */ \
+    ROW(51, 128, 128, 1, 128, 2, 4, F_RING,   S_ALL,  B ? 8 : 1,  S_NONE, 1,            S_NONE,   1)          /* 16 held to 64 registers (bf16): FOUR workgroups per CU */ \
+    /* (bf16: the rotating q|k|v epilogue is held to 128 registers -- two workgroups per CU like the other epilogues: unconstrained it took 138, ONE workgroup per CU, 83 instead of 51 us at M = 6000) */ \
+    ROW(52, 192, 192, 1, 128, 2, 4, F_RING,   S_ALL,  ROPE ? 4 : 1, S_X3,  ROPE ? 4 : 1, S_NONE,   1)          /* 96x48 per wave, 48 KiB: 512 tiles for q|k|v at M = 6000 */ \
+    ROW(53, 192, 192, 2, 128, 2, 4, F_RING,   S_ALL,  ROPE ? 4 : 1, S_X3,  1,            S_NONE,   1)          /* 96 KiB */                            \
+    /* M-tiles of 96 / 160 rows: the frame's launches run 1.2-2.6 rounds of 128-row tiles on the chip's 512-768 workgroup slots and pay for a whole last round; */ \
+    /* a 96- or 160-row tile changes the tile count by 4/3 or 4/5 at the same N-tile (whole statistics slots, whole (w1, w2) groups) */                \
+    ROW(54,  96, 128, 1, 128, 2, 4, F_RING,   S_ALL,  B ? 6 : 1,  S_X3,   1,            S_NONE,   1)          /* 48x32 per wave, 28 KiB */            \
+    ROW(55,  96, 128, 2, 128, 2, 4, F_RING,   S_ALL,  1,          S_X3,   1,            S_SK_NOX, 1)          /* 56 KiB */                            \
+    ROW(56,  96, 128, 4, 128, 2, 4, F_RING,   S_ALL,  1,          S_X3,   1,            S_SK_NOX, 1)          /* 112 KiB */                           \
+    ROW(57, 160, 128, 1, 128, 2, 4, F_RING,   S_ALL,  1,          S_X3,   1,            S_NONE,   1)          /* 80x32 per wave, 36 KiB */            \
+    ROW(58, 160, 128, 2, 128, 2, 4, F_RING,   S_ALL,  1,          S_X3,   1,            S_NONE,   1)          /* 72 KiB */                            \
+    ROW(59, 192, 128, 3, 128, 2, 4, F_RING,   S_ALL,  1,          S_X3,   1,            S_NONE,   1)          /* 120 KiB: 32 x 8 = 256 tiles for N = 1024 at M = 6000 */ \
+    /* phased big tiles: one workgroup per CU, four phases per K-tile, the two wave groups one barrier apart */                                        \
+    ROW(60, 256, 256, 2, 128, 2, 4, F_PHASED, S_BF16, 1,          S_X3,   1,            S_NONE,   1)          /* 128x64 per wave, 128 KiB */          \
+    ROW(61, 256, 128, 2, 128, 4, 2, F_PHASED, S_BF16, 1,          S_X3,   1,            S_NONE,   1)          /* 64x64 per wave, 96 KiB */            \
+    ROW(62, 128, 256, 2, 128, 2, 4, F_PHASED, S_BF16, 1,          S_X3,   1,            S_NONE,   1)          /* 64x64 per wave, 96 KiB */            \
+    ROW(63, 128, 128, 2, 128, 2, 4, F_PHASED, S_BF16, 1,          S_X3,   1,            S_NONE,   1)          /* 64x32 per wave, 64 KiB: two per CU */ \
+    /* register-pipelined rings: the next K step's fragments are read while the current one's MFMAs run -- for one workgroup per CU */                 \
+    ROW(64, 128, 128, 4, 128, 2, 4, F_PIPE,   S_BF16, 1,          S_NONE, 1,            S_NONE,   1)          /* 29's tile and ring, 128 KiB */       \
+    ROW(65, 128, 128, 3, 128, 2, 4, F_PIPE,   S_BF16, 1,          S_NONE, 1,            S_NONE,   1)          /* 28's, 96 KiB */                      \
+    ROW(66, 128, 128, 4, 128, 2, 2, F_PIPE,   S_BF16, 1,          S_NONE, 1,            S_NONE,   1)          /* 4 waves, 64x64 per wave, 128 KiB */
+
+// BM << 16 | BN of a tile id's split-K form, 0 if it has none (the host sizes the workspace from it: 9 (128x64) and 10 / 26 (64x128) have equal element
+// counts and different tile grids)
+constexpr int sk_tile_dims(int v) {
+#define ROW(ID, BM, BN, ST, RB, WM, WN, FORM, MAIN, OCC, XF, XOCC, SKF, SKOCC) \
+    if (v == ID && SKF != S_NONE) return BM << 16 | BN;
+    TOC3D_GEMM_TILES(ROW)
+#undef ROW
+    return 0;
+}
+
+// variant + 100 / + 200 / + 300 = the same tile in another XCD order (8 row bands; 4 row bands x 2 column halves; 2 row bands x 4 column quarters), 0 = heuristic
+inline int decode_variant(int variant, GemmArgs& a) {
+    if (variant >= 100 && variant < 400) { a.order = variant / 100; variant %= 100; }
     if (variant == 0) {
         // measured on MI355X (tools/gemm_sweep.py): occupancy beats ring depth on these shapes -- single-buffer tiles
         // (24-32 KiB LDS, >= 3 workgroups per CU); the narrower tile when there are few 128x128 tiles
         const int t128 = ((a.M + 127) / 128) * ((a.N + 127) / 128);
         variant = t128 < 700 ? 17 : 16;
     }
-    switch (variant) {
-        case 1: launch_cfg<T, EPI, 128, 128, 2>(a, s); break;
-        case 8: launch_cfg<T, EPI, 128, 128, 1>(a, s); break;
-        case 9: launch_cfg<T, EPI, 128, 64, 2>(a, s); break;
-        case 10: launch_cfg<T, EPI, 64, 128, 2>(a, s); break;
-        case 13: launch_cfg<T, EPI, 128, 64, 1>(a, s); break;
-        case 14: launch_cfg<T, EPI, 64, 64, 2>(a, s); break;
-        case 15: launch_cfg<T, EPI, 128, 128, 1, 128, 2, 2, 4>(a, s); break;      // v8 forced to <= 128 registers: 4 workgroups / CU
-        case 16: launch_cfg<T, EPI, 128, 128, 1, 128, 2, 4, (sizeof(T) == 2 ? 6 : 1)>(a, s); break;   // 8 waves, 64x32 per wave; bf16 held to 80 registers (6 waves / SIMD = 3 workgroups / CU; the SwiGLU epilogue would take 82)
-        case 17: launch_cfg<T, EPI, 128, 128, 2, 128, 2, 4, 1>(a, s); break;      // 8 waves, double buffered (64 KiB)
-        case 19: launch_cfg<T, EPI, 256, 128, 1, 128, 4, 2, 1>(a, s); break;      // 8 waves, 256x128, single buffer (48 KiB)
-        // big K-tiles for latency-bound launches (about one tile per CU): fewer, fatter load rounds
-        case 22: launch_cfg<T, EPI, 128, 128, 1, 256, 2, 4, 1>(a, s); break;      // K-tile 128 bf16, 64 KiB
-        case 24: launch_cfg<T, EPI, 64, 128, 1, 512, 2, 4, 1>(a, s); break;       // 64x128 tile, K-tile 256, 96 KiB
-        case 26: launch_cfg<T, EPI, 64, 128, 1, 256, 2, 4, 1>(a, s); break;       // 64x128 tile, K-tile 128, 48 KiB
-        case 27: launch_cfg<T, EPI, 64, 64, 1, 512, 2, 2, 1>(a, s); break;        // 64x64 tile, 4 waves, K-tile 256, 64 KiB
-        // deep LDS rings on 8 wavefronts: more bytes continuously in flight per CU (counted vmcnt, one barrier per K-tile)
-        case 28: launch_cfg<T, EPI, 128, 128, 3, 128, 2, 4, 1>(a, s); break;      // 96 KiB
-        case 29: launch_cfg<T, EPI, 128, 128, 4, 128, 2, 4, 1>(a, s); break;      // 128 KiB
-        case 30: if (sizeof(T) == 2) launch_cfg<bf16_t, EPI, 128, 128, 4, 64, 2, 4, 1>(a, s); else return TOC3D_ERR_ARG; break;   // K-tile 32, 64 KiB
-        case 33: launch_cfg<T, EPI, 128, 64, 4, 128, 2, 4, 1>(a, s); break;       // 128x64, 4-deep, 96 KiB
-        // 16 wavefronts per workgroup: 256-wide tiles (fewer L2->LDS bytes per FLOP) without giving up waves per CU
-        // K-tile 32 rings on 8 wavefronts at the LDS footprint of the single-buffer tile: prefetch inside the workgroup without losing occupancy
-        // N-tiles that are not powers of two (the vendor library's answer to tile-count quantisation on N = 3072 / 1024)
-        case 45: launch_cfg<T, EPI, 128, 192, 2, 128, 2, 4, 1>(a, s); break;      // 128x192 double buffered, 80 KiB
-        case 47: launch_cfg<T, EPI, 128, 192, 2, 128, 4, 2, 1>(a, s); break;      // 128x192 double buffered, 32x96 per wave (serves SwiGLU)
-        case 49: launch_cfg<T, EPI, 192, 128, 2, 128, 2, 4, 1>(a, s); break;      // 192x128 double buffered, 96x32 per wave (serves SwiGLU), 80 KiB
-        // (the rotating q|k|v epilogue is held to 128 registers -- two workgroups per CU like the other epilogues: unconstrained it took 138, ONE workgroup per CU and 83 instead of 51 us at M = 6000)
-        case 52: launch_cfg<T, EPI, 192, 192, 1, 128, 2, 4, (epi_is_rope(EPI) ? 4 : 1)>(a, s); break;      // 192x192 single buffer, 96x48 per wave, 48 KiB: 512 tiles for q|k|v at M = 6000 (one per slot at two per CU)
-        case 53: launch_cfg<T, EPI, 192, 192, 2, 128, 2, 4, (epi_is_rope(EPI) ? 4 : 1)>(a, s); break;      // 192x192 double buffered, 96 KiB
-        // M-tiles of 96 / 160 rows (round 4): the frame's launches run 1.2-2.6 rounds of 128-row tiles on the chip's 512-768 workgroup slots and pay for a whole
-        // last round; a 96- or 160-row tile changes the tile count by 4/3 or 4/5 at the same N-tile (whole statistics slots, whole (w1, w2) groups)
-        case 54: launch_cfg<T, EPI, 96, 128, 1, 128, 2, 4, (sizeof(T) == 2 ? 6 : 1)>(a, s); break;    // 96x128 single buffer, 48x32 per wave, 28 KiB
-        case 55: launch_cfg<T, EPI, 96, 128, 2, 128, 2, 4, 1>(a, s); break;                           // 96x128 double buffered, 56 KiB
-        case 56: launch_cfg<T, EPI, 96, 128, 4, 128, 2, 4, 1>(a, s); break;                           // 96x128 4-deep ring, 112 KiB
-        case 57: launch_cfg<T, EPI, 160, 128, 1, 128, 2, 4, 1>(a, s); break;                          // 160x128 single buffer, 80x32 per wave, 36 KiB
-        case 58: launch_cfg<T, EPI, 160, 128, 2, 128, 2, 4, 1>(a, s); break;                          // 160x128 double buffered, 72 KiB
-        case 59: launch_cfg<T, EPI, 192, 128, 3, 128, 2, 4, 1>(a, s); break;                          // 192x128 3-deep ring, 120 KiB: 32 x 8 = 256 tiles for N = 1024 at M = 6000
-        case 51: launch_cfg<T, EPI, 128, 128, 1, 128, 2, 4, (sizeof(T) == 2 ? 8 : 1)>(a, s); break;   // variant 16 held to 64 registers (bf16): FOUR workgroups per CU -- the loop is bound by operand bytes in flight per CU
-        // phased big tiles (bf16 only): one workgroup per CU, four phases per K-tile, the two wave groups one barrier apart
-        case 60: if (sizeof(T) == 2) launch_phased<EPI, 256, 256, 2, 4>(a, s); else return TOC3D_ERR_ARG; break;   // 128x64 per wave, 128 KiB
-        case 61: if (sizeof(T) == 2) launch_phased<EPI, 256, 128, 4, 2>(a, s); else return TOC3D_ERR_ARG; break;   // 64x64 per wave, 96 KiB
-        case 62: if (sizeof(T) == 2) launch_phased<EPI, 128, 256, 2, 4>(a, s); else return TOC3D_ERR_ARG; break;   // 64x64 per wave, 96 KiB
-        case 63: if (sizeof(T) == 2) launch_phased<EPI, 128, 128, 2, 4>(a, s); else return TOC3D_ERR_ARG; break;   // 64x32 per wave, 64 KiB: two per CU
-        // register-pipelined rings (bf16 only; gemm_tile, PIPE): the next K step's fragments are read while the current one's MFMAs run -- for one workgroup per CU
-#define TOC3D_PIPE(BM_, BN_, ST_, WM_, WN_)                                                                                                              \
-        if constexpr (sizeof(T) == 2 && EPI != TOC3D_EPI_CONV3X3) launch_cfg<bf16_t, EPI, BM_, BN_, ST_, 128, WM_, WN_, 1, 1>(a, s); \
-        else return TOC3D_ERR_ARG;                                                                                                                       \
-        break
-        case 64: TOC3D_PIPE(128, 128, 4, 2, 4);              // variant 29's tile and ring: 8 waves, 64x32 per wave, 128 KiB
-        case 65: TOC3D_PIPE(128, 128, 3, 2, 4);              // variant 28's: 96 KiB
-        case 66: TOC3D_PIPE(128, 128, 4, 2, 2);              // 4 waves, 64x64 per wave, 128 KiB
-#undef TOC3D_PIPE
+    return variant;
+}
+
+// the launch a row's form names; X: 0 = the element type's own products, 3 / 6 = bf16 x 3 / x 6
+template <typename T, int EPI, int BM, int BN, int STAGES, int RB, int WM, int WN, int FORM, int OCC, int X>
+void launch_tile(const GemmArgs& a, hipStream_t s) {
+    if constexpr (FORM == F_PHASED) launch_phased<EPI, BM, BN, WM, WN, X != 0>(a, s);
+    else launch_cfg<T, EPI, BM, BN, STAGES, RB, WM, WN, OCC, FORM == F_PIPE ? 1 : X>(a, s);
+}
+
+// the three dispatchers: a row's case launches it if its family column serves this instantiation, else the id is refused like an unknown one
+// (if constexpr: a refused row instantiates no kernel)
+template <typename T, int EPI>
+int launch_epi(int variant, GemmArgs a, hipStream_t s) {
+    constexpr bool B = sizeof(T) == 2, ROPE = epi_is_rope(EPI);
+    switch (decode_variant(variant, a)) {
+#define ROW(ID, BM, BN, ST, RB, WM, WN, FORM, MAIN, OCC, XF, XOCC, SKF, SKOCC)                                                              \
+        case ID:                                                                                                                          \
+            if constexpr ((MAIN == S_ALL || B) && !(FORM == F_PIPE && EPI == TOC3D_EPI_CONV3X3)) launch_tile<T, EPI, BM, BN, ST, RB, WM, WN, FORM, (OCC), 0>(a, s); \
+            else return TOC3D_ERR_ARG;                                                                                                    \
+            break;
+        TOC3D_GEMM_TILES(ROW)
+#undef ROW
         default: return TOC3D_ERR_ARG;
     }
     return TOC3D_OK;
 }
 
-// bf16 x 3 / x 6 products on f32 operands (TOC3D_DTYPE_F32X3 / F32X6): a set of tile variants (same numbering as launch_epi)
+// bf16 x 3 / x 6 products on f32 operands (TOC3D_DTYPE_F32X3 / F32X6)
 template <int EPI, int X>
 int launch_epi_x(int variant, GemmArgs a, hipStream_t s) {
-    if (variant >= 300) { a.order = 3; variant -= 300; }
-    else if (variant >= 200) { a.order = 2; variant -= 200; }
-    else if (variant >= 100) { a.order = 1; variant -= 100; }
-    if (variant == 0) {
-        const int t128 = ((a.M + 127) / 128) * ((a.N + 127) / 128);
-        variant = t128 < 700 ? 17 : 16;
+    constexpr bool ROPE = epi_is_rope(EPI);
+    switch (decode_variant(variant, a)) {
+#define ROW(ID, BM, BN, ST, RB, WM, WN, FORM, MAIN, OCC, XF, XOCC, SKF, SKOCC)                                                              \
+        case ID:                                                                                                                          \
+            if constexpr (XF == S_X36 || (XF == S_X3 && X == 3)) launch_tile<float, EPI, BM, BN, ST, RB, WM, WN, FORM, (XOCC), X>(a, s);   \
+            else return TOC3D_ERR_ARG;                                                                                                    \
+            break;
+        TOC3D_GEMM_TILES(ROW)
+#undef ROW
+        default: return TOC3D_ERR_ARG;
     }
-    // the rotating q|k|v epilogue (round 6) is held to 128 registers on the 8-wave tiles that share a CU between two workgroups (the bf16 form of variants 52 / 53 does the
-    // same): unconstrained, variant 49 took 148 -- ONE workgroup per CU, 137 instead of ~75 us for q|k|v at M = 6000
-    constexpr int RO = epi_is_rope(EPI) ? 4 : 1;
+    return TOC3D_OK;
+}
+
+// split-K forms (gemm_epi_splitk.hip instantiates the residual epilogues); X3: 0 or 3
+template <typename T, int EPI, int X3 = 0>
+int launch_epi_sk(int variant, const GemmArgs& a, hipStream_t s) {
+    constexpr bool B = sizeof(T) == 2;
     switch (variant) {
-        case 1: launch_cfg<float, EPI, 128, 128, 2, 128, 2, 2, 1, X>(a, s); break;
-        case 8: launch_cfg<float, EPI, 128, 128, 1, 128, 2, 2, 1, X>(a, s); break;
-        // round 5 (fp32x3 is the constructor default now): the tiles the bf16 tables lean on, for the x3 tables' in-place tuning -- the three-product K step is
-        // longer, so tile-count quantisation weighs more
-        case 9: launch_cfg<float, EPI, 128, 64, 2, 128, 2, 2, 1, X>(a, s); break;
-        case 29: if constexpr (X == 3) launch_cfg<float, EPI, 128, 128, 4, 128, 2, 4, 1, X>(a, s); else return TOC3D_ERR_ARG; break;
-        case 33: if constexpr (X == 3) launch_cfg<float, EPI, 128, 64, 4, 128, 2, 4, 1, X>(a, s); else return TOC3D_ERR_ARG; break;
-        case 45: if constexpr (X == 3) launch_cfg<float, EPI, 128, 192, 2, 128, 2, 4, RO, X>(a, s); else return TOC3D_ERR_ARG; break;
-        case 47: if constexpr (X == 3) launch_cfg<float, EPI, 128, 192, 2, 128, 4, 2, RO, X>(a, s); else return TOC3D_ERR_ARG; break;
-        case 52: if constexpr (X == 3) launch_cfg<float, EPI, 192, 192, 1, 128, 2, 4, RO, X>(a, s); else return TOC3D_ERR_ARG; break;
-        case 53: if constexpr (X == 3) launch_cfg<float, EPI, 192, 192, 2, 128, 2, 4, 1, X>(a, s); else return TOC3D_ERR_ARG; break;
-        case 10: launch_cfg<float, EPI, 64, 128, 2, 128, 2, 2, 1, X>(a, s); break;
-        case 14: launch_cfg<float, EPI, 64, 64, 2, 128, 2, 2, 1, X>(a, s); break;
-        case 16: launch_cfg<float, EPI, 128, 128, 1, 128, 2, 4, 1, X>(a, s); break;
-        case 17: launch_cfg<float, EPI, 128, 128, 2, 128, 2, 4, 1, X>(a, s); break;
-        case 19: launch_cfg<float, EPI, 256, 128, 1, 128, 4, 2, RO, X>(a, s); break;
-        case 22: launch_cfg<float, EPI, 128, 128, 1, 256, 2, 4, RO, X>(a, s); break;      // K-tile of 64 f32: half the barriers per K
-        case 26: launch_cfg<float, EPI, 64, 128, 1, 256, 2, 4, 1, X>(a, s); break;
-        case 28: launch_cfg<float, EPI, 128, 128, 3, 128, 2, 4, 1, X>(a, s); break;
-        case 49: launch_cfg<float, EPI, 192, 128, 2, 128, 2, 4, RO, X>(a, s); break;
-        // phased big tiles on planes (round 6; gemm_phased_kernel, X3): both operands must be planes (TOC3D_DTYPE_F32X3P), K a multiple of 32
-        // M-tiles of 96 / 160 rows on planes (round 6: the N = 1024 residual GEMMs of the accelerated blocks make 176-392 tiles of 128 rows for 256 CUs; see the bf16 table)
-        case 54: if constexpr (X == 3) launch_cfg<float, EPI, 96, 128, 1, 128, 2, 4, 1, X>(a, s); else return TOC3D_ERR_ARG; break;
-        case 55: if constexpr (X == 3) launch_cfg<float, EPI, 96, 128, 2, 128, 2, 4, 1, X>(a, s); else return TOC3D_ERR_ARG; break;
-        case 56: if constexpr (X == 3) launch_cfg<float, EPI, 96, 128, 4, 128, 2, 4, 1, X>(a, s); else return TOC3D_ERR_ARG; break;
-        case 57: if constexpr (X == 3) launch_cfg<float, EPI, 160, 128, 1, 128, 2, 4, 1, X>(a, s); else return TOC3D_ERR_ARG; break;
-        case 58: if constexpr (X == 3) launch_cfg<float, EPI, 160, 128, 2, 128, 2, 4, 1, X>(a, s); else return TOC3D_ERR_ARG; break;
-        case 59: if constexpr (X == 3) launch_cfg<float, EPI, 192, 128, 3, 128, 2, 4, 1, X>(a, s); else return TOC3D_ERR_ARG; break;
-        case 60: if constexpr (X == 3) launch_phased<EPI, 256, 256, 2, 4, true>(a, s); else return TOC3D_ERR_ARG; break;
-        case 61: if constexpr (X == 3) launch_phased<EPI, 256, 128, 4, 2, true>(a, s); else return TOC3D_ERR_ARG; break;
-        case 62: if constexpr (X == 3) launch_phased<EPI, 128, 256, 2, 4, true>(a, s); else return TOC3D_ERR_ARG; break;
-        case 63: if constexpr (X == 3) launch_phased<EPI, 128, 128, 2, 4, true>(a, s); else return TOC3D_ERR_ARG; break;
+#define ROW(ID, BM, BN, ST, RB, WM, WN, FORM, MAIN, OCC, XF, XOCC, SKF, SKOCC)                                                              \
+        case ID:                                                                                                                          \
+            if constexpr (SKF == S_SK || (SKF == S_SK_NOX && X3 == 0)) launch_cfg_sk<T, EPI, BM, BN, ST, RB, WM, WN, (SKOCC), X3>(a, s);   \
+            else return TOC3D_ERR_ARG;                                                                                                    \
+            break;
+        TOC3D_GEMM_TILES(ROW)
+#undef ROW
         default: return TOC3D_ERR_ARG;
     }
     return TOC3D_OK;

@@ -357,40 +357,12 @@ __global__ __launch_bounds__(1024) void window_topk_kernel(const float* __restri
 //                              fast set, LDS tree (fixed order -> deterministic), wave 0 normalises it;
 //   blocks [nW, nW + ceil(nW*k/16)) : one wave per kept row: copy + LayerNorm.
 // ---------------------------------------------------------------------------------------------------
-// The PREVIOUS block's scatter folded into this gather (toc3d_gather_merge_ln_pending): a token's current value is not in x yet -- it is the
-// previous selection's compact row (kept tokens) or x + the previous representative token's branch outputs (dropped tokens), exactly what
-// toc3d_scatter_update would have written.  inv[token] >= 0: compact row of the previous selection; < 0: -(1 + previous window).  The wave
-// that gathers a token (every real token is gathered exactly once: kept -> copied, dropped -> merged) also writes that value back to x.
-struct PendingScatter {
-    const int32_t* inv; const float* slow; const float* r1; const float* r2; const float* r3; const float* r4; float* xw;
-};
-
-template <bool PENDING>
-TOC3D_DEV f32x4 token_value(const float* __restrict__ x, int C, int src, int pk, int vi, const PendingScatter& pd) {
-    if constexpr (!PENDING) {
-        return *reinterpret_cast<const f32x4*>(x + (int64_t)src * C + 4 * vi);
-    } else {
-        f32x4 v;
-        if (pk >= 0) {
-            v = *reinterpret_cast<const f32x4*>(pd.slow + (int64_t)pk * C + 4 * vi);
-        } else {
-            const int64_t wo = (int64_t)(-1 - pk) * C + 4 * vi;
-            v = *reinterpret_cast<const f32x4*>(pd.xw + (int64_t)src * C + 4 * vi);      // (through the writable alias: x itself is declared __restrict__)
-            v = (v + *reinterpret_cast<const f32x4*>(pd.r1 + wo)) + *reinterpret_cast<const f32x4*>(pd.r2 + wo);       // toc3d_eva_vit.py:454-456, the scatter kernel's order
-            if (pd.r3) v = (v + *reinterpret_cast<const f32x4*>(pd.r3 + wo)) + *reinterpret_cast<const f32x4*>(pd.r4 + wo);
-        }
-        *reinterpret_cast<f32x4*>(pd.xw + (int64_t)src * C + 4 * vi) = v;
-        return v;
-    }
-}
-
-template <typename T, int MAXV, bool PENDING>
+template <typename T, int MAXV>
 __global__ __launch_bounds__(1024) void gather_merge_ln_kernel(const float* __restrict__ x, int C, const int32_t* __restrict__ tok,
                                                                const float* __restrict__ wgt, const int32_t* __restrict__ crow_tok,
                                                                const int32_t* __restrict__ rep_row, int nW, int N, int k, int Ms,
                                                                const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
-                                                               float* __restrict__ shortcut, T* __restrict__ a_out, int64_t lda, int kept_copy,
-                                                               PendingScatter pd) {
+                                                               float* __restrict__ shortcut, T* __restrict__ a_out, int64_t lda, int kept_copy) {
     extern __shared__ __attribute__((aligned(16))) float s_part[];        // [16][C]
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int nvec = C >> 2;
@@ -403,29 +375,27 @@ __global__ __launch_bounds__(1024) void gather_merge_ln_kernel(const float* __re
         // this wave owns fast positions p = k + wave + 16 j; lane j prefetches index/weight j, then rows are
         // fetched four at a time so the tok -> x dependency is paid once per four rows, not per row
         const int mine = (N - k - wave + 15) / 16;
-        int my_src = -1, my_pk = 0;
+        int my_src = -1;
         float my_w = 0.f;
         if (lane < mine) {
             my_src = tok[(int64_t)win * N + k + wave + 16 * lane];
             my_w = wgt[(int64_t)win * N + k + wave + 16 * lane];
-            if (PENDING && my_src >= 0) my_pk = pd.inv[my_src];
         }
         for (int j0 = 0; j0 < mine; j0 += 4) {
-            int src[4], pk[4];
+            int src[4];
             float wg[4];
             f32x4 row[4][MAXV];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 // (v_readlane: the lane index is wave-uniform; __shfl would be a ds_bpermute round trip between the index load and the row loads it feeds)
                 src[u] = __builtin_amdgcn_readlane(my_src, (j0 + u) & 63);
-                pk[u] = PENDING ? __builtin_amdgcn_readlane(my_pk, (j0 + u) & 63) : 0;
                 wg[u] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, my_w), (j0 + u) & 63));
                 if (j0 + u >= mine) src[u] = -1;         // padded slots (src < 0) contribute x = 0; their weight is in the denominator
 #pragma unroll
                 for (int i = 0; i < MAXV; ++i) {
                     const int vi = lane + 64 * i;
                     row[u][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-                    if (vi < nvec && src[u] >= 0) row[u][i] = token_value<PENDING>(x, C, src[u], pk[u], vi, pd);
+                    if (vi < nvec && src[u] >= 0) row[u][i] = *reinterpret_cast<const f32x4*>(x + (int64_t)src[u] * C + 4 * vi);
                 }
             }
 #pragma unroll
@@ -468,14 +438,13 @@ __global__ __launch_bounds__(1024) void gather_merge_ln_kernel(const float* __re
     if (orow >= Ms) return;
     const int src = crow_tok[orow];
     if (src == -2) return;                               // representative row: written by its window's block above
-    const int pk = (PENDING && src >= 0) ? pd.inv[src] : 0;
     f32x4 v[MAXV];
 #pragma unroll
     for (int i = 0; i < MAXV; ++i) {
         const int vi = lane + 64 * i;
         v[i] = f32x4{0.f, 0.f, 0.f, 0.f};
         if (vi < nvec) {
-            if (src >= 0) v[i] = token_value<PENDING>(x, C, src, pk, vi, pd);
+            if (src >= 0) v[i] = *reinterpret_cast<const f32x4*>(x + (int64_t)src * C + 4 * vi);
             // the f32 copy of a kept row is only needed when the projection GEMM reads its residual from the compact buffer; with
             // kept_copy == 0 that GEMM gathers the row from x itself (toc3d_linear_fused residual_index) and 40 % of this kernel's bytes go
             // (explicit zero rows, src < 0, keep theirs: the GEMM reads rows without a token in place)
@@ -618,17 +587,6 @@ __global__ __launch_bounds__(1024 / GM_SPLIT) void gather_merge_ln_split_kernel(
     wave_ln_write<T, MAXV>(v, nvec, lane, mean, rstd, gamma, beta, a_out + orow * lda);
 }
 
-// token -> slot of a selection: inv[token] = compact row (kept) or -(1 + window) (dropped); pad slots (tok < 0) have no token.
-__global__ __launch_bounds__(256) void token_inverse_map_kernel(const int32_t* __restrict__ tok, const int32_t* __restrict__ prow, int nW, int N, int k,
-                                                                int32_t* __restrict__ inv) {
-    const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (id >= (int64_t)nW * N) return;
-    const int t = tok[id];
-    if (t < 0) return;
-    const int p = (int)(id % N);
-    inv[t] = p < k ? prow[id] : -1 - (int)(id / N);
-}
-
 // scatter the slow rows back and add the representative token's branch outputs to the fast rows, in place.
 __global__ __launch_bounds__(256) void scatter_update_kernel(float* __restrict__ x, int C, const int32_t* __restrict__ tok,
                                                              const int32_t* __restrict__ prow, int nW, int N, int k,
@@ -711,27 +669,6 @@ __global__ __launch_bounds__(256) void copy_bytes_kernel(char* __restrict__ dst,
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += stride)
         reinterpret_cast<f32x4*>(dst)[i] = reinterpret_cast<const f32x4*>(src)[i];
     for (int64_t j = n16 * 16 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < nbytes; j += stride) dst[j] = src[j];
-}
-
-// Pull a read-only buffer (the next block's packed weights) towards the chip ahead of its use: plain 16-byte loads whose values are
-// kept alive but never stored.  The lines land in the Infinity Cache (and the L2 of the XCD the workgroup runs on); the GEMM that follows
-// then starts on cache hits instead of HBM misses.  Few workgroups on purpose: this runs beside the block chain on a side lane.
-constexpr int PREFETCH_MAX_SEGS = 8;
-struct PrefetchSegs { const f32x4* ptr[PREFETCH_MAX_SEGS]; int64_t n16[PREFETCH_MAX_SEGS]; };
-
-__global__ __launch_bounds__(256) void prefetch_kernel(PrefetchSegs sg, float* __restrict__ sink) {
-    const f32x4* __restrict__ p = sg.ptr[blockIdx.y];
-    const int64_t n16 = sg.n16[blockIdx.y];
-    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    for (; i + 3 * stride < n16; i += 4 * stride) {              // four independent loads in flight per thread
-        const f32x4 a = p[i], b = p[i + stride], c = p[i + 2 * stride], d = p[i + 3 * stride];
-        acc += (a + b) + (c + d);
-    }
-    for (; i < n16; i += stride) acc += p[i];
-    // never true for finite data that is not all-NaN; keeps the loads observable without writing anything
-    if (acc[0] != acc[0] && acc[1] != acc[1] && acc[2] != acc[2] && acc[3] != acc[3] && sink) sink[0] = acc[0];
 }
 
 // several small device-to-device copies in ONE launch (the per-frame inputs of the recorded plan: every launch has a ~5 us floor)
@@ -866,22 +803,22 @@ int toc3d_window_topk(const float* scores, int64_t V, int64_t h, int64_t w, int6
 
 static int launch_gather(int dtype, const float* x, int64_t C, const int32_t* tok, const float* wgt, const int32_t* crow_tok, const int32_t* rep_row,
                          int64_t nW, int64_t N, int64_t k, int64_t rows, const float* gamma, const float* beta, float eps, float* shortcut, void* a_out,
-                         int64_t lda, int64_t kept_copy, PendingScatter pd, toc3d_stream_t stream) {
+                         int64_t lda, int64_t kept_copy, toc3d_stream_t stream) {
     dim3 grid((unsigned)(nW + (rows + 15) / 16)), block(1024);
     const size_t lds = (size_t)16 * C * 4;
     hipStream_t s = as_stream(stream);
-#define TOC3D_GATHER(T, P)                                                                                                          \
+#define TOC3D_GATHER(T)                                                                                                             \
     do {                                                                                                                            \
         static Toc3dLdsAttr attr;                                                                                                   \
-        attr.ensure(reinterpret_cast<const void*>(&gather_merge_ln_kernel<T, 4, P>), 65536);                                        \
-        toc3d_launch((gather_merge_ln_kernel<T, 4, P>), grid, block, lds, s, x, (int)C, tok, wgt, crow_tok, rep_row, (int)nW, (int)N, (int)k, (int)rows, \
-                     gamma, beta, eps, shortcut, (T*)a_out, lda, (int)(kept_copy != 0), pd);                                        \
+        attr.ensure(reinterpret_cast<const void*>(&gather_merge_ln_kernel<T, 4>), 65536);                                        \
+        toc3d_launch((gather_merge_ln_kernel<T, 4>), grid, block, lds, s, x, (int)C, tok, wgt, crow_tok, rep_row, (int)nW, (int)N, (int)k, (int)rows, \
+                     gamma, beta, eps, shortcut, (T*)a_out, lda, (int)(kept_copy != 0));                                            \
     } while (0)
-    if (dtype == TOC3D_BF16) TOC3D_GATHER(bf16_t, false);
-    else if (dtype == TOC3D_F32) TOC3D_GATHER(float, false);
+    if (dtype == TOC3D_BF16) TOC3D_GATHER(bf16_t);
+    else if (dtype == TOC3D_F32) TOC3D_GATHER(float);
     else if (dtype == TOC3D_F32X3P) {            // a_out as (hi, lo) planes (the q|k|v GEMM's A operand); shortcut stays f32
         TOC3D_REQUIRE(planes_rows_ok(a_out, lda), "toc3d_gather_merge_ln: rows of (hi, lo) planes start on 128-byte boundaries (a_out aligned, lda a multiple of 32)");
-        TOC3D_GATHER(f32p_t, false);
+        TOC3D_GATHER(f32p_t);
     }
     else { toc3d_set_error("toc3d_gather_merge_ln: bad dtype"); return TOC3D_ERR_ARG; }
 #undef TOC3D_GATHER
@@ -901,7 +838,7 @@ int toc3d_gather_merge_ln_ex(int dtype, const float* x, int64_t C, const int32_t
     TOC3D_REQUIRE(N - k <= 1024, "toc3d_gather_merge_ln: N - k = %lld dropped tokens per window exceed the kernel's 1024", (long long)(N - k));
     TOC3D_REQUIRE(N <= TOKEN_ROWS_MAX && rows <= TOKEN_ROWS_MAX, "toc3d_gather_merge_ln: too many rows (N, rows: the kernel counts in 32 bits)");
     if (nW <= 0) return TOC3D_OK;
-    return launch_gather(dtype, x, C, tok, wgt, crow_tok, rep_row, nW, N, k, rows, gamma, beta, eps, shortcut, a_out, lda, kept_copy, PendingScatter{}, stream);
+    return launch_gather(dtype, x, C, tok, wgt, crow_tok, rep_row, nW, N, k, rows, gamma, beta, eps, shortcut, a_out, lda, kept_copy, stream);
 }
 
 

@@ -149,10 +149,12 @@ def _tune(dtg, epi, call, out, ldo, rep_out, M):
         o = torch.empty(M, ldo, dtype=torch.float32, device=out.device)
     rep_s = torch.empty_like(rep_out) if rep_out is not None else None
     cands = _VARIANTS[dtg]
+    # what launch_cfg (csrc/gemm_kernels.h) refuses, read off the tile's geometry
+    bn, wn = (lambda v: lib.TILES[v % 100][1]), (lambda v: lib.TILES[v % 100][3])
     if epi in (lib.EPI_SWIGLU, lib.EPI_SWIGLU_STATS, lib.EPI_SWIGLU_STATS_LN):
-        cands = [v for v in cands if v not in (33, 45, 145, 52, 53, 152)]   # wave slabs that are not whole (w1, w2) 32-column groups
-    if epi in (lib.EPI_SWIGLU_STATS, lib.EPI_SWIGLU_STATS_LN):  # statistics slots are 128 packed columns: N-tiles of 128 / 256 only
-        cands = [v for v in cands if v % 100 not in (9, 13, 14, 27, 33, 45, 47)]
+        cands = [v for v in cands if (bn(v) // wn(v)) % 32 == 0]     # a wavefront owns whole (w1, w2) 32-column groups
+    if epi in (lib.EPI_SWIGLU_STATS, lib.EPI_SWIGLU_STATS_LN):
+        cands = [v for v in cands if bn(v) % 128 == 0]               # statistics slots are 128 packed columns
     # Inside the block sequence every GEMM starts on cold operands (the previous kernels streamed tens of MB through
     # L2 / Infinity Cache): time single launches behind a cache-sized memset, not a warm back-to-back loop, or the
     # tuner prefers shallow pipelines that lose in place (tools/ubench/n1024_all_variants.py).

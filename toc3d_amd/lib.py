@@ -22,10 +22,50 @@ EPI_BIAS_RELU = 10              # relu(A.W^T + bias): served wherever EPI_BIAS i
 # that kernel's softmax is exp2-based (include/toc3d.h), so the conversion factor rides on the multiply the epilogue does anyway
 ATTN_ROT_Q_SCALE = 64 ** -0.5 * 1.4426950408889634
 NO_FUSED = (None, 0, None, 0, None, 0, 0.0, None, 0, None)     # the ten extra arguments of toc3d_linear_fused for epilogues 0-3
-# GEMM tile variants (mod 100; + 100 / 200 / 300 select the XCD order at run time) the product library carries: every variant the autotuner may pick or a
-# shipped table names (csrc/gemm_kernels.h launch_epi).
-PRODUCT_VARIANTS = (1, 8, 9, 10, 13, 14, 15, 16, 17, 19, 22, 24, 26, 27, 28, 29, 30, 33, 45, 47, 49, 51, 52, 53, 54, 55, 56, 57, 58, 59, 60, 61, 62, 63, 64, 65, 66)
-# ... of which the bf16 x 3 forms exist only with BOTH operands as (hi, lo) planes (TOC3D_DTYPE_F32X3P / F32X3WA): the 96- / 160-row tiles and the phased big tiles
+# GEMM tiles: id -> (BM, BN, WM, WN, (bf16|f32, x3|x6, split-K family code)) -- the host's twin of the one tile table, TOC3D_GEMM_TILES in csrc/gemm_kernels.h (the
+# family codes are that table's, without the S_ prefix; tests/test_cpu_abi.py parses the C++ rows and holds the two together).  A NEW TILE IS ONE NEW ROW HERE.
+# The id is a variant mod 100: + 100 / 200 / 300 select the XCD order at run time, + 1000 * split the split-K form.
+TILES = {
+    1: (128, 128, 2, 2, ("ALL", "X36", "SK")),
+    8: (128, 128, 2, 2, ("ALL", "X36", "NONE")),
+    9: (128, 64, 2, 2, ("ALL", "X36", "SK")),
+    10: (64, 128, 2, 2, ("ALL", "X36", "SK")),
+    13: (128, 64, 2, 2, ("ALL", "NONE", "NONE")),
+    14: (64, 64, 2, 2, ("ALL", "X36", "SK")),
+    15: (128, 128, 2, 2, ("ALL", "NONE", "NONE")),
+    16: (128, 128, 2, 4, ("ALL", "X36", "SK")),
+    17: (128, 128, 2, 4, ("ALL", "X36", "SK")),
+    19: (256, 128, 4, 2, ("ALL", "X36", "SK")),
+    22: (128, 128, 2, 4, ("ALL", "X36", "SK")),
+    24: (64, 128, 2, 4, ("ALL", "NONE", "NONE")),
+    26: (64, 128, 2, 4, ("ALL", "X36", "SK")),
+    27: (64, 64, 2, 2, ("ALL", "NONE", "NONE")),
+    28: (128, 128, 2, 4, ("ALL", "X36", "SK")),
+    29: (128, 128, 2, 4, ("ALL", "X3", "SK_NOX")),
+    30: (128, 128, 2, 4, ("BF16", "NONE", "NONE")),
+    33: (128, 64, 2, 4, ("ALL", "X3", "NONE")),
+    45: (128, 192, 2, 4, ("ALL", "X3", "NONE")),
+    47: (128, 192, 4, 2, ("ALL", "X3", "NONE")),
+    49: (192, 128, 2, 4, ("ALL", "X36", "NONE")),
+    51: (128, 128, 2, 4, ("ALL", "NONE", "NONE")),
+    52: (192, 192, 2, 4, ("ALL", "X3", "NONE")),
+    53: (192, 192, 2, 4, ("ALL", "X3", "NONE")),
+    54: (96, 128, 2, 4, ("ALL", "X3", "NONE")),
+    55: (96, 128, 2, 4, ("ALL", "X3", "SK_NOX")),
+    56: (96, 128, 2, 4, ("ALL", "X3", "SK_NOX")),
+    57: (160, 128, 2, 4, ("ALL", "X3", "NONE")),
+    58: (160, 128, 2, 4, ("ALL", "X3", "NONE")),
+    59: (192, 128, 2, 4, ("ALL", "X3", "NONE")),
+    60: (256, 256, 2, 4, ("BF16", "X3", "NONE")),
+    61: (256, 128, 4, 2, ("BF16", "X3", "NONE")),
+    62: (128, 256, 2, 4, ("BF16", "X3", "NONE")),
+    63: (128, 128, 2, 4, ("BF16", "X3", "NONE")),
+    64: (128, 128, 2, 4, ("BF16", "NONE", "NONE")),
+    65: (128, 128, 2, 4, ("BF16", "NONE", "NONE")),
+    66: (128, 128, 2, 2, ("BF16", "NONE", "NONE")),
+}
+PRODUCT_VARIANTS = tuple(TILES)    # every tile the autotuner may pick or a shipped table names
+# ... of which the tuner and the shipped tables treat the bf16 x 3 forms as existing only with BOTH operands as (hi, lo) planes (TOC3D_DTYPE_F32X3P / F32X3WA): the 96- / 160-row tiles and the phased big tiles
 X3_PLANES_ONLY_VARIANTS = (54, 55, 56, 57, 58, 59, 60, 61, 62, 63)
 
 
@@ -149,9 +189,6 @@ def load():
     lib.toc3d_plan_lane_stream.argtypes = [_I64]
     lib.toc3d_plan_num_launches.restype = _I64
     lib.toc3d_plan_num_launches.argtypes = [_P]
-    if hasattr(lib, "toc3d_linear_chain_info"):
-        lib.toc3d_linear_chain_info.restype = _I        # number of ops (< 0: unknown config), not an error code
-        lib.toc3d_linear_chain_info.argtypes = [_I, _P]
     for name, sig in _SIGS.items():
         fn = getattr(lib, name)
         fn.restype = _I
@@ -190,11 +227,6 @@ def copy_segments(pairs, stream):
         d, b = ptr_arrays([t for t, _ in chunk])
         s, _ = ptr_arrays([t for _, t in chunk])
         call("toc3d_copy_segments", len(chunk), d, s, b, stream)
-
-
-def prefetch(tensors, workgroups, stream):
-    """One toc3d_prefetch launch over up to 8 (contiguous) device tensors."""
-    call("toc3d_prefetch", len(tensors), *ptr_arrays(tensors), workgroups, stream)
 
 
 # Lane of the launch plan being recorded by THIS thread (toc3d_amd/plan.py); None = launch on torch's current stream.  Thread-local
