@@ -30,7 +30,10 @@
 extern "C" {
 #endif
 
-#define TOC3D_ABI_VERSION 11  /* bumped whenever entry points are added or changed; toc3d_amd/lib.py checks it before binding symbols */
+/* The major version moves when an entry point is changed or removed (an incompatible change), the minor when one is added; a new major starts at minor 0.
+ * toc3d_amd/lib.py checks both before binding symbols: the major must be equal, the minor at least the one it binds. */
+#define TOC3D_ABI_VERSION 11
+#define TOC3D_ABI_MINOR 1     /* 1: toc3d_neck_rows_fanout */
 
 #define TOC3D_OK 0
 #define TOC3D_ERR_ARG (-1)
@@ -89,6 +92,7 @@ extern "C" {
 typedef void* toc3d_stream_t;
 
 int toc3d_abi_version(void);
+int toc3d_abi_minor(void);
 const char* toc3d_last_error(void); /* thread-local, valid until the next failing call on this thread */
 
 /* ---------------------------------------------------------------------------------------------------
@@ -496,12 +500,22 @@ int toc3d_memory_post_update(const float* emb_in, const float* ref_in, const dou
  * dtype: TOC3D_DTYPE_BF16, TOC3D_DTYPE_F32, or -- toc3d_head_frustum_inputs (pos_in, cone_act), toc3d_nchw_to_rows (out), toc3d_mln_apply (out_act) --
  *   TOC3D_DTYPE_F32X3P: f32 arithmetic unchanged, the act rows written as (hi, lo) planes in the layout toc3d_head_query_inputs writes (the A operand of a
  *   bf16 x 3 GEMM on planes).  Such a buffer is 128-byte aligned and its leading dimension a multiple of 32 (refused otherwise); only the valid columns'
- *   hi and lo parts are written (pre-zero once: zero bytes are zero planes).  The f32 outputs `cone` and `out` stay plain. */
+ *   hi and lo parts are written (pre-zero once: zero bytes are zero planes).  The f32 outputs `cone` and `out` stay plain.
+ * toc3d_neck_rows_fanout (ABI minor 1): the hand-off from the neck to the head in one pass.  The detector `.view()`s the neck's level-0 output as NCHW
+ *   (detectors/petr3d.py:189-190,239) and the head flattens and permutes it straight back to token rows (dense_heads/streampetr_head.py:629); with both
+ *   modules in one detector the neck's conv rows fan out to both forms.  x f32 [V*T, ldx] (ldx >= C: the neck's conv output rows, T = h*w) is read once;
+ *   nchw f32 [V, C, T] gets the bits of toc3d_nhwc_to_nchw(x), through the same padded LDS tile; rows [V*T, ld_rows] in `dtype` (BF16, F32 or F32X3P)
+ *   gets the bits of toc3d_nchw_to_rows(dtype, nchw, rows, ...), written straight from the registers: the same conversion, and only the C valid columns --
+ *   columns [C, ld_rows) are not touched; for planes, only the valid hi and lo parts (rule and refusal as above).  16-byte accesses where C, T, the leading
+ *   dimensions and the pointers allow, element-wise otherwise (same bits).  Null pointers, ldx < C, ld_rows < C, V > 65535, a non-positive size or another
+ *   dtype: TOC3D_ERR_ARG, nothing is launched. */
 int toc3d_head_frustum_inputs(int dtype, const float* img2lidar, const float* intrinsics, const float* coords_d, const float* position_range,
                               int64_t B, int64_t N, int64_t h, int64_t w, int64_t D, int64_t stride, int64_t pad_h, int64_t pad_w,
                               void* pos_in, int64_t ld_pos, void* cone_act, int64_t ld_cone, float* cone, toc3d_stream_t stream);
 int toc3d_relu_inplace(int dtype, void* x, int64_t n, toc3d_stream_t stream);
 int toc3d_nchw_to_rows(int dtype, const float* x, void* out, int64_t ldo, int64_t V, int64_t C, int64_t hw, toc3d_stream_t stream);
+int toc3d_neck_rows_fanout(int dtype, const float* x, int64_t ldx, float* nchw, void* rows, int64_t ld_rows, int64_t V, int64_t T, int64_t C,
+                           toc3d_stream_t stream);
 int toc3d_mln_apply(int dtype, const float* x, const float* gamma, const float* beta, int64_t M, int64_t E, float* out, void* out_act, int64_t ld_act,
                     toc3d_stream_t stream);
 int toc3d_se_gate(const float* pos, const float* se, float* out, int64_t n, toc3d_stream_t stream);

@@ -104,6 +104,67 @@ __global__ __launch_bounds__(256) void nchw_rows_kernel(const float* __restrict_
     }
 }
 
+// 4 consecutive elements of an act row, the first at a multiple of 4 columns of an aligned row: per element the bits of put1, as one 16-byte (f32) or
+// 8-byte (bf16; each plane of f32p_t) store
+TOC3D_DEV void put4(float* p, const float (&v)[4]) { store4(p, v); }
+TOC3D_DEV void put4(bf16_t* p, const float (&v)[4]) {
+    const bf16_t b[4] = {to_act<bf16_t>(v[0]), to_act<bf16_t>(v[1]), to_act<bf16_t>(v[2]), to_act<bf16_t>(v[3])};
+    store4(p, b);
+}
+TOC3D_DEV void put4(f32p_t* p, const float (&v)[4]) { store4_planes(p, v); }
+
+// The neck's conv rows x f32 [V*T, ldx], read ONCE, written twice: rows [V*T, ld] act straight from the registers (what nchw_rows_kernel would make of the
+// NCHW tensor: the same put1 per element, valid columns only), and NCHW f32 [V, C, T] through nhwc_to_nchw_kernel's padded 32 x 32 tile.  One workgroup per
+// (view, 32 tokens, 32 channels).  VIN: x and rows take 4-column accesses (16-byte loads; host-checked alignment, C % 4 == 0) -- thread = (token tid / 8,
+// column quad tid % 8); VOUT: nchw takes 16-byte stores along T (T % 4 == 0) -- thread = (channel tid / 8, token quad tid % 8).  LDS traffic is dword-wide
+// either way; with the row stride of 33 the 32 lanes of a half-wave (the conflict group of ds_read_b32 / ds_write_b32) hit 32 different banks in all four
+// patterns: write (r + 4 q + k) % 32 over r 0..3, q 0..7; read (4 j + k + c) % 32 over c 0..3, j 0..7; the scalar forms as in the two kernels this one replaces.
+template <typename T, bool VIN, bool VOUT>
+__global__ __launch_bounds__(256) void neck_rows_fanout_kernel(const float* __restrict__ x, int64_t ldx, float* __restrict__ nchw, T* __restrict__ rows, int64_t ld,
+                                                               int Tn, int C) {
+    __shared__ float tile[32][33];
+    const int v = blockIdx.z, t0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+    const int tid = threadIdx.x;
+    if (VIN) {
+        const int r = tid >> 3, q4 = (tid & 7) * 4;
+        const int t = t0 + r, c = c0 + q4;
+        float a[4] = {0.f, 0.f, 0.f, 0.f};
+        if (t < Tn && c < C) {                                            // C % 4 == 0: a quad is valid as a whole
+            const int64_t row = (int64_t)v * Tn + t;
+            const f32x4 g = *reinterpret_cast<const f32x4*>(x + row * ldx + c);
+            a[0] = g[0]; a[1] = g[1]; a[2] = g[2]; a[3] = g[3];
+            put4(rows + row * ld + c, a);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) tile[r][q4 + k] = a[k];
+    } else {
+        const int tx = tid & 31, ty = tid >> 5;
+        for (int i = ty; i < 32; i += 8) {
+            const int t = t0 + i, c = c0 + tx;
+            float a = 0.f;
+            if (t < Tn && c < C) {
+                const int64_t row = (int64_t)v * Tn + t;
+                a = x[row * ldx + c];
+                put1(rows + row * ld + c, a);
+            }
+            tile[i][tx] = a;
+        }
+    }
+    __syncthreads();
+    if (VOUT) {
+        const int cl = tid >> 3, j4 = (tid & 7) * 4;
+        const int c = c0 + cl, t = t0 + j4;
+        if (c < C && t < Tn)                                              // T % 4 == 0: likewise
+            *reinterpret_cast<f32x4*>(nchw + ((int64_t)v * C + c) * Tn + t) = f32x4{tile[j4][cl], tile[j4 + 1][cl], tile[j4 + 2][cl], tile[j4 + 3][cl]};
+    } else {
+        const int tx = tid & 31, ty = tid >> 5;
+        for (int i = ty; i < 32; i += 8) {
+            const int c = c0 + i, t = t0 + tx;
+            if (t < Tn && c < C) nchw[((int64_t)v * C + c) * Tn + t] = tile[tx][i];
+        }
+    }
+}
+
 // MLN.forward (misc.py:181-188): out = gamma * LayerNorm(x; no affine, eps 1e-5) + beta; one wavefront per row, E <= 1024
 template <typename T>
 __global__ __launch_bounds__(256) void mln_kernel(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -144,6 +205,15 @@ bool planes_rows_ok(int dtype, const void* act, int64_t ld) {
 }
 #define TOC3D_PLANES_ROWS(fn, what, act, ld)                                                                                                           \
     TOC3D_REQUIRE(planes_rows_ok(dtype, act, ld), fn ": " what ": rows of (hi, lo) planes start on 128-byte boundaries (buffer aligned, leading dimension a multiple of 32)")
+
+template <typename T>
+void launch_neck_rows_fanout(bool vin, bool vout, dim3 grid, hipStream_t s, const float* x, int64_t ldx, float* nchw, void* rows, int64_t ld, int Tn, int C) {
+    T* r = static_cast<T*>(rows);
+    if (vin && vout) toc3d_launch(neck_rows_fanout_kernel<T, true, true>, grid, dim3(256), 0, s, x, ldx, nchw, r, ld, Tn, C);
+    else if (vin) toc3d_launch(neck_rows_fanout_kernel<T, true, false>, grid, dim3(256), 0, s, x, ldx, nchw, r, ld, Tn, C);
+    else if (vout) toc3d_launch(neck_rows_fanout_kernel<T, false, true>, grid, dim3(256), 0, s, x, ldx, nchw, r, ld, Tn, C);
+    else toc3d_launch(neck_rows_fanout_kernel<T, false, false>, grid, dim3(256), 0, s, x, ldx, nchw, r, ld, Tn, C);
+}
 
 }  // namespace
 
@@ -192,6 +262,26 @@ int toc3d_nchw_to_rows(int dtype, const float* x, void* out, int64_t ldo, int64_
     else if (dtype == TOC3D_F32X3P) toc3d_launch(nchw_rows_kernel<f32p_t>, grid, dim3(256), 0, as_stream(stream), x, (f32p_t*)out, ldo, (int)C, (int)hw);
     else { toc3d_set_error("toc3d_nchw_to_rows: bad dtype"); return TOC3D_ERR_ARG; }
     TOC3D_LAUNCH_CHECK("toc3d_nchw_to_rows");
+    return TOC3D_OK;
+}
+
+int toc3d_neck_rows_fanout(int dtype, const float* x, int64_t ldx, float* nchw, void* rows, int64_t ld_rows, int64_t V, int64_t T, int64_t C,
+                           toc3d_stream_t stream) {
+    TOC3D_REQUIRE(x && nchw && rows, "toc3d_neck_rows_fanout: null buffer");
+    TOC3D_REQUIRE(dtype == TOC3D_BF16 || dtype == TOC3D_F32 || dtype == TOC3D_F32X3P, "toc3d_neck_rows_fanout: bad dtype");
+    TOC3D_REQUIRE(V > 0 && T > 0 && C > 0, "toc3d_neck_rows_fanout: bad dims (V, T, C > 0)");
+    TOC3D_REQUIRE(V <= 65535 && T <= 0x7fffffffll - 31 && C <= 65535ll * 32, "toc3d_neck_rows_fanout: bad dims (V <= 65535 views, T and C within one launch's grid)");
+    TOC3D_REQUIRE(ldx >= C && ld_rows >= C, "toc3d_neck_rows_fanout: bad leading dimensions (ldx >= C, ld_rows >= C)");
+    TOC3D_PLANES_ROWS("toc3d_neck_rows_fanout", "rows", rows, ld_rows);
+    // 4-column accesses: 16-byte loads of x; stores of 16 (f32) / 8 (bf16, each plane) bytes to rows
+    const uintptr_t row_align = dtype == TOC3D_BF16 ? 7 : 15;
+    const bool vin = C % 4 == 0 && ldx % 4 == 0 && ld_rows % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(rows) & row_align) == 0;
+    const bool vout = T % 4 == 0 && (reinterpret_cast<uintptr_t>(nchw) & 15) == 0;
+    dim3 grid((unsigned)((T + 31) / 32), (unsigned)((C + 31) / 32), (unsigned)V);
+    if (dtype == TOC3D_BF16) launch_neck_rows_fanout<bf16_t>(vin, vout, grid, as_stream(stream), x, ldx, nchw, rows, ld_rows, (int)T, (int)C);
+    else if (dtype == TOC3D_F32) launch_neck_rows_fanout<float>(vin, vout, grid, as_stream(stream), x, ldx, nchw, rows, ld_rows, (int)T, (int)C);
+    else launch_neck_rows_fanout<f32p_t>(vin, vout, grid, as_stream(stream), x, ldx, nchw, rows, ld_rows, (int)T, (int)C);
+    TOC3D_LAUNCH_CHECK("toc3d_neck_rows_fanout");
     return TOC3D_OK;
 }
 

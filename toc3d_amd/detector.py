@@ -1,0 +1,230 @@
+"""``Petr3D``: the assembled detector -- the reference's top-level class (``detectors/petr3d.py``) at inference time, under the reference's type name, built
+from this package's backbone (``ToC3DEVAViT`` / ``EVA_ViT``), neck (``CPFPN``) and head (``StreamPETRHead``).
+
+``simple_test`` is one frame: ``extract_img_feat`` (backbone, neck; :84-243) and ``simple_test_pts`` (head, box decoding; :521-541), with the two places where the
+ToC3D loop closes -- the head's memory bank supplies the backbone's motion queries of the NEXT frame (:115-157), and the scene token decides ``prev_exists`` and
+``reset_memory()`` (:527-532, :546-549).  The ``model=dict(type='Petr3D', ...)`` block of a shipped config builds it unchanged.
+
+One thing a detector that owns both modules does that the hand-written chain cannot: the neck's last launch fans its conv rows out
+(``toc3d_neck_rows_fanout``, :meth:`toc3d_amd.CPFPN.forward_fanout`) -- to the NCHW tensor the reference ``.view()``s (:239; ``data['img_feats']``, the bits of a
+separate ``CPFPN.forward``) and, in the same pass, to the token rows the head's ``memory_embed`` reads (``streampetr_head.py:629``), in the head's own workspace.
+The head then runs on those rows (``forward(..., img_feats_rows=True)``): the transpose back, and the copy in front of it, are gone; every other launch and every
+bit of the frame are the chain's.
+
+Differences to the reference, by design:
+* inference only: training mode, ``forward_train``, ``forward(return_loss=True)``, ``aux_2d_only=False`` and ``token_select_vis=True`` raise
+  ``NotImplementedError``; ``use_grid_mask`` is accepted (GridMask is the identity outside training, ``grid_mask.py:85``); ``test_time_print`` is accepted and ignored;
+* ``img_roi_head=dict(type='FocalHead', ...)`` is accepted and nothing is built from it: with ``aux_2d_only=True`` the reference returns ``topk_indexes=None`` at
+  eval without calling it (:319-320).  A checkpoint's ``img_roi_head.*`` keys are dropped from the unexpected keys of ``load_state_dict``; nothing else is forgiven;
+* the ``pts_*`` parts and ``img_rpn_head`` are accepted as ``None`` only; backbones and necks other than this package's are refused at construction;
+* ``prev_exists`` reaches the backbone as the Python bool the scene-token comparison already is: no host synchronisation;
+* ``extract_img_feat(img)`` does not squeeze the caller's ``img`` in place (:102 does);
+* extra keywords: ``precision`` (handed to the three parts), ``gumbel_noise=`` on ``simple_test`` / ``extract_img_feat`` (handed to the backbone).
+Derived state (packed weights, workspaces, plans, the bank) belongs to the parts; ``load_state_dict``, ``.to()`` and ``init_weights()`` drop it, and
+``prev_scene_token`` with it.  No CPU path.
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn as nn
+
+from . import plan as _plan
+from . import registry
+from .backbone import EVA_ViT, ToC3DEVAViT
+from .head import StreamPETRHead
+from .neck import CPFPN
+
+_NAME = "toc3d_amd.Petr3D"
+_ABSENT = ("pts_voxel_layer", "pts_voxel_encoder", "pts_middle_encoder", "pts_fusion_layer", "pts_backbone", "pts_neck", "img_rpn_head")
+
+
+def bbox3d2result(bboxes, scores, labels, attrs=None):
+    """mmdet3d's ``bbox3d2result`` (``mmdet3d/core/bbox/transforms.py``) when mmdet3d is importable; otherwise the dict that function builds, on the CPU."""
+    try:  # pragma: no cover - mmdet3d is not installed in the build image
+        from mmdet3d.core import bbox3d2result as _impl
+        return _impl(bboxes, scores, labels, attrs)
+    except ImportError:
+        pass
+    result = dict(boxes_3d=bboxes.to("cpu"), scores_3d=scores.cpu(), labels_3d=labels.cpu())
+    if attrs is not None:
+        result["attrs_3d"] = attrs.cpu()
+    return result
+
+
+class Petr3D(_plan.DerivedState, nn.Module):
+    def __init__(self, use_grid_mask=False, pts_voxel_layer=None, pts_voxel_encoder=None, pts_middle_encoder=None, pts_fusion_layer=None, img_backbone=None,
+                 pts_backbone=None, img_neck=None, pts_neck=None, pts_bbox_head=None, img_roi_head=None, img_rpn_head=None, train_cfg=None, test_cfg=None,
+                 num_frame_head_grads=2, num_frame_backbone_grads=2, num_frame_losses=2, stride=16, position_level=0, aux_2d_only=True, single_test=False,
+                 pretrained=None, token_select_vis=False, vis_num_sample=20, vis_start_id=0, vis_out_path="./token_vis", test_time_print=False, precision=None):
+        """Every keyword of the reference's ``__init__`` (:27-55), plus ``precision``."""
+        super().__init__()
+        given = dict(pts_voxel_layer=pts_voxel_layer, pts_voxel_encoder=pts_voxel_encoder, pts_middle_encoder=pts_middle_encoder, pts_fusion_layer=pts_fusion_layer,
+                     pts_backbone=pts_backbone, pts_neck=pts_neck, img_rpn_head=img_rpn_head)
+        present = [k for k in _ABSENT if given[k] is not None]
+        if present:
+            raise NotImplementedError(f"{_NAME}: {', '.join(present)} not implemented: the camera-only detector of the shipped configs passes None")
+        if not aux_2d_only:
+            raise NotImplementedError(f"{_NAME}: aux_2d_only=False (token selection by img_roi_head at eval, petr3d.py:319-323) is not implemented")
+        if token_select_vis:
+            raise NotImplementedError(f"{_NAME}: token_select_vis=True (petr3d.py:562-579) is not implemented")
+        if position_level != 0:
+            raise NotImplementedError(f"{_NAME}: position_level={position_level} is not implemented: the head reads neck level 0 (the shipped configs' default)")
+        if not all(isinstance(c, dict) for c in (img_backbone, img_neck, pts_bbox_head)):
+            raise ValueError(f"{_NAME}: needs img_backbone=dict(...), img_neck=dict(...) and pts_bbox_head=dict(...)")
+        if img_roi_head is not None and not (isinstance(img_roi_head, dict) and img_roi_head.get("type") == "FocalHead"):
+            raise NotImplementedError(f"{_NAME}: img_roi_head is accepted as dict(type='FocalHead', ...) or None only (nothing is built from it)")
+        kw = {} if precision is None else dict(precision=precision)
+        head_cfg = dict(pts_bbox_head)                                      # MVXTwoStageDetector.__init__: the head gets the pts slice of train_cfg / test_cfg
+        head_cfg.update(train_cfg=train_cfg.get("pts") if train_cfg else None, test_cfg=test_cfg.get("pts") if test_cfg else None)
+        self.img_backbone = registry.build_backbone(img_backbone, **kw)
+        self.img_neck = registry.build_neck(img_neck, **kw)
+        self.pts_bbox_head = registry.build_head(head_cfg, **kw)
+        if not isinstance(self.img_backbone, (EVA_ViT, ToC3DEVAViT)) or not isinstance(self.img_neck, CPFPN) or not isinstance(self.pts_bbox_head, StreamPETRHead):
+            raise NotImplementedError(f"{_NAME}: built from this package's EVA_ViT / ToC3DEVAViT, CPFPN and StreamPETRHead only, got "
+                                      f"{type(self.img_backbone).__name__}, {type(self.img_neck).__name__}, {type(self.pts_bbox_head).__name__}")
+        if self.img_neck.out_channels != self.pts_bbox_head.in_channels:
+            raise ValueError(f"{_NAME}: the neck's out_channels {self.img_neck.out_channels} != the head's in_channels {self.pts_bbox_head.in_channels}")
+        self.precision = precision
+        self.train_cfg, self.test_cfg = train_cfg, test_cfg
+        self.use_grid_mask = use_grid_mask
+        self.num_frame_head_grads, self.num_frame_backbone_grads, self.num_frame_losses = num_frame_head_grads, num_frame_backbone_grads, num_frame_losses
+        self.single_test, self.stride, self.position_level, self.aux_2d_only = single_test, stride, position_level, aux_2d_only
+        self.query_backbone_selection = getattr(self.img_backbone, "pruning_loc", None) is not None                                     # :73-74
+        self.token_select_vis, self.vis_num_sample, self.vis_out_path, self.vis_start_id, self.cur_id = False, vis_num_sample, vis_out_path, vis_start_id, 0
+        self.test_time_print = test_time_print
+        self._drop_derived()
+        self.eval()
+
+    with_img_neck, with_img_roi_head, with_pts_bbox = True, False, True
+
+    # ---- derived state: the parts keep their own; the detector's is the scene it is in and the tensor whose rows sit in the head's workspace --------------
+    _DERIVED = dict(prev_scene_token=None, _fanned=None, last_frame=None)
+
+    def train(self, mode=True):
+        if mode:
+            raise NotImplementedError(f"{_NAME}: training mode is not implemented (inference only)")
+        return super().train(False)
+
+    def init_weights(self):
+        if hasattr(self.img_backbone, "init_weights"):
+            self.img_backbone.init_weights()
+        self.pts_bbox_head.init_weights()
+        for part in (self.img_backbone, self.img_neck):
+            part._drop_derived()
+        self._drop_derived()
+
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        """``strict=True`` forgives exactly the ``img_roi_head.*`` keys of a shipped checkpoint: nothing at eval reads them (module docstring)."""
+        kept = type(state_dict)((k, v) for k, v in state_dict.items() if not k.startswith("img_roi_head."))
+        if hasattr(state_dict, "_metadata"):
+            kept._metadata = state_dict._metadata
+        return super().load_state_dict(kept, strict=strict, **kw)
+
+    # ---- the reference's methods -------------------------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def extract_img_feat(self, img, len_queue=1, training_mode=False, gt_bboxes=None, centers2d=None, depths=None, prev_exists=None, ego_pose_inv=None,
+                         gumbel_noise=None):
+        """:84-243 at eval: ``(img_feats (B, N, C, h, w), token_masks, attn_scores, keep_idxes, drop_idxes)``.  ``prev_exists``: the Python bool of the scene-token
+        comparison (a tensor costs one host synchronisation)."""
+        if img is None:
+            return None, None, None, None, None
+        if training_mode or len_queue != 1:
+            raise NotImplementedError(f"{_NAME}: extract_img_feat with training_mode / len_queue != 1 is not implemented (inference only)")
+        B = img.size(0)
+        if img.dim() == 6:
+            img = img.flatten(1, 2)
+        if img.dim() == 5:
+            img = img.flatten(0, 1)                                                                                                     # :101-105
+        if ego_pose_inv is not None and ego_pose_inv.dim() == 4:
+            ego_pose_inv = ego_pose_inv.flatten(0, 1)
+        head, backbone = self.pts_bbox_head, self.img_backbone
+        if self.query_backbone_selection:
+            assert prev_exists is not None                                                                                               # :121
+            q = head.backbone_queries(backbone.pruning_num_queries, prev_exists, B)                                                     # :122-136
+            extra = {} if gumbel_noise is None else dict(gumbel_noise=gumbel_noise)
+            out = backbone(x=img, temp_queries=q["temp_queries"], temp_ref_points=q["temp_ref_points"], temp_vel=q["temp_vel"],
+                           temp_timestamp=q["temp_timestamp"], temp_ego_pose=q["temp_ego_pose"], prev_exists=q["prev_exists"], ego_pose_inv=ego_pose_inv, **extra)
+            token_masks, attn_scores, keep_idxes, drop_idxes, feats = out.token_masks, out.attn_scores, out.keep_idx, out.drop_idx, out.img_feats
+        else:
+            token_masks = attn_scores = keep_idxes = drop_idxes = None
+            feats = backbone(img)
+        feats = list(feats.values()) if isinstance(feats, dict) else list(feats)
+        V, _, h, w = feats[0].shape
+        rows, ld, dtype = head.img_feats_rows_buffer(B, V // B, h, w, feats[0].device)
+        outs = self.img_neck.forward_fanout(feats, rows, ld, dtype)                                                                     # :189-190, and the head's :629
+        BN, C, H, W = outs[self.position_level].size()
+        img_feats = outs[self.position_level].view(B, BN // B, C, H, W)                                                                  # :239
+        self._fanned = (img_feats, rows)
+        return img_feats, token_masks, attn_scores, keep_idxes, drop_idxes
+
+    def extract_feat(self, img, T, training_mode=False, gt_bboxes=None, centers2d=None, depths=None, prev_exists=None, ego_pose_inv=None):
+        return self.extract_img_feat(img, T, training_mode, gt_bboxes, centers2d, depths, prev_exists, ego_pose_inv)                   # :246-260
+
+    @torch.no_grad()
+    def prepare_location(self, img_metas, **data):
+        """:311-316 with ``misc.locations`` (:59-84): the normalised pixel centres, (B*N, h, w, 2).  (The head takes them and does not read them.)"""
+        pad_h, pad_w = img_metas[0]["pad_shape"][0][:2]
+        bs, n = data["img_feats"].shape[:2]
+        h, w = data["img_feats"].shape[-2:]
+        dev, s = data["img_feats"].device, self.stride
+        shifts_x = (torch.arange(0, s * w, step=s, dtype=torch.float32, device=dev) + s // 2) / pad_w
+        shifts_y = (torch.arange(0, h * s, step=s, dtype=torch.float32, device=dev) + s // 2) / pad_h
+        shift_y, shift_x = torch.meshgrid(shifts_y, shifts_x, indexing="ij")
+        location = torch.stack((shift_x.reshape(-1), shift_y.reshape(-1)), dim=1).reshape(h, w, 2)
+        return location[None].repeat(bs * n, 1, 1, 1)
+
+    def forward_roi_head(self, location, **data):
+        return {"topk_indexes": None}                                                                                                    # :319-320 (aux_2d_only at eval)
+
+    @torch.no_grad()
+    def simple_test_pts(self, img_metas, **data):
+        """:521-541.  The head runs on the rows the neck left in its workspace when ``data['img_feats']`` is the tensor :meth:`extract_img_feat` returned last;
+        any other tensor goes through the head's own transpose."""
+        location = None                                 # (prepare_location's tensor is what the head ignores: not built every frame)
+        topk_indexes = self.forward_roi_head(location, **data)["topk_indexes"]
+        if img_metas[0]["scene_token"] != self.prev_scene_token:
+            self.prev_scene_token = img_metas[0]["scene_token"]
+            data["prev_exists"] = data["img"].new_zeros(1)
+            self.pts_bbox_head.reset_memory()
+        else:
+            data["prev_exists"] = data["img"].new_ones(1)
+        fanned, self._fanned = self._fanned, None
+        if fanned is not None:                         # ... and the rows are still the head's (new weights or a move of the head alone give it a new workspace)
+            x = data["img_feats"]
+            fanned = x is fanned[0] and self.pts_bbox_head.img_feats_rows_buffer(x.shape[0], x.shape[1], x.shape[3], x.shape[4], x.device)[0] is fanned[1]
+        fanned = bool(fanned)
+        outs = self.pts_bbox_head(location, img_metas, topk_indexes, img_feats_rows=fanned, **data)
+        bbox_list = self.pts_bbox_head.get_bboxes(outs, img_metas)
+        return [bbox3d2result(bboxes, scores, labels) for bboxes, scores, labels in bbox_list]
+
+    @torch.no_grad()
+    def simple_test(self, img_metas, gt_bboxes=None, centers2d=None, depths=None, gumbel_noise=None, **data):
+        """:543-594: ``[dict(pts_bbox=dict(boxes_3d, scores_3d, labels_3d))]``.  What :meth:`extract_img_feat` returned for the frame -- the reference hands it to
+        ``token_selection_vis`` (:562-579) -- stays readable as ``self.last_frame`` until the next one."""
+        prev_exists = img_metas[0]["scene_token"] == self.prev_scene_token                                                               # :546-549, as the bool it is
+        img_feats, token_masks, _, keep_idxes, drop_idxes = self.extract_img_feat(data["img"], 1, gt_bboxes=gt_bboxes, centers2d=centers2d, depths=depths,
+                                                                                  prev_exists=prev_exists, ego_pose_inv=data["ego_pose_inv"], gumbel_noise=gumbel_noise)
+        data["img_feats"] = img_feats
+        self.last_frame = dict(img_feats=img_feats, token_masks=token_masks, keep_idxes=keep_idxes, drop_idxes=drop_idxes)
+        bbox_list = [dict() for _ in range(len(img_metas))]
+        for result_dict, pts_bbox in zip(bbox_list, self.simple_test_pts(img_metas, **data)):
+            result_dict["pts_bbox"] = pts_bbox
+        return bbox_list
+
+    def forward_test(self, img_metas, rescale=None, gt_bboxes=None, centers2d=None, depths=None, gumbel_noise=None, **data):
+        if not isinstance(img_metas, list):
+            raise TypeError("{} must be a list, but got {}".format("img_metas", type(img_metas)))                                       # :510-513
+        for key in data:                                                                                                                 # :514-518
+            data[key] = data[key][0][0].unsqueeze(0) if key != "img" else data[key][0]
+        return self.simple_test(img_metas[0], gt_bboxes, centers2d, depths, gumbel_noise=gumbel_noise, **data)
+
+    def forward_train(self, *args, **kwargs):
+        raise NotImplementedError(f"{_NAME}: forward_train is not implemented (inference only)")
+
+    def forward(self, return_loss=True, **data):
+        if return_loss:
+            raise NotImplementedError(f"{_NAME}: forward(return_loss=True) is not implemented (inference only); call forward(return_loss=False, ...)")
+        for key in ("gt_bboxes", "centers2d", "depths"):                                                                                 # :415-417
+            if key in data:
+                data[key] = list(zip(*data[key]))
+        return self.forward_test(**data)

@@ -173,18 +173,31 @@ class StreamPETRHead(_plan.DerivedState, nn.Module):
     memory_embedding, memory_reference_point, memory_timestamp, memory_egopose, memory_velo = map(_bank_attr, _BANK)
 
     # ---- forward ---------------------------------------------------------------------------------------------------------------------------------
+    def img_feats_rows_buffer(self, B, N, h, w, device=None):
+        """``(rows, ld, dtype)`` of :meth:`toc3d_amd.HeadTokenEmbedding.feat_workspace`: where a producer of token rows (``CPFPN.forward_fanout``) puts them for
+        ``forward(..., img_feats_rows=True)``."""
+        return self._tokens.feat_workspace(B, N, h, w, self.pc_range.device if device is None else device)
+
     @torch.no_grad()
-    def forward(self, memory_center, img_metas, topk_indexes=None, **data):
+    def forward(self, memory_center, img_metas, topk_indexes=None, img_feats_rows=False, **data):
         """``data``: ``img_feats`` (B, N, C, h, w), ``intrinsics`` / ``lidar2img`` (B, N, 4, 4), ``prev_exists`` (B,), ``timestamp`` (B,) f64, ``ego_pose`` /
         ``ego_pose_inv`` (B, 4, 4) -- what ``Petr3D.forward_pts_train`` / ``simple_test_pts`` pass (``petr3d.py:319-320``); ``img_metas[0]['pad_shape'][0]`` =
         (pad_h, pad_w[, 3]).  ``memory_center`` is accepted and left as it is (module docstring).  Returns ``dict(all_cls_scores (L, B, Q, num_classes),
-        all_bbox_preds (L, B, Q, code_size), dn_mask_dict=None)`` with Q = num_query + num_propagated and L = the decoder's layers (1 with ``levels="last"``)."""
+        all_bbox_preds (L, B, Q, code_size), dn_mask_dict=None)`` with Q = num_query + num_propagated and L = the decoder's layers (1 with ``levels="last"``).
+        ``img_feats_rows=True``: the token rows of ``img_feats`` already sit in :meth:`img_feats_rows_buffer` of its shape (a detector's neck put them there); the
+        tensor gives the shape and the device and is not read."""
         if self.training:
             raise RuntimeError(f"{_NAME}: training mode is not implemented (call .eval(): denoising queries and the losses are out of scope)")
         if topk_indexes is not None:
             raise NotImplementedError(f"{_NAME}: topk_indexes (token selection by img_roi_head) is not implemented; the shipped configs pass None at eval")
         x = data["img_feats"]
-        memory, pos_embed, _ = self._tokens(x, data["intrinsics"], data["lidar2img"], img_metas[0]["pad_shape"][0])
+        if img_feats_rows:
+            (B, N, C, h, w) = x.shape
+            if C != self.in_channels or not x.is_cuda:
+                raise ValueError(f"{_NAME}: img_feats {tuple(x.shape)} on {x.device} do not fit in_channels={self.in_channels} on the GPU")
+            memory, pos_embed, _ = self._tokens.forward_rows((B, N, h, w), data["intrinsics"], data["lidar2img"], img_metas[0]["pad_shape"][0], x.device)
+        else:
+            memory, pos_embed, _ = self._tokens(x, data["intrinsics"], data["lidar2img"], img_metas[0]["pad_shape"][0])
         bank = self._memory(x.device)
         bank.pre_update_memory(data)
         tgt, query_pos, reference_points, temp_memory, temp_pos, rec_ego_pose = self._queries.forward_from(bank)

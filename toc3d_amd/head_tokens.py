@@ -70,6 +70,23 @@ class HeadTokenEmbedding(StagedModule):
         return dict(pin=z(M, _ru(3 * D, 64)), cone_a=z(M, 64), cone=z(M, 8, f), h1=z(M, _ru(4 * E, 64)), feat=z(M, _ru(C, 64)), m1=z(M, _ru(E, 64)),
                     c1=z(M, _ru(E, 64)), mem_a=z(M, _ru(E, 64)), s1=z(M, _ru(E, 64)), pos=z(M, E, f), mem_raw=z(M, E, f), gam=z(M, E, f), bet=z(M, E, f), se=z(M, E, f))
 
+    def feat_workspace(self, B, N, h, w, device):
+        """``(rows, ld, dtype)``: this module's own token rows of the image features for a ``(B, N, h, w)`` -- the buffer ``toc3d_nchw_to_rows`` fills in
+        :meth:`forward` --, its leading dimension and the C ABI's dtype of its rows.  A producer that holds the features as rows (the neck:
+        :meth:`toc3d_amd.CPFPN.forward_fanout`) writes columns ``[0, in_channels)`` there; :meth:`forward_rows` then runs on them.  The buffer lives until
+        ``load_state_dict`` / ``.to()``; the padding columns are zero and stay zero."""
+        dev = torch.device(device)
+        with torch.cuda.device(dev):
+            W = self._workspace((B, N, h, w), dev)
+        return W["feat"], W["feat"].shape[1], self._packed["dts"].rows
+
+    @torch.no_grad()
+    def forward_rows(self, shape, intrinsics: torch.Tensor, lidar2img: torch.Tensor, pad_shape, device):
+        """:meth:`forward` on token rows that already sit in :meth:`feat_workspace` of ``shape`` = (B, N, h, w): no NCHW tensor is read, copied or
+        transposed (no ``toc3d_nchw_to_rows``); every other launch, and every bit, is :meth:`forward`'s."""
+        B, N, h, w = (int(v) for v in shape)
+        return self._forward(None, (B, N, h, w), torch.device(device), intrinsics, lidar2img, pad_shape)
+
     @torch.no_grad()
     def forward(self, img_feats: torch.Tensor, intrinsics: torch.Tensor, lidar2img: torch.Tensor, pad_shape):
         """img_feats (B, N, C, h, w) f32 (neck level 0, ``data['img_feats']`` :626); intrinsics / lidar2img (B, N, 4, 4);
@@ -79,7 +96,10 @@ class HeadTokenEmbedding(StagedModule):
         B, N, C, h, w = img_feats.shape
         if C != self.in_channels:
             raise ValueError(f"{self._NAME}: img_feats {tuple(img_feats.shape)} do not fit in_channels={self.in_channels}")
-        dev = img_feats.device
+        return self._forward(img_feats, (B, N, h, w), img_feats.device, intrinsics, lidar2img, pad_shape)
+
+    def _forward(self, img_feats, shape, dev, intrinsics, lidar2img, pad_shape):
+        (B, N, h, w), C = shape, self.in_channels
         with torch.cuda.device(dev):
             W = self._workspace((B, N, h, w), dev)
             P = self._packed
@@ -109,7 +129,8 @@ class HeadTokenEmbedding(StagedModule):
             linear(W["pin"], P["pe0"], W["h1"], 4 * E, 3 * D, relu=True)
             linear(W["h1"], P["pe2"], W["pos"], E, 4 * E, f32_out=True)
             # memory_embed :635
-            lib.call("toc3d_nchw_to_rows", rows, img_feats.float().contiguous(), W["feat"], W["feat"].shape[1], B * N, C, h * w, s)
+            if img_feats is not None:                   # (forward_rows: the rows are in W["feat"] already)
+                lib.call("toc3d_nchw_to_rows", rows, img_feats.float().contiguous(), W["feat"], W["feat"].shape[1], B * N, C, h * w, s)
             linear(W["feat"], P["me0"], W["m1"], E, C, relu=True)
             linear(W["m1"], P["me2"], W["mem_raw"], E, E, f32_out=True)
             # spatial_alignment :638

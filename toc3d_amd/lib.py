@@ -14,7 +14,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, os.environ.get("TOC3D_LIB", "libtoc3d_gfx950.so"))       # TOC3D_LIB: a development build beside the shipped one (library A/B runs)
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "toc3d.h")
 
-ABI_VERSION = 11                # == TOC3D_ABI_VERSION of include/toc3d.h (tests/test_cpu_abi.py cross-checks)
+ABI_VERSION = 11                # == TOC3D_ABI_VERSION of include/toc3d.h (tests/test_cpu_abi.py cross-checks): moves on a changed or removed entry point
+ABI_MINOR = 1                   # == TOC3D_ABI_MINOR: moves on an added entry point (1: toc3d_neck_rows_fanout); a library with a higher minor still binds
 F32, BF16, F32X3, F32X6, F32X3W, F32X3P, F32X3WO, F32X3WA = 0, 1, 2, 3, 4, 5, 6, 7          # F32X3: linear layers only -- f32 buffers, products as three bf16 MFMAs (include/toc3d.h)
 EPI_BIAS, EPI_RESIDUAL, EPI_SWIGLU, EPI_GELU, EPI_SWIGLU_STATS, EPI_RESIDUAL_LN, EPI_RESIDUAL_STATS, EPI_SWIGLU_STATS_LN, EPI_CONV3X3, EPI_QKV_ROPE = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 EPI_BIAS_RELU = 10              # relu(A.W^T + bias): served wherever EPI_BIAS is (a new value of an existing argument: the ABI version does not move)
@@ -118,6 +119,7 @@ _SIGS = {
     "toc3d_relu_inplace": "iplp",
     "toc3d_nchw_to_rows": "ippllllp",
     "toc3d_mln_apply": "ipppllpplp",
+    "toc3d_neck_rows_fanout": "iplppllllp",
     "toc3d_se_gate": "ppplp",
     "toc3d_memory_pre_update": "pppppppppplllllip",
     "toc3d_memory_scores": "pllpp",
@@ -170,11 +172,16 @@ def load():
         abi = lib.toc3d_abi_version()
     except AttributeError:
         abi = None
-    if abi != ABI_VERSION:
+    try:
+        lib.toc3d_abi_minor.restype = _I
+        minor = lib.toc3d_abi_minor()
+    except AttributeError:
+        minor = None                # a build from before the minor existed: it lacks the entry points added since
+    if abi != ABI_VERSION or minor is None or minor < ABI_MINOR:
         # checked BEFORE any symbol is bound: an older build (TOC3D_LIB) fails here with a message, not with a bare
         # AttributeError on the first entry point it lacks
-        raise RuntimeError(f"{LIB_PATH} reports ABI version {abi}, this package binds ABI {ABI_VERSION} (include/toc3d.h): "
-                           "rebuild the library (`make -C toc3d_amd/csrc`)")
+        raise RuntimeError(f"{LIB_PATH} reports ABI version {abi}.{'?' if minor is None else minor}, this package binds ABI {ABI_VERSION}.{ABI_MINOR} "
+                           "(include/toc3d.h): rebuild the library (`make -C toc3d_amd/csrc`)")
     lib.toc3d_last_error.restype = ctypes.c_char_p
     lib.toc3d_attn_rot_q_scale.restype = _F
     lib.toc3d_attn_rot_q_scale.argtypes = [_I64]

@@ -69,6 +69,19 @@ class CPFPN(DerivedState, nn.Module):
 
     @torch.no_grad()
     def forward(self, inputs):
+        return self._forward(inputs, None)
+
+    @torch.no_grad()
+    def forward_fanout(self, inputs, rows, ld_rows, dtype):
+        """``forward`` with the conv rows fanned out (``toc3d_neck_rows_fanout`` in place of ``toc3d_nhwc_to_nchw``): the same NCHW outputs, bit for bit, and
+        in the same launch the level-0 token rows ``rows`` [V*h*w, ld_rows] in the C ABI's ``dtype`` (``lib.BF16`` / ``F32`` / ``F32X3P``) -- what
+        ``toc3d_nchw_to_rows`` would make of the NCHW tensor; columns from ``out_channels`` on are left as they are.  ``rows`` is the consumer's own buffer
+        (:meth:`toc3d_amd.HeadTokenEmbedding.feat_workspace`): a recorded plan names it, like the input."""
+        if not (isinstance(rows, torch.Tensor) and rows.is_cuda and rows.dim() == 2 and rows.is_contiguous() and rows.shape[1] == ld_rows):
+            raise ValueError("toc3d_amd.CPFPN.forward_fanout: rows must be a contiguous 2-D device tensor whose row length is ld_rows")
+        return self._forward(inputs, (rows, int(ld_rows), int(dtype)))
+
+    def _forward(self, inputs, fan):
         assert len(inputs) == len(self.in_channels)
         feat = inputs[0]
         if not feat.is_cuda:
@@ -113,16 +126,25 @@ class CPFPN(DerivedState, nn.Module):
                 gemm.linear(self, lib.EPI_RESIDUAL, a, P["w_lat"], P["b_lat"], ws["lat"], M, Co, Kl)
                 lib.call("toc3d_im2col_3x3", dt, ws["lat"], ws["col"], Kf, V, h, w, Co, s)
                 gemm.linear(self, lib.EPI_RESIDUAL, ws["col"], P["w_fpn"], P["b_fpn"], ws["o0"], M, Co, Kf)
-            lib.call("toc3d_nhwc_to_nchw", ws["o0"], ws["out0"], V, h * w, Co, s)
+            if fan is None:
+                lib.call("toc3d_nhwc_to_nchw", ws["o0"], ws["out0"], V, h * w, Co, s)
+            else:
+                lib.call("toc3d_neck_rows_fanout", fan[2], ws["o0"], Co, ws["out0"], fan[0], fan[1], V, h * w, Co, s)
 
         # The launch sequence names the input buffer: it can be recorded (and replayed with one C call) only for an input that sits
         # at a fixed address and is read in place -- the toc3d_amd backbone's own output buffer.  Anything else launches eagerly.
         in_place = nhwc.data_ptr() == feat.data_ptr() and feat.dtype == torch.float32
+        if fan is not None and fan[0].shape[0] != M:
+            raise ValueError(f"toc3d_amd.CPFPN.forward_fanout: rows has {fan[0].shape[0]} rows, the frame has {M} tokens")
         if in_place:
             states = ws.setdefault("launch", {})
-            if nhwc.data_ptr() not in states and len(states) >= 4:
+            skey = nhwc.data_ptr() if fan is None else (nhwc.data_ptr(), fan[0].data_ptr(), fan[1], fan[2])       # the fanned-out frame names the rows buffer too
+            if skey not in states and len(states) >= 4:
                 states.pop(next(iter(states)))
-            run_frame(states.setdefault(nhwc.data_ptr(), {}), self.launch_mode, 1, frame, self._stream_pool)
+            state = states.setdefault(skey, {})
+            if fan is not None:
+                state["rows"] = fan[0]                  # a recorded plan points into it: it lives as long as the plan does, whatever its owner does
+            run_frame(state, self.launch_mode, 1, frame, self._stream_pool)
         else:
             run_frame({}, "eager", 1, frame, self._stream_pool)
         out0 = ws["out0"] if self.alias_outputs else ws["out0"].clone()

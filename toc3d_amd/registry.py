@@ -1,5 +1,6 @@
 """Registry surface: ``ToC3DEVAViT`` / ``EVA_ViT`` on mmdet's BACKBONES, ``CPFPN`` on NECKS, ``PETRTemporalTransformer`` on TRANSFORMER, ``NMSFreeCoder`` on
-BBOX_CODERS, ``StreamPETRHead`` on HEADS (the reference: ``@HEADS.register_module()``, ``dense_heads/streampetr_head.py:32``).
+BBOX_CODERS, ``StreamPETRHead`` on HEADS (the reference: ``@HEADS.register_module()``, ``dense_heads/streampetr_head.py:32``), ``Petr3D`` on DETECTORS
+(``@DETECTORS.register_module()``, ``detectors/petr3d.py:23``).
 
 The reference registers its classes with ``@BACKBONES.register_module()`` (``toc3d_eva_vit.py:25``,
 ``eva_vit.py:270``), ``@NECKS.register_module()`` (``cp_fpn.py:15``) and ``@TRANSFORMER.register_module()``
@@ -50,16 +51,21 @@ try:  # pragma: no cover
     from mmdet.models.builder import HEADS
 except Exception:  # noqa: BLE001
     HEADS = _ShimRegistry("head")
+try:  # pragma: no cover
+    from mmdet.models.builder import DETECTORS
+except Exception:  # noqa: BLE001
+    DETECTORS = _ShimRegistry("detector")
 
 
 def register_all():
     from .backbone import EVA_ViT, ToC3DEVAViT
     from .decoder import PETRTemporalTransformer
+    from .detector import Petr3D
     from .head import StreamPETRHead
     from .head_outputs import NMSFreeCoder
     from .neck import CPFPN
     for reg, cls in ((BACKBONES, ToC3DEVAViT), (BACKBONES, EVA_ViT), (NECKS, CPFPN), (TRANSFORMER, PETRTemporalTransformer), (BBOX_CODERS, NMSFreeCoder),
-                     (HEADS, StreamPETRHead)):
+                     (HEADS, StreamPETRHead), (DETECTORS, Petr3D)):
         try:
             reg.register_module(name=cls.__name__, force=True, module=cls)
         except TypeError:
@@ -84,3 +90,7 @@ def build_bbox_coder(cfg, **kw):
 
 def build_head(cfg, **kw):
     return HEADS.build(cfg, **kw) if isinstance(HEADS, _ShimRegistry) else HEADS.build(dict(cfg, **kw))
+
+
+def build_detector(cfg, **kw):
+    return DETECTORS.build(cfg, **kw) if isinstance(DETECTORS, _ShimRegistry) else DETECTORS.build(dict(cfg, **kw))

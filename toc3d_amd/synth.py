@@ -597,3 +597,66 @@ def head_inputs(sizes: dict = None, shape: dict = None, seed: int = 0):
         data.update(img_feats=tok["feats"], intrinsics=tok["intrinsics"], lidar2img=tok["lidar2img"])
         frames.append(data)
     return dict(frames=frames, img_metas=[dict(pad_shape=[(h * 16, w * 16, 3)]) for _ in range(B)])
+
+
+# ---- the assembled detector (toc3d_amd.Petr3D) -------------------------------------------------------------------------------------------------------------
+# the sizes of the detector fixture (tools/gen_golden_detector.py): the tiny backbone at 6 x 320 x 800 (the shape every tiny backbone fixture is proven at), the
+# tiny neck, and a head whose topk_proposals equals the backbone's pruning_num_queries, so the backbone reads real proposals from frame 1 on
+DETECTOR_TINY = dict(backbone="toc3d_tiny", neck="tiny", hw=(320, 800), views=6, frames=4, new_scene_at=3,
+                     head=dict(in_channels=32, num_query=72, memory_len=160, topk_proposals=64, num_propagated=24,
+                               decoder=dict(embed_dims=256, num_heads=8, feedforward_channels=128, num_layers=2), max_num=30, post_center_range=None))
+DETECTOR_FULL = dict(backbone="toc3d_faster", neck="full", hw=(320, 800), views=6, frames=2, new_scene_at=None, head=HEAD_FULL)      # the shipped sizes (ToC3D_faster.py)
+
+
+def detector_cfg(sizes: dict = None) -> dict:
+    """The ``model=dict(type='Petr3D', ...)`` block of the shipped configs (projects/configs/ToC3D/ToC3D_faster.py:35-166) at the given sizes (default: as
+    shipped), every key of the block: the backbone's ``token_selection_loss``, ``img_roi_head=dict(type='FocalHead', ...)`` and ``train_cfg`` included."""
+    from . import configs
+    sizes = DETECTOR_FULL if sizes is None else sizes
+    pcr = list(PC_RANGE)
+    backbone = dict(configs.get(sizes["backbone"]), token_selection_loss=dict(type="TokenSelectionLoss", semantic_loss=dict(type="GaussianFocalLoss", loss_weight=5.0)))
+    neck = dict(configs.CPFPN_CFG if sizes["neck"] == "full" else configs.CPFPN_TINY)
+    roi = dict(type="FocalHead", num_classes=10, in_channels=neck["out_channels"], loss_cls2d=dict(type="QualityFocalLoss", use_sigmoid=True, beta=2.0, loss_weight=2.0),
+               loss_centerness=dict(type="GaussianFocalLoss", reduction="mean", loss_weight=1.0), loss_bbox2d=dict(type="L1Loss", loss_weight=5.0),
+               loss_iou2d=dict(type="GIoULoss", loss_weight=2.0), loss_centers2d=dict(type="L1Loss", loss_weight=10.0),
+               train_cfg=dict(assigner2d=dict(type="HungarianAssigner2D", cls_cost=dict(type="FocalLossCost", weight=2.0),
+                                              reg_cost=dict(type="BBoxL1Cost", weight=5.0, box_format="xywh"), iou_cost=dict(type="IoUCost", iou_mode="giou", weight=2.0),
+                                              centers2d_cost=dict(type="BBox3DL1Cost", weight=10.0))))
+    train_cfg = dict(pts=dict(grid_size=[512, 512, 1], voxel_size=[0.2, 0.2, 8], point_cloud_range=pcr, out_size_factor=4,
+                              assigner=dict(type="HungarianAssigner3D", cls_cost=dict(type="FocalLossCost", weight=2.0), reg_cost=dict(type="BBox3DL1Cost", weight=0.25),
+                                            iou_cost=dict(type="IoUCost", weight=0.0), pc_range=pcr)))
+    return dict(type="Petr3D", num_frame_head_grads=1, num_frame_backbone_grads=1, num_frame_losses=1, use_grid_mask=True, img_backbone=backbone, img_neck=neck,
+                img_roi_head=roi, pts_bbox_head=head_cfg(sizes["head"]), train_cfg=train_cfg)
+
+
+def detector_state_dict(sizes: dict = None, seed: int = 0):
+    """Seeded weights of the whole detector under the reference's names: ``img_backbone.*`` (``make_state_dict``), ``img_neck.*`` (``neck_state_dict``) and
+    ``pts_bbox_head.*`` (``head_state_dict``) -- the same tensors those helpers give the parts."""
+    from . import configs
+    sizes = DETECTOR_FULL if sizes is None else sizes
+    sd = OrderedDict()
+    sd.update(("img_backbone." + k, v) for k, v in make_state_dict(configs.get(sizes["backbone"]), seed=seed).items())
+    sd.update(("img_neck." + k, v) for k, v in neck_state_dict(configs.CPFPN_CFG if sizes["neck"] == "full" else configs.CPFPN_TINY, seed=seed).items())
+    sd.update(("pts_bbox_head." + k, v) for k, v in head_state_dict(sizes["head"], seed=seed).items())
+    return sd
+
+
+def detector_inputs(sizes: dict = None, seed: int = 0):
+    """Per frame what ``Petr3D.simple_test`` takes for one sample (B = 1): ``img_metas`` (``scene_token``, ``pad_shape``), ``data`` -- ``img`` (1, N, 3, H, W),
+    ``intrinsics`` / ``lidar2img`` (1, N, 4, 4), f64 ``timestamp`` (1,), ``ego_pose`` / ``ego_pose_inv`` (1, 4, 4) -- and ``gumbel``, three (N, T, 2) draws.  Frame 0
+    starts scene "a"; frame ``new_scene_at`` starts scene "b"."""
+    from . import configs
+    sizes = DETECTOR_FULL if sizes is None else sizes
+    cfg, (H, W), N, F = configs.get(sizes["backbone"]), sizes["hw"], sizes["views"], sizes["frames"]
+    h, w = H // 16, W // 16
+    mem = memory_inputs(dict(num_propagated=sizes["head"]["num_propagated"], embed_dims=8), 1, sizes["head"]["num_query"], 10, F, seed=seed)
+    frames = []
+    for f in range(F):
+        img = make_inputs(cfg, 1, N, (H, W), seed=1000 * seed + f)
+        tok = head_tokens_inputs(dict(in_channels=1, stride=16), 1, N, h, w, seed=100 * seed + f)
+        d = mem["frames"][f]["data"]
+        data = dict(img=img["x"][None], intrinsics=tok["intrinsics"], lidar2img=tok["lidar2img"], timestamp=d["timestamp"], ego_pose=d["ego_pose"],
+                    ego_pose_inv=d["ego_pose_inv"])
+        scene = "b" if sizes["new_scene_at"] is not None and f >= sizes["new_scene_at"] else "a"
+        frames.append(dict(img_metas=[dict(scene_token=scene, pad_shape=[(H, W, 3)])], data=data, gumbel=img["gumbel"]))
+    return frames
