@@ -864,7 +864,7 @@ class ToC3DEVAViT(_BackboneBase):
         # loop): both staging buffers exist, the plan key carries which one a recording used.
         m["stage"] = dict(tq=torch.empty(B, Q, QUERY_DIM, **f32), rp=torch.empty(B, Q, 3, **f32), vel=torch.empty(B, Q, 2, **f32),
                           ts32=torch.empty(B, Q, 1, **f32), ts64=torch.empty(B, Q, 1, dtype=torch.float64, device=dev),
-                          pose=torch.empty(B, Q, 4, 4, **f32), inv=torch.empty(B, 4, 4, **f32),
+                          pose=torch.empty(B, Q, 4, 4, **f32), inv=torch.empty(B, 4, 4, **f32), new=torch.zeros(B, **f32),
                           gumbel_all=torch.empty(ns, V * T, 2, **f32), rng=self._rng_state(dev))
         m["stage"]["gumbel"] = [m["stage"]["gumbel_all"][s_] for s_ in range(ns)]      # one buffer: the device-side draw fills all stages in one launch
         m["groups"] = []
@@ -918,9 +918,11 @@ class ToC3DEVAViT(_BackboneBase):
     def _block_done(self, i, plan, carried):
         """After block ``i`` of one view group was issued (``carried``: its update of x is still pending in the compact rows).  No-op here."""
 
-    def _score_stage(self, ex, lane, side, prep_lane, st, plan, P, prev_exists, gumbel):
+    def _score_stage(self, ex, lane, side, prep_lane, st, plan, P, prev_exists, gumbel, frame_new=None):
         """One scorer stage of one view group (toc3d_eva_vit.py:264-285) on ``lane``; work that does not gate the block chain
-        (image-level ranking, the selection of the window type the next block does not use) goes to the group's ``side`` lane."""
+        (image-level ranking, the selection of the window type the next block does not use) goes to the group's ``side`` lane.
+        ``frame_new`` (a mixed step: f32 flags of this group's frames, device memory): the query path scores every row, then the
+        static chain runs on every row and its last launch overwrites the rows of the flagged frames only."""
         s = lib.stream_ptr()
         q = P["scorers"][st]
         C, dt = self.embed_dim, self._dt
@@ -935,7 +937,7 @@ class ToC3DEVAViT(_BackboneBase):
             f0 = plan["frame0"]
             lib.call("toc3d_score_tokens", x, C, mask_prev, plan["prep"]["wc"][st][f0:f0 + B], plan["prep"]["bc"][st][f0:f0 + B], g, V, T, V // B,
                      pred, score, mask, s)
-        else:
+        if not prev_exists or frame_new is not None:
             # ScoreBasedTokenSelector.score (toc3d_utils.py:114-129); the reference also evaluates the motion-aware
             # queries here and discards them (:376-385) -- skipped, no observable effect
             t_act, u1, u2 = plan["att"], plan["u1"], plan["u2"]
@@ -944,7 +946,10 @@ class ToC3DEVAViT(_BackboneBase):
             lib.call("toc3d_global_mean_half", dt, t_act, C, V, T, C, s)
             self._linear(lib.EPI_GELU, t_act, q["w_o0"], q["b_o0"], u1, M, C // 2, C)
             self._linear(lib.EPI_GELU, u1, q["w_o2"], q["b_o2"], u2, M, C // 4, q["w_o2"].shape[1])
-            lib.call("toc3d_score_head", dt, u2, u2.shape[1], C // 4, q["w_o4"], q["b_o4"], g, M, pred, score, mask, s)
+            if frame_new is None:
+                lib.call("toc3d_score_head", dt, u2, u2.shape[1], C // 4, q["w_o4"], q["b_o4"], g, M, pred, score, mask, s)
+            else:                                                   # a group holds B whole frames, or (B = 1) part of one: M // B rows per flag
+                lib.call("toc3d_score_head_frames", dt, u2, u2.shape[1], C // 4, q["w_o4"], q["b_o4"], g, frame_new, M // B, M, pred, score, mask, s)
         self._stage_override(st, plan, score, mask)
 
         def topk(L):
@@ -1044,8 +1049,19 @@ class ToC3DEVAViT(_BackboneBase):
         dev = x.device
         V = x.shape[0]
         # the reference's detector passes a Python bool (petr3d.py:122,155); a tensor costs one host sync per frame
-        prev = bool(prev_exists.bool().flatten()[0].item()) if isinstance(prev_exists, torch.Tensor) else bool(prev_exists)
         B = temp_queries.shape[0] if temp_queries is not None else 1
+        mixed = None                                             # a list / tuple of B Python bools: one per frame (B camera streams stepped together)
+        if isinstance(prev_exists, (list, tuple)):
+            flags = tuple(bool(p) for p in prev_exists)
+            if temp_queries is None:
+                B = len(flags)
+            if len(flags) != B:
+                raise ValueError(f"prev_exists has {len(flags)} entries for {B} frames")
+            prev = any(flags)                                    # all True / all False: the two paths of the single bool, launch for launch
+            if prev and not all(flags):
+                mixed = flags                                    # some frames start a scene, the others continue: the third recorded mode
+        else:
+            prev = bool(prev_exists.bool().flatten()[0].item()) if isinstance(prev_exists, torch.Tensor) else bool(prev_exists)
         assert V % B == 0
         ns = len(self.pruning_loc)
         key = (tuple(x.shape), x.dtype, B, self.view_groups)
@@ -1077,12 +1093,19 @@ class ToC3DEVAViT(_BackboneBase):
                 put(sg["ts64"], temp_timestamp, torch.float64)
             else:
                 put(sg["ts32"], temp_timestamp)
+            if mixed is not None:
+                # which frames are new, as f32 in device memory: the recorded mixed frame serves every pattern.  One small tensor per pattern seen,
+                # made once (at most 2^B - 2 of them), so a step costs no host-to-device copy of its own
+                pats = plan.setdefault("new_patterns", {})
+                if mixed not in pats:
+                    pats[mixed] = torch.tensor([0.0 if p else 1.0 for p in mixed], dtype=torch.float32, device=dev)
+                staged.append((sg["new"], pats[mixed]))
         draw = gumbel_noise is None and ns > 0               # F.gumbel_softmax's own sampling (toc3d_utils.py:147), drawn inside the frame: toc3d_gumbel_noise
         for st in range(ns):
             if not draw:
                 staged.append((sg["gumbel"][st], gumbel_noise[st].to(device=dev, dtype=torch.float32).reshape(V * T, 2).contiguous()))
         lib.copy_segments(staged, s0)
-        if not prev:
+        if not prev or mixed is not None:
             for gp in groups:                                    # first-frame scorer scratch
                 if gp["u1"] is None:
                     C = self.embed_dim
@@ -1125,7 +1148,8 @@ class ToC3DEVAViT(_BackboneBase):
                     with ex.lane(g):
                         if i in self.pruning_loc:
                             r0, r1 = gp["v0"] * T, (gp["v0"] + gp["nv"]) * T
-                            self._score_stage(ex, g, side_of(g), prep_lane, st, gp, P, prev, [gm[r0:r1] for gm in sg["gumbel"]])
+                            new = None if mixed is None else sg["new"][gp["frame0"]:gp["frame0"] + gp["B"]]
+                            self._score_stage(ex, g, side_of(g), prep_lane, st, gp, P, prev, [gm[r0:r1] for gm in sg["gumbel"]], new)
                         if self._accelerated(i):
                             self._accel_block(ex, g, side_of(g), i, st, gp, P, carry_in=cin, carry_out=cout)
                         else:
@@ -1147,7 +1171,7 @@ class ToC3DEVAViT(_BackboneBase):
         if self._instrumented:
             frame(EagerExec(2 * G + 1, self._stream_pool))
         else:
-            self._run_frame(plan, 2 * G + 1, frame, variant=(prev, ts_key, draw))
+            self._run_frame(plan, 2 * G + 1, frame, variant=("mixed" if mixed is not None else prev, ts_key, draw))
         h, w = plan["h"], plan["w"]
         cl = (lambda t: t) if self.alias_outputs else (lambda t: t.clone())
         masks = [cl(plan["mask"][s]).view(V, h, w, 1) for s in range(ns)]

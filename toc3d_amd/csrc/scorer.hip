@@ -12,6 +12,7 @@
 // No fast-math intrinsics: sin/cos arguments reach 5e10 and need full range reduction.
 #include "capi.h"
 #include "common.h"
+#include "../../include/toc3d_streams.h"
 
 namespace {
 
@@ -350,13 +351,11 @@ __global__ __launch_bounds__(256) void score_tokens_kernel(const float* __restri
     if (lane == 0) score_tail(d0 + bc[b * 2], d1 + bc[b * 2 + 1], gumbel, row, pred, score, mask_out);
 }
 
+// one wave per row: Linear(kdim -> 2) in lane order, then the tail (shared by the two kernels below: same bits for a row)
 template <typename T>
-__global__ __launch_bounds__(256) void score_head_kernel(const T* __restrict__ f, int64_t ld, int kdim, const float* __restrict__ w,
-                                                         const float* __restrict__ b, const float* __restrict__ gumbel, int64_t M,
-                                                         float* __restrict__ pred, float* __restrict__ score, float* __restrict__ mask_out) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + wave;
-    if (row >= M) return;
+TOC3D_DEV void score_head_row(const T* __restrict__ f, int64_t ld, int kdim, const float* __restrict__ w, const float* __restrict__ b,
+                              const float* __restrict__ gumbel, int64_t row, int lane, float* __restrict__ pred, float* __restrict__ score,
+                              float* __restrict__ mask_out) {
     float d0 = 0.f, d1 = 0.f;
     for (int c = lane * 8; c < kdim; c += 512) {
         float v[8];
@@ -370,6 +369,30 @@ __global__ __launch_bounds__(256) void score_head_kernel(const T* __restrict__ f
     d0 = wave_sum(d0);
     d1 = wave_sum(d1);
     if (lane == 0) score_tail(d0 + b[0], d1 + b[1], gumbel, row, pred, score, mask_out);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void score_head_kernel(const T* __restrict__ f, int64_t ld, int kdim, const float* __restrict__ w,
+                                                         const float* __restrict__ b, const float* __restrict__ gumbel, int64_t M,
+                                                         float* __restrict__ pred, float* __restrict__ score, float* __restrict__ mask_out) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + wave;
+    if (row >= M) return;
+    score_head_row(f, ld, kdim, w, b, gumbel, row, lane, pred, score, mask_out);
+}
+
+// ... for the rows of the frames whose flag is set only (row r belongs to frame r / rows_per_frame); the other rows are neither read nor written.
+// The flag is the same for the whole wave (one row per wave): the branch does not diverge.
+template <typename T>
+__global__ __launch_bounds__(256) void score_head_frames_kernel(const T* __restrict__ f, int64_t ld, int kdim, const float* __restrict__ w,
+                                                                const float* __restrict__ b, const float* __restrict__ gumbel,
+                                                                const float* __restrict__ frame_new, int64_t rows_per_frame, int64_t M,
+                                                                float* __restrict__ pred, float* __restrict__ score, float* __restrict__ mask_out) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + wave;
+    if (row >= M) return;
+    if (frame_new[row / rows_per_frame] == 0.f) return;
+    score_head_row(f, ld, kdim, w, b, gumbel, row, lane, pred, score, mask_out);
 }
 
 // columns [C/2, C) of each view <- mean over the view's tokens (toc3d_utils.py:125-126)
@@ -603,6 +626,32 @@ int toc3d_score_head(int dtype, const void* f, int64_t ld, int64_t kdim, const f
         toc3d_launch(score_head_kernel<float>, grid, dim3(256), 0, as_stream(stream), (const float*)f, ld, (int)kdim, w, b, gumbel, M, pred, score, mask_out);
     else { toc3d_set_error("toc3d_score_head: bad dtype"); return TOC3D_ERR_ARG; }
     TOC3D_LAUNCH_CHECK("toc3d_score_head");
+    return TOC3D_OK;
+}
+
+int toc3d_streams_abi(void) { return TOC3D_STREAMS_ABI; }
+
+int toc3d_score_head_frames(int dtype, const void* f, int64_t ld, int64_t kdim, const float* w, const float* b, const float* gumbel,
+                            const float* frame_new, int64_t rows_per_frame, int64_t M, float* pred, float* score, float* mask_out,
+                            toc3d_stream_t stream) {
+    TOC3D_REQUIRE(f && w && b && frame_new && pred && score && mask_out, "toc3d_score_head_frames: null buffer");
+    TOC3D_REQUIRE(kdim % 8 == 0 && ld >= kdim && ld % 8 == 0, "toc3d_score_head_frames: kdim / ld must be multiples of 8");
+    TOC3D_REQUIRE(kdim >= 0 && kdim <= kMaxCount, "toc3d_score_head_frames: bad kdim (counted in 32 bits)");
+    TOC3D_REQUIRE(aligned16(f), "toc3d_score_head_frames: f must be 16-byte aligned");
+    TOC3D_REQUIRE(dtype == TOC3D_BF16 || dtype == TOC3D_F32, "toc3d_score_head_frames: bad dtype");
+    TOC3D_REQUIRE(rows_per_frame > 0, "toc3d_score_head_frames: rows_per_frame must be positive");
+    if (M <= 0) return TOC3D_OK;
+    // whole frames only: frame_new has M / rows_per_frame entries, and row / rows_per_frame stays inside it
+    TOC3D_REQUIRE(M % rows_per_frame == 0, "toc3d_score_head_frames: M must be a multiple of rows_per_frame");
+    TOC3D_REQUIRE(M <= 4 * kMaxCount, "toc3d_score_head_frames: too many rows (ceil(M / 4) is counted in 32 bits)");
+    dim3 grid((unsigned)((M + 3) / 4));
+    if (dtype == TOC3D_BF16)
+        toc3d_launch(score_head_frames_kernel<bf16_t>, grid, dim3(256), 0, as_stream(stream), (const bf16_t*)f, ld, (int)kdim, w, b, gumbel, frame_new,
+                     rows_per_frame, M, pred, score, mask_out);
+    else
+        toc3d_launch(score_head_frames_kernel<float>, grid, dim3(256), 0, as_stream(stream), (const float*)f, ld, (int)kdim, w, b, gumbel, frame_new,
+                     rows_per_frame, M, pred, score, mask_out);
+    TOC3D_LAUNCH_CHECK("toc3d_score_head_frames");
     return TOC3D_OK;
 }
 

@@ -19,7 +19,9 @@ Differences to the reference, by design:
 * the ``pts_*`` parts and ``img_rpn_head`` are accepted as ``None`` only; backbones and necks other than this package's are refused at construction;
 * ``prev_exists`` reaches the backbone as the Python bool the scene-token comparison already is: no host synchronisation;
 * ``extract_img_feat(img)`` does not squeeze the caller's ``img`` in place (:102 does);
-* extra keywords: ``precision`` (handed to the three parts), ``gumbel_noise=`` on ``simple_test`` / ``extract_img_feat`` (handed to the backbone).
+* extra keywords: ``precision`` (handed to the three parts), ``gumbel_noise=`` on ``simple_test`` / ``extract_img_feat`` (handed to the backbone);
+* extra methods: ``simple_test_streams`` / ``reset_streams`` -- B independent camera streams per step, scene changes per stream (``extract_img_feat`` then takes
+  ``prev_exists`` as a list of B bools).
 Derived state (packed weights, workspaces, plans, the bank) belongs to the parts; ``load_state_dict``, ``.to()`` and ``init_weights()`` drop it, and
 ``prev_scene_token`` with it.  No CPU path.
 """
@@ -98,7 +100,7 @@ class Petr3D(_plan.DerivedState, nn.Module):
     with_img_neck, with_img_roi_head, with_pts_bbox = True, False, True
 
     # ---- derived state: the parts keep their own; the detector's is the scene it is in and the tensor whose rows sit in the head's workspace --------------
-    _DERIVED = dict(prev_scene_token=None, _fanned=None, last_frame=None)
+    _DERIVED = dict(prev_scene_token=None, prev_scene_tokens=None, _fanned=None, last_frame=None)
 
     def train(self, mode=True):
         if mode:
@@ -188,6 +190,10 @@ class Petr3D(_plan.DerivedState, nn.Module):
             self.pts_bbox_head.reset_memory()
         else:
             data["prev_exists"] = data["img"].new_ones(1)
+        return self._pts_results(img_metas, location, topk_indexes, data)
+
+    def _pts_results(self, img_metas, location, topk_indexes, data):
+        """The head on ``data`` (``prev_exists`` decided by the caller) and the decoded lists, one per sample."""
         fanned, self._fanned = self._fanned, None
         if fanned is not None:                         # ... and the rows are still the head's (new weights or a move of the head alone give it a new workspace)
             x = data["img_feats"]
@@ -210,6 +216,43 @@ class Petr3D(_plan.DerivedState, nn.Module):
         for result_dict, pts_bbox in zip(bbox_list, self.simple_test_pts(img_metas, **data)):
             result_dict["pts_bbox"] = pts_bbox
         return bbox_list
+
+    # ---- several camera streams per step (no counterpart in the reference, whose simple_test compares ONE scene token) ---------------------------------------
+    @torch.no_grad()
+    def simple_test_streams(self, img_metas, gumbel_noise=None, **data):
+        """One step of B independent camera streams (several vehicles, or several scenes of an offline evaluation) in one forward of every part.
+        ``img_metas``: a list of B dicts, stream b's at index b; ``data['img']`` (B, N, 3, H, W) -- or the uint8 form the backbone takes, (B, N, H0, W0, 3) --
+        and every other key with a leading B (``intrinsics`` / ``lidar2img`` (B, N, 4, 4), ``timestamp`` (B,), ``ego_pose`` / ``ego_pose_inv`` (B, 4, 4)).
+        Returns a list of B ``dict(pts_bbox=dict(boxes_3d, scores_3d, labels_3d))``; ``self.last_frame`` as after :meth:`simple_test`, with a leading B.
+
+        Each stream's scene token is compared with that stream's previous one (``self.prev_scene_tokens``, derived state like ``prev_scene_token``): the
+        backbone gets the list of B Python bools (a step in which some streams start a scene and others continue is ONE forward), the head the (B,) tensor,
+        whose zeros make ``pre_update_memory`` clear exactly those samples of the bank.  ``reset_memory()`` is called only when every stream is new -- and
+        when B differs from the previous step's: a change of B restarts EVERY stream (the bank is allocated per batch size; stream b of the new step is not
+        known to be stream b of the old one).  Stream b is what a B = 1 detector stepped through :meth:`simple_test` computes for it."""
+        B = len(img_metas)
+        tokens = [m["scene_token"] for m in img_metas]
+        before = self.prev_scene_tokens
+        if before is None or len(before) != B:
+            before = [None] * B
+        prev = [p is not None and t == p for t, p in zip(tokens, before)]
+        self.prev_scene_tokens = tokens
+        self.prev_scene_token = None                    # (a later simple_test starts a scene: the two forms are not meant to be interleaved on one detector)
+        if not any(prev):
+            self.pts_bbox_head.reset_memory()
+        img_feats, token_masks, _, keep_idxes, drop_idxes = self.extract_img_feat(data["img"], 1, prev_exists=prev, ego_pose_inv=data["ego_pose_inv"],
+                                                                                  gumbel_noise=gumbel_noise)
+        data["img_feats"] = img_feats
+        self.last_frame = dict(img_feats=img_feats, token_masks=token_masks, keep_idxes=keep_idxes, drop_idxes=drop_idxes)
+        data["prev_exists"] = torch.tensor([1.0 if p else 0.0 for p in prev], dtype=torch.float32, device=data["img"].device)
+        return [dict(pts_bbox=r) for r in self._pts_results(img_metas, None, None, data)]
+
+    def reset_streams(self, indices=None):
+        """Forget the scene tokens of the streams ``indices`` (default: all): their next step starts a scene whatever token it carries."""
+        if self.prev_scene_tokens is None:
+            return
+        for b in range(len(self.prev_scene_tokens)) if indices is None else indices:
+            self.prev_scene_tokens[b] = None
 
     def forward_test(self, img_metas, rescale=None, gt_bboxes=None, centers2d=None, depths=None, gumbel_noise=None, **data):
         if not isinstance(img_metas, list):

@@ -144,13 +144,20 @@ _SIGS = {
     "toc3d_plan_run": "pp",
 }
 _CT = {"p": _P, "l": _I64, "i": _I, "f": _F, "L": ctypes.c_uint64}
+# include/toc3d_streams.h (several camera streams per step), in a table of its own: _SIGS is include/toc3d.h one to one, whose minor stays where the tests of
+# the 11.1 surface pin it (the header folds into toc3d.h at 11.2).  Bound at first use (call()): a library built before the header existed lacks the symbols.
+STREAMS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "toc3d_streams.h")
+STREAMS_ABI = 1                 # == TOC3D_STREAMS_ABI
+_STREAMS_SIGS = {
+    "toc3d_score_head_frames": "ipllppppllpppp",
+}
 
 _lib = None
 
 
-def header_text() -> str:
-    """include/toc3d.h without comments."""
-    return re.sub(r"/\*.*?\*/", "", open(HEADER_PATH).read(), flags=re.S)
+def header_text(path: str = HEADER_PATH) -> str:
+    """include/toc3d.h (or another header of the library) without comments."""
+    return re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
 
 
 def header_functions():
@@ -213,9 +220,28 @@ def _conv(a):
     return a
 
 
+def _bind_streams(lib):
+    """The entry points of include/toc3d_streams.h, bound when the first of them is called."""
+    try:
+        lib.toc3d_streams_abi.restype = _I
+        abi = lib.toc3d_streams_abi()
+        fns = {name: getattr(lib, name) for name in _STREAMS_SIGS}
+    except AttributeError:
+        abi, fns = None, {}
+    if abi != STREAMS_ABI:
+        raise RuntimeError(f"{LIB_PATH} reports streams ABI {abi}, this package binds {STREAMS_ABI} (include/toc3d_streams.h): "
+                           "rebuild the library (`make -C toc3d_amd/csrc`)")
+    for name, fn in fns.items():
+        fn.restype = _I
+        fn.argtypes = [_CT[c] for c in _STREAMS_SIGS[name]]
+    lib._toc3d_streams_bound = True
+
+
 def call(name: str, *args):
     """Invoke a C-ABI entry point; tensors are passed as device pointers; raises on a non-zero return."""
     lib = load()
+    if name in _STREAMS_SIGS and not getattr(lib, "_toc3d_streams_bound", False):
+        _bind_streams(lib)
     rc = getattr(lib, name)(*[_conv(a) for a in args])
     if rc != 0:
         raise RuntimeError(f"{name} failed ({rc}): {lib.toc3d_last_error().decode()}")

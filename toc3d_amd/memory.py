@@ -121,13 +121,26 @@ class TemporalMemory:
 
     # -- consumer side: what Petr3D passes to the backbone (detectors/petr3d.py:115-134) --------------------
     def backbone_queries(self, num_proposals: int, prev_exists, batch_size: int = 1) -> Dict[str, torch.Tensor]:
-        mid = bool(prev_exists.bool().flatten()[0].item()) if isinstance(prev_exists, torch.Tensor) else bool(prev_exists)
+        """``prev_exists``: a bool (or a tensor, read at its first element) for the whole batch, or a list / tuple of Python bools, one per sample (B camera
+        streams stepped together).  The sequence form returns a list: every flag False with zeros while the bank is unallocated, otherwise the caller's flags
+        with the bank's slices of ALL samples -- a sample that starts a scene still holds its previous scene's entries (finite; its flag makes the backbone
+        ignore them, and ``pre_update_memory`` zeroes them with ``prev_exists = 0``)."""
+        per_sample = isinstance(prev_exists, (list, tuple))
+        if per_sample:
+            flags = [bool(p) for p in prev_exists]
+            B = self._B if self._len else batch_size
+            if len(flags) != B:
+                raise ValueError(f"prev_exists has {len(flags)} entries, the bank holds {B} samples" if self._len else
+                                 f"prev_exists has {len(flags)} entries for batch_size {B}")
+            mid = True
+        else:
+            mid = bool(prev_exists.bool().flatten()[0].item()) if isinstance(prev_exists, torch.Tensor) else bool(prev_exists)
         if not mid or self._len == 0:
             B = self._B or batch_size
             z = lambda *s, dt=torch.float32: torch.zeros(B, num_proposals, *s, dtype=dt, device=self.device)
             return dict(temp_queries=z(self.embed_dims), temp_ref_points=z(3), temp_timestamp=z(1), temp_ego_pose=z(4, 4), temp_vel=z(2),
-                        prev_exists=False)
+                        prev_exists=[False] * B if per_sample else False)
         n = num_proposals
         return dict(temp_queries=self.memory_embedding[:, :n], temp_ref_points=self.memory_reference_point[:, :n],
                     temp_timestamp=self.memory_timestamp[:, :n], temp_ego_pose=self.memory_egopose[:, :n], temp_vel=self.memory_velo[:, :n],
-                    prev_exists=True)
+                    prev_exists=flags if per_sample else True)

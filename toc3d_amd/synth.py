@@ -660,3 +660,20 @@ def detector_inputs(sizes: dict = None, seed: int = 0):
         scene = "b" if sizes["new_scene_at"] is not None and f >= sizes["new_scene_at"] else "a"
         frames.append(dict(img_metas=[dict(scene_token=scene, pad_shape=[(H, W, 3)])], data=data, gumbel=img["gumbel"]))
     return frames
+
+
+def stack_detector_frames(frames):
+    """B single-stream frames of ``detector_inputs`` (any streams, any seeds) -> ONE step of ``Petr3D.simple_test_streams``: ``dict(img_metas=[B dicts], data=...,
+    gumbel=...)`` with every tensor stacked along the leading dim (``img`` (B, N, 3, H, W), ``timestamp`` (B,), ...) and three (B * N, T, 2) draws, frame-major."""
+    return dict(img_metas=[fr["img_metas"][0] for fr in frames],
+                data={k: torch.cat([fr["data"][k] for fr in frames], 0) for k in frames[0]["data"]},
+                gumbel=[torch.cat([fr["gumbel"][s] for fr in frames], 0) for s in range(len(frames[0]["gumbel"]))])
+
+
+def detector_stream_steps(sizes: dict = None, seeds=(0, 1), new_scene_at=(3, 2)):
+    """B camera streams stepped together: stream b is ``detector_inputs(sizes, seed=seeds[b])`` with its scene change at frame ``new_scene_at[b]`` (None: no
+    change).  Returns ``(steps, streams)``: ``streams[b]`` the stream's own B = 1 frames, ``steps[f]`` = ``stack_detector_frames`` of the streams' frames f."""
+    sizes = DETECTOR_FULL if sizes is None else sizes
+    assert len(seeds) == len(new_scene_at)
+    streams = [detector_inputs(dict(sizes, new_scene_at=at), seed=seed) for seed, at in zip(seeds, new_scene_at)]
+    return [stack_detector_frames(frames) for frames in zip(*streams)], streams

@@ -10,6 +10,12 @@ stages, medians over the same number of legs).  The two forms differ by the neck
 a copy + ``toc3d_nchw_to_rows``) and return the same bits (tests/test_gpu_detector.py).  One JSON line on stdout, also written to --out.
 
   python tools/detector_time.py
+
+``--streams 1 2 4``: instead, B camera streams per step through ``Petr3D.simple_test_streams`` (stream b = ``synth.detector_inputs(seed=b)``), same warm-up, median
+and alternation scheme, written to profiles/detector_streams_time.json.  Per B: a steady step (every stream continues) and, for B >= 2, a mixed step (stream 0 is
+forgotten with ``reset_streams([0])`` in front of every step, so it starts a scene while the others continue; the call is inside the bracket).  B = 1 goes through the
+unchanged ``simple_test`` -- the baseline, checked against profiles/detector_time.json within that file's own spread -- and also gives the first-frame step (a scene
+start every step) that the two-forward alternative to a mixed step would add to a steady one.  Peak device memory (``torch.cuda.max_memory_allocated``) per B.
 """
 import argparse
 import json
@@ -114,13 +120,92 @@ def run(precision, warmup, steps, repeats=3):
                 split_ms=split, split_sum_ms=round(sum(split.values()), 4))
 
 
+def run_streams(precision, counts, warmup, steps, repeats=3):
+    sizes = synth.DETECTOR_FULL
+    sd = synth.detector_state_dict(sizes)
+    res = {}
+    for B in counts:
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        det = toc3d_amd.build_detector(synth.detector_cfg(sizes), precision=precision)
+        det.load_state_dict(sd, strict=True)
+        det.to(DEV)
+        has_table = tuned(sizes, precision, det.img_backbone, det.img_neck)
+        per = [synth.detector_inputs(sizes, seed=b) for b in range(B)]
+        frames = [synth.stack_detector_frames([p[f] for p in per]) for f in range(2)]
+        metas = frames[0]["img_metas"]
+        data = [{k: v.to(DEV) for k, v in f["data"].items()} for f in frames]
+        if B == 1:                                                         # the unchanged simple_test: the baseline, and the scene start of the two-forward alternative
+            def first():
+                det.prev_scene_token = None
+                return det.simple_test(metas, **data[1])
+            legs = dict(steady=lambda: det.simple_test(metas, **data[1]), first=first)
+            det.simple_test(metas, **data[0])
+        else:
+            def mixed():
+                det.reset_streams([0])
+                return det.simple_test_streams(metas, **data[1])
+            legs = dict(steady=lambda: det.simple_test_streams(metas, **data[1]), mixed=mixed)
+            det.simple_test_streams(metas, **data[0])
+        runs = {name: [] for name in legs}
+        for _ in range(repeats):                                           # alternating: every leg sees the same drift of the card
+            for name, fn in legs.items():
+                runs[name].append(timed(fn, warmup, steps)["median_ms"])
+        r = dict(tuned_table=bool(has_table), peak_memory_mib=round(torch.cuda.max_memory_allocated() / 2 ** 20, 1))
+        for name, ms in runs.items():
+            r[name + "_ms"] = ms
+            r[name + "_median_ms"] = median(ms)
+            r[name + "_spread_ms"] = round(max(ms) - min(ms), 4)
+        r["steady_frames_per_s"] = round(1000.0 * B / r["steady_median_ms"], 2)
+        res[str(B)] = r
+        print(f"[{precision}] B = {B}: " + ", ".join(f"{name} {r[name + '_median_ms']} ms" for name in legs), file=sys.stderr, flush=True)
+        del det, legs
+    one = res.get("1")
+    for B, r in res.items():
+        if one is None or B == "1":
+            continue
+        r["steady_frames_per_s_over_b1"] = round(r["steady_frames_per_s"] / one["steady_frames_per_s"], 4)
+        r["mixed_over_steady"] = round(r["mixed_median_ms"] / r["steady_median_ms"], 4)
+        r["two_forwards_ms"] = round(r["steady_median_ms"] + one["first_median_ms"], 4)          # the alternative: the steady step + one B = 1 first-frame step
+        r["mixed_over_two_forwards"] = round(r["mixed_median_ms"] / r["two_forwards_ms"], 4)
+        r["mixed_beats_two_forwards"] = bool(r["mixed_median_ms"] < r["two_forwards_ms"])
+    return res
+
+
+def main_streams(a):
+    res = dict(tool="detector_time --streams", device=torch.cuda.get_device_name(0), sizes=dict(backbone="toc3d_faster", image=[6, 320, 800], neck="CPFPN 1024 -> 256",
+                                                                                                  head={k: v for k, v in synth.HEAD_FULL.items() if k != "decoder"}),
+               streams=a.streams, warmup=a.warmup, steps=a.steps, repeats=3)
+    base_path = os.path.join(ROOT, "profiles", "detector_time.json")
+    base = json.load(open(base_path)) if os.path.exists(base_path) else {}
+    for precision in a.precisions.split(","):
+        r = run_streams(precision, a.streams, a.warmup, a.steps)
+        if "1" in r and precision in base:                                  # B = 1 is the parent's code: within the earlier file's own spread of its figure?
+            b = base[precision]
+            spread = max(b["detector_ms"]) - min(b["detector_ms"])
+            r["1"]["baseline_file_ms"], r["1"]["baseline_file_spread_ms"] = b["detector_median_ms"], round(spread, 4)
+            r["1"]["within_baseline_file_spread"] = bool(abs(r["1"]["steady_median_ms"] - b["detector_median_ms"]) <= spread)
+        res[precision] = r
+    line = json.dumps(res)
+    print(line)
+    out = a.out or os.path.join(ROOT, "profiles", "detector_streams_time.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as fh:
+        fh.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--precisions", default="fp32x3,bf16")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "detector_time.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/detector_time.json, or profiles/detector_streams_time.json with --streams")
+    ap.add_argument("--streams", type=int, nargs="+", default=None, help="camera streams per step to time through simple_test_streams, e.g. 1 2 4")
     a = ap.parse_args()
+    if a.streams:
+        return main_streams(a)
+    a.out = a.out or os.path.join(ROOT, "profiles", "detector_time.json")
     res = dict(tool="detector_time", device=torch.cuda.get_device_name(0), sizes=dict(backbone="toc3d_faster", image=[6, 320, 800], neck="CPFPN 1024 -> 256",
                                                                                         head={k: v for k, v in synth.HEAD_FULL.items() if k != "decoder"}),
                warmup=a.warmup, steps=a.steps, repeats=3)
