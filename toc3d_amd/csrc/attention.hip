@@ -12,8 +12,7 @@
 // Dense blocks zero-pad *after* LayerNorm (eva_vit.py:249-254): a padded slot is a key with k = 0 (k_proj has
 // no bias, eva_vit.py:98) and v = v_bias, identical for every pad, so the npad virtual keys are folded in
 // analytically at the end: denominator += npad * exp(0 - m), numerator += npad * exp(0 - m) * v_bias.
-#include "capi.h"
-#include "common.h"
+#include "act_rows.h"
 
 namespace {
 
@@ -708,7 +707,7 @@ int toc3d_window_attention_pf(int dtype, const void* qkv, int64_t ldqkv, void* o
     const bool out_planes = dtype == TOC3D_F32X3P || dtype == TOC3D_F32X3WO, x3_products = dtype == TOC3D_F32X3 || dtype == TOC3D_F32X3P;
     if (dtype != TOC3D_BF16) dtype = TOC3D_F32;
     if (out_planes) {
-        TOC3D_REQUIRE(((uintptr_t)out % 128) == 0 && ldo % 32 == 0, "toc3d_window_attention: rows of (hi, lo) planes start on 128-byte boundaries (out aligned, ldo a multiple of 32)");
+        TOC3D_REQUIRE(planes_rows_ok(out, ldo), "toc3d_window_attention: rows of (hi, lo) planes start on 128-byte boundaries (out aligned, ldo a multiple of 32)");
     }
     TOC3D_REQUIRE(qkv && out && rows && slots && count && rope_cos && rope_sin, "toc3d_window_attention: null buffer");
     TOC3D_REQUIRE(!npad || v_bias, "toc3d_window_attention: npad given without v_bias");

@@ -20,8 +20,7 @@
 // Virtual kept-pad keys of accelerated blocks (rows[j] < 0): their q|k|v is the projection of LN(0) = beta, a per-block constant, but
 // the RoPE of its k depends on the window slot -- the host packs pad_rot [window slots, 3C] with the same GEMM epilogue, and the key
 // reads row slots[j] of it.  Dense blocks: the npad zero-pad keys are folded analytically (attention.hip header).
-#include "capi.h"
-#include "common.h"
+#include "act_rows.h"
 
 // Development instrumentation (tools/ubench/attn_timeline.py builds a private copy with -DTOC3D_ATTN_TRACE; the library never defines it):
 // per-workgroup stamps of the 100 MHz real-time counter at entry / indices back / operands landed / compute done / stores acknowledged.
@@ -593,7 +592,7 @@ int toc3d_window_attention_rot(int dtype, const void* qkv, int64_t ldqkv, void* 
         TOC3D_REQUIRE(stride <= 1024 && max_count <= 512, "toc3d_window_attention_rot: windows of up to 1024 keys / 512 queries");
         const int64_t Cx = num_heads * HD;
         TOC3D_REQUIRE(ldqkv >= 3 * Cx && ldo >= Cx && ldqkv % 32 == 0 && ldo % 32 == 0, "toc3d_window_attention_rot: rows of planes are whole 32-element groups (ldqkv, ldo multiples of 32)");
-        TOC3D_REQUIRE(((uintptr_t)qkv % 128) == 0 && ((uintptr_t)out % 128) == 0 && (!pad_rot || ((uintptr_t)pad_rot % 128) == 0), "toc3d_window_attention_rot: planes start on 128-byte boundaries");
+        TOC3D_REQUIRE(aligned(qkv, 128) && aligned(out, 128) && aligned(pad_rot, 128), "toc3d_window_attention_rot: planes start on 128-byte boundaries");
         TOC3D_REQUIRE(num_heads <= 65535 && nwin <= 65535, "toc3d_window_attention_rot: grid too large");
         TOC3D_REQUIRE(n_prefetch == 0 || prefetch_workgroups == 0, "toc3d_window_attention_rot: the planes form carries no weight prefetch");
         if (nwin == 0 || max_count == 0) return TOC3D_OK;

@@ -167,6 +167,10 @@ TOC3D_DEV void store4(float* p, const float (&v)[4]) { *reinterpret_cast<f32x4*>
 // 64 + 2 (c % 32).  f32p_t tags such a buffer in the row kernels' templates (pointer arithmetic as for float).  Rows start on 128-byte boundaries (host-checked),
 // so group and position follow from the address the f32 element would have.
 struct f32p_t { float v; };
+TOC3D_DEV char* planes_addr(const void* f32_addr) {                      // where the element's hi lives; its lo is 64 bytes on
+    const uintptr_t a = reinterpret_cast<uintptr_t>(f32_addr);
+    return reinterpret_cast<char*>(a & ~(uintptr_t)127) + ((a & 127) >> 1);
+}
 TOC3D_DEV void store4_planes(void* f32_addr, const float (&v)[4]) {      // 4 consecutive elements, the first at a multiple of 4
     typedef bf16_t bf16x4_t __attribute__((ext_vector_type(4)));
     bf16x4_t hi, lo;
@@ -176,8 +180,7 @@ TOC3D_DEV void store4_planes(void* f32_addr, const float (&v)[4]) {      // 4 co
         hi[e] = h;
         lo[e] = (bf16_t)(v[e] - (float)h);
     }
-    const uintptr_t a = reinterpret_cast<uintptr_t>(f32_addr);
-    char* g = reinterpret_cast<char*>(a & ~(uintptr_t)127) + ((a & 127) >> 1);
+    char* g = planes_addr(f32_addr);
     *reinterpret_cast<bf16x4_t*>(g) = hi;
     *reinterpret_cast<bf16x4_t*>(g + 64) = lo;
 }

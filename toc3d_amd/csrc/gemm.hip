@@ -21,6 +21,7 @@
 // instantiated by gemm_epi_{plain,residual,swiglu}.hip.
 #include <cstdlib>
 
+#include "act_rows.h"
 #include "gemm_kernels.h"
 
 thread_local bool g_bad_variant = false;               // variant cannot serve the requested epilogue
@@ -414,7 +415,7 @@ int toc3d_linear_qkv_rope(int dtype, int variant, const void* A, int64_t lda, co
     TOC3D_REQUIRE(lda >= K && ldw >= K && ldo >= N && (lda * esz) % 16 == 0 && (ldw * esz) % 16 == 0, "toc3d_linear_qkv_rope: bad leading dims");
     TOC3D_REQUIRE(((uintptr_t)A % 16) == 0 && ((uintptr_t)W % 16) == 0 && ((uintptr_t)rope_tab % 16) == 0, "toc3d_linear_qkv_rope: misaligned buffer");
     TOC3D_REQUIRE(rope_side > 0 && rope_side <= 64, "toc3d_linear_qkv_rope: rope_side out of range (the tables live in LDS: <= 64; launch_cfg / launch_phased size their LDS attribute for 64)");
-    if (x3) TOC3D_REQUIRE(ldo % 32 == 0 && ((uintptr_t)out % 128) == 0 && (dtype != TOC3D_F32X3P || lda % 32 == 0), "toc3d_linear_qkv_rope: rows of (hi, lo) planes are whole 32-element groups on 128-byte boundaries");
+    if (x3) TOC3D_REQUIRE(planes_rows_ok(out, ldo) && (dtype != TOC3D_F32X3P || lda % 32 == 0), "toc3d_linear_qkv_rope: rows of (hi, lo) planes are whole 32-element groups on 128-byte boundaries");
     if (M == 0) return TOC3D_OK;
     const bool vec = ldo % 4 == 0 && (uintptr_t)out % (4 * esz) == 0;
     const bool vec8 = !x3 && vec && ldo % 8 == 0 && (uintptr_t)out % 16 == 0;

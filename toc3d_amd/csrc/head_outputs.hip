@@ -12,22 +12,12 @@
 //                           an MFMA tile to 128 columns), + inverse_sigmoid(reference_points), sigmoid, pc_range, and the writes of all_cls_scores / all_bbox_preds;
 //   * nms_free_decode_kernel  one workgroup per sample: sigmoid, the max_num best (query, class) pairs in descending order (ties: lowest flat index), box gather,
 //                           denormalize_bbox, the post_center_range / score_threshold mask, compaction by a block prefix sum (no atomics: deterministic order).
-// exp / log / atan2 are the libm forms (no fast-math intrinsics): scores decide a ranking.
-#include "capi.h"
-#include "common.h"
+// exp / log / atan2 are the libm forms (no fast-math intrinsics): scores decide a ranking.  A GEMM's A operand is stored in its three forms by put4 (act_rows.h).
+#include "act_rows.h"
 
 #include <float.h>
 
 namespace {
-
-// ---- stores of 4 consecutive elements in the three forms a GEMM's A operand takes ------------------------------------------------------------------
-template <typename T> TOC3D_DEV void put4(T* p, const float (&v)[4]);
-template <> TOC3D_DEV void put4<float>(float* p, const float (&v)[4]) { store4(p, v); }
-template <> TOC3D_DEV void put4<bf16_t>(bf16_t* p, const float (&v)[4]) {
-    const bf16_t b[4] = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
-    store4(p, b);
-}
-template <> TOC3D_DEV void put4<f32p_t>(f32p_t* p, const float (&v)[4]) { store4_planes(p, v); }
 
 // torch.nan_to_num with its defaults: NaN -> 0, +inf -> FLT_MAX, -inf -> -FLT_MAX; everything else unchanged (bit tests: no dependence on fast-math settings)
 TOC3D_DEV float nan_to_num(float x) {
@@ -120,11 +110,6 @@ __global__ __launch_bounds__(256) void ln_relu_kernel(const float* __restrict__ 
 
 // ---- the two last layers and everything behind them -------------------------------------------------------------------------------------------------
 TOC3D_DEV float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
-// mmdet's inverse_sigmoid: clamp to [0, 1], eps = 1e-5 on numerator and denominator
-TOC3D_DEV float inverse_sigmoidf_(float x) {
-    x = fminf(fmaxf(x, 0.f), 1.f);
-    return logf(fmaxf(x, 1e-5f) / fmaxf(1.f - x, 1e-5f));
-}
 
 struct HeadOutArgs {
     const float* h;                      // [M, ldh]: class tower in columns [0, E), box tower in [E, 2E), both BEFORE their last LayerNorm / ReLU
@@ -177,7 +162,7 @@ __global__ __launch_bounds__(256) void head_outputs_kernel(const HeadOutArgs a) 
             float t = mine_r + a.b_reg[lane];
             if (lane < 3) {
                 // tmp[..., 0:3] += inverse_sigmoid(reference_points); sigmoid; * (pc_range[3:6] - pc_range[0:3]) + pc_range[0:3]  (two roundings, as the reference's two ops)
-                t += inverse_sigmoidf_(a.ref[(int64_t)(row % a.ref_rows) * 3 + lane]);
+                t += inverse_sigmoid(a.ref[(int64_t)(row % a.ref_rows) * 3 + lane]);
                 t = __fadd_rn(__fmul_rn(sigmoidf_(t), a.span[lane]), a.lo[lane]);
             }
             a.box[(int64_t)row * a.ldb + lane] = t;
@@ -338,13 +323,11 @@ __global__ __launch_bounds__(DEC_THREADS) void nms_free_decode_kernel(const Deco
     if (tid == 0) a.counts[b] = base;
 }
 
-bool aligned(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
-
 // the checks on an act-dtype output of a row kernel: bf16 rows as 8-byte pieces, f32 rows as 16-byte pieces, planes as whole 128-byte groups
 const char* act_rows_problem(int dtype, const void* act, int64_t ld_act) {
     if (dtype == TOC3D_BF16) return aligned(act, 8) && ld_act % 4 == 0 ? nullptr : "bf16 rows must be 8-byte aligned (ld_act a multiple of 4)";
     if (dtype == TOC3D_F32) return aligned(act, 16) && ld_act % 4 == 0 ? nullptr : "f32 rows must be 16-byte aligned (ld_act a multiple of 4)";
-    if (dtype == TOC3D_F32X3P) return aligned(act, 128) && ld_act % 32 == 0 ? nullptr : "rows of (hi, lo) planes start on 128-byte boundaries (out_act aligned, ld_act a multiple of 32)";
+    if (dtype == TOC3D_F32X3P) return planes_rows_ok(act, ld_act) ? nullptr : "rows of (hi, lo) planes start on 128-byte boundaries (out_act aligned, ld_act a multiple of 32)";
     return "dtype must be TOC3D_DTYPE_BF16, TOC3D_DTYPE_F32 or TOC3D_DTYPE_F32X3P";
 }
 
@@ -366,12 +349,11 @@ int toc3d_head_nan_to_num_rows(int dtype, const float* x, int64_t ldx, float* ou
     TOC3D_REQUIRE(E < (1ll << 31) && M <= ((1ll << 31) - 1) * 256 / (E / 4), "toc3d_head_nan_to_num_rows: too many elements for one launch");
     if (M == 0) return TOC3D_OK;
     const dim3 grid((unsigned)((M * (E / 4) + 255) / 256));
-    if (!out_act || dtype == TOC3D_F32)
-        toc3d_launch(nan_to_num_kernel<float>, grid, dim3(256), 0, as_stream(stream), x, ldx, out, ldo, (float*)out_act, ld_act, M, (int)(E / 4));
-    else if (dtype == TOC3D_BF16)
-        toc3d_launch(nan_to_num_kernel<bf16_t>, grid, dim3(256), 0, as_stream(stream), x, ldx, out, ldo, (bf16_t*)out_act, ld_act, M, (int)(E / 4));
-    else
-        toc3d_launch(nan_to_num_kernel<f32p_t>, grid, dim3(256), 0, as_stream(stream), x, ldx, out, ldo, (f32p_t*)out_act, ld_act, M, (int)(E / 4));
+    // (without out_act the dtype names nothing: the f32 kernel writes `out` alone)
+    if (int rc = toc3d_dispatch_act<ACT_ANY>("toc3d_head_nan_to_num_rows", out_act ? dtype : TOC3D_F32, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            toc3d_launch(nan_to_num_kernel<T>, grid, dim3(256), 0, as_stream(stream), x, ldx, out, ldo, (T*)out_act, ld_act, M, (int)(E / 4));
+        })) return rc;
     TOC3D_LAUNCH_CHECK("toc3d_head_nan_to_num_rows");
     return TOC3D_OK;
 }
@@ -387,12 +369,10 @@ int toc3d_head_ln_relu_rows(int dtype, const float* x, int64_t ldx, const float*
     TOC3D_REQUIRE(M < (1ll << 31) - 4, "toc3d_head_ln_relu_rows: too many rows");
     if (M == 0) return TOC3D_OK;
     const dim3 grid((unsigned)((M + 3) / 4));
-    if (dtype == TOC3D_BF16)
-        toc3d_launch(ln_relu_kernel<bf16_t>, grid, dim3(256), 0, as_stream(stream), x, ldx, gamma, beta, eps, (bf16_t*)out_act, ld_act, (int)M, (int)E_ln, (int)E_relu);
-    else if (dtype == TOC3D_F32)
-        toc3d_launch(ln_relu_kernel<float>, grid, dim3(256), 0, as_stream(stream), x, ldx, gamma, beta, eps, (float*)out_act, ld_act, (int)M, (int)E_ln, (int)E_relu);
-    else
-        toc3d_launch(ln_relu_kernel<f32p_t>, grid, dim3(256), 0, as_stream(stream), x, ldx, gamma, beta, eps, (f32p_t*)out_act, ld_act, (int)M, (int)E_ln, (int)E_relu);
+    if (int rc = toc3d_dispatch_act<ACT_ANY>("toc3d_head_ln_relu_rows", dtype, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            toc3d_launch(ln_relu_kernel<T>, grid, dim3(256), 0, as_stream(stream), x, ldx, gamma, beta, eps, (T*)out_act, ld_act, (int)M, (int)E_ln, (int)E_relu);
+        })) return rc;
     TOC3D_LAUNCH_CHECK("toc3d_head_ln_relu_rows");
     return TOC3D_OK;
 }

@@ -13,18 +13,9 @@
 //                            into temp_pos / temp_memory: the torch.cat of :446-451 is a store address.
 // sinf / cosf / sin / cos are the range-reduced libm forms and every division is the correctly rounded one (this file is built without fast-math): the arguments
 // reach 2 pi * 1.5e9 (epoch timestamps) and 32 * 1.5e9, and a 1-ulp change of an argument of that size is a different result.
-#include "capi.h"
-#include "common.h"
+#include "act_rows.h"
 
 namespace {
-
-template <typename T> TOC3D_DEV void put4(T* p, const float (&v)[4]);
-template <> TOC3D_DEV void put4<float>(float* p, const float (&v)[4]) { store4(p, v); }
-template <> TOC3D_DEV void put4<bf16_t>(bf16_t* p, const float (&v)[4]) {
-    const bf16_t b[4] = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
-    store4(p, b);
-}
-template <> TOC3D_DEV void put4<f32p_t>(f32p_t* p, const float (&v)[4]) { store4_planes(p, v); }
 
 constexpr int QE = 256;                                    // embed_dims: pos2posemb3d yields 3 * 128, pos2posemb1d 256, MLN(180) has f_dim 256
 constexpr int POS_W = 384, NERF_W = 180, NERF_WP = 192, T1D_W = 256;
@@ -183,14 +174,12 @@ __global__ __launch_bounds__(256) void query_combine_kernel(const QueryCombineAr
     *reinterpret_cast<f32x4*>(dm + c) = m;
 }
 
-bool aligned(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
-
 // an act-dtype output [rows, ld] of `width` columns: bf16 rows as 8-byte pieces, f32 rows as 16-byte pieces, planes as whole 128-byte groups
 const char* act_rows_problem(int dtype, const void* act, int64_t ld, int64_t width) {
     if (ld < width) return "leading dimension smaller than the row";
     if (dtype == TOC3D_BF16) return aligned(act, 8) && ld % 4 == 0 ? nullptr : "bf16 rows must be 8-byte aligned (leading dimension a multiple of 4)";
     if (dtype == TOC3D_F32) return aligned(act, 16) && ld % 4 == 0 ? nullptr : "f32 rows must be 16-byte aligned (leading dimension a multiple of 4)";
-    if (dtype == TOC3D_F32X3P) return aligned(act, 128) && ld % 32 == 0 ? nullptr : "rows of (hi, lo) planes start on 128-byte boundaries (buffer aligned, leading dimension a multiple of 32)";
+    if (dtype == TOC3D_F32X3P) return planes_rows_ok(act, ld) ? nullptr : "rows of (hi, lo) planes start on 128-byte boundaries (buffer aligned, leading dimension a multiple of 32)";
     return "dtype must be TOC3D_DTYPE_BF16, TOC3D_DTYPE_F32 or TOC3D_DTYPE_F32X3P";
 }
 
@@ -225,12 +214,10 @@ int toc3d_head_query_inputs(int dtype, const float* reference_point, int64_t ref
     a.ld_pos = ld_pos; a.ld_nerf = ld_nerf; a.ld_t1d = ld_t1d; a.ref_out = ref_out; a.ref_out_stride = ref_out_stride;
     a.n = (int)n; a.np = (int)np; a.rows = B * n;
     const dim3 grid((unsigned)((a.rows * QUADS_ROW + 255) / 256));
-    if (dtype == TOC3D_BF16)
-        toc3d_launch(query_inputs_kernel<bf16_t>, grid, dim3(256), 0, as_stream(stream), a, (bf16_t*)pos3d, (bf16_t*)nerf, (bf16_t*)t1d);
-    else if (dtype == TOC3D_F32)
-        toc3d_launch(query_inputs_kernel<float>, grid, dim3(256), 0, as_stream(stream), a, (float*)pos3d, (float*)nerf, (float*)t1d);
-    else
-        toc3d_launch(query_inputs_kernel<f32p_t>, grid, dim3(256), 0, as_stream(stream), a, (f32p_t*)pos3d, (f32p_t*)nerf, (f32p_t*)t1d);
+    if (int rc = toc3d_dispatch_act<ACT_ANY>("toc3d_head_query_inputs", dtype, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            toc3d_launch(query_inputs_kernel<T>, grid, dim3(256), 0, as_stream(stream), a, (T*)pos3d, (T*)nerf, (T*)t1d);
+        })) return rc;
     TOC3D_LAUNCH_CHECK("toc3d_head_query_inputs");
     return TOC3D_OK;
 }

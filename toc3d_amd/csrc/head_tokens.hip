@@ -1,9 +1,8 @@
 // Token side of StreamPETRHead.forward (second half): what consumes the neck's features behind the
 // backbone.  Reference: dense_heads/streampetr_head.py position_embeding :378-422, forward :627-639; models/utils/misc.py
 // locations :59-82, MLN :154-188, SELayer_Linear :139-151.  The linear layers run on toc3d_linear; this file holds the elementwise /
-// geometry kernels around them.  All HBM-bound byte work on [tokens, 64..1024] rows.
-#include "capi.h"
-#include "common.h"
+// geometry kernels around them.  All HBM-bound byte work on [tokens, 64..1024] rows.  Act rows are stored with put1 / put4 (act_rows.h).
+#include "act_rows.h"
 
 namespace {
 
@@ -14,21 +13,6 @@ struct FrustumArgs {
     float pr[6];                // position_range
     int B, N, h, w, D, stride, pad_h, pad_w;
 };
-
-// one element of an act row: the act dtype's rounding, or -- f32p_t (common.h) -- the element's (hi, lo) pair in the planes layout of store4_planes
-template <typename T> TOC3D_DEV void put1(T* p, float v) { *p = to_act<T>(v); }
-TOC3D_DEV void put1(f32p_t* p, float v) {
-    const bf16_t h = (bf16_t)v;
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
-    char* g = reinterpret_cast<char*>(a & ~(uintptr_t)127) + ((a & 127) >> 1);
-    *reinterpret_cast<bf16_t*>(g) = h;
-    *reinterpret_cast<bf16_t*>(g + 64) = (bf16_t)(v - (float)h);
-}
-
-TOC3D_DEV float inv_sigmoid(float x) {                                  // mmdet inverse_sigmoid, eps = 1e-5
-    x = fminf(fmaxf(x, 0.f), 1.f);
-    return logf(fmaxf(x, 1e-5f) / fmaxf(1.f - x, 1e-5f));
-}
 
 // one thread per (token, depth bin): the 3-D point of the pixel centre at that depth through lidar2img^-1 (:391-413)
 template <typename T>
@@ -59,9 +43,9 @@ __global__ __launch_bounds__(256) void frustum_kernel(FrustumArgs a, T* __restri
         p[i] = __fdiv_rn(__fsub_rn(s, a.pr[i]), __fsub_rn(a.pr[3 + i], a.pr[i]));
     }
     T* dst = pin + tokg * ld_pin + d * 3;
-    put1(dst, inv_sigmoid(p[0]));
-    put1(dst + 1, inv_sigmoid(p[1]));
-    put1(dst + 2, inv_sigmoid(p[2]));
+    put1(dst, inverse_sigmoid(p[0]));
+    put1(dst + 1, inverse_sigmoid(p[1]));
+    put1(dst + 2, inverse_sigmoid(p[2]));
     // cone (:419-420): [|fx|, |fy|] / 1e3 of camera (token index % N) -- the reference's repeat order (:385-386) --, then the points
     // of the last depth bin and of bin D - 30
     float* cr = cone + tokg * 8;
@@ -103,15 +87,6 @@ __global__ __launch_bounds__(256) void nchw_rows_kernel(const float* __restrict_
         if (t < hw && c < C) put1(out + ((int64_t)v * hw + t) * ld + c, tile[tx][r]);
     }
 }
-
-// 4 consecutive elements of an act row, the first at a multiple of 4 columns of an aligned row: per element the bits of put1, as one 16-byte (f32) or
-// 8-byte (bf16; each plane of f32p_t) store
-TOC3D_DEV void put4(float* p, const float (&v)[4]) { store4(p, v); }
-TOC3D_DEV void put4(bf16_t* p, const float (&v)[4]) {
-    const bf16_t b[4] = {to_act<bf16_t>(v[0]), to_act<bf16_t>(v[1]), to_act<bf16_t>(v[2]), to_act<bf16_t>(v[3])};
-    store4(p, b);
-}
-TOC3D_DEV void put4(f32p_t* p, const float (&v)[4]) { store4_planes(p, v); }
 
 // The neck's conv rows x f32 [V*T, ldx], read ONCE, written twice: rows [V*T, ld] act straight from the registers (what nchw_rows_kernel would make of the
 // NCHW tensor: the same put1 per element, valid columns only), and NCHW f32 [V, C, T] through nhwc_to_nchw_kernel's padded 32 x 32 tile.  One workgroup per
@@ -200,20 +175,8 @@ __global__ void se_gate_kernel(const float* __restrict__ pos, const float* __res
 
 // an act output [rows, ld] of an entry point that also takes TOC3D_DTYPE_F32X3P: planes rows are whole 128-byte groups on 128-byte boundaries (the refusal of
 // toc3d_head_query_inputs); the other dtypes keep their checks
-bool planes_rows_ok(int dtype, const void* act, int64_t ld) {
-    return dtype != TOC3D_F32X3P || ((reinterpret_cast<uintptr_t>(act) & 127) == 0 && ld % 32 == 0);
-}
 #define TOC3D_PLANES_ROWS(fn, what, act, ld)                                                                                                           \
-    TOC3D_REQUIRE(planes_rows_ok(dtype, act, ld), fn ": " what ": rows of (hi, lo) planes start on 128-byte boundaries (buffer aligned, leading dimension a multiple of 32)")
-
-template <typename T>
-void launch_neck_rows_fanout(bool vin, bool vout, dim3 grid, hipStream_t s, const float* x, int64_t ldx, float* nchw, void* rows, int64_t ld, int Tn, int C) {
-    T* r = static_cast<T*>(rows);
-    if (vin && vout) toc3d_launch(neck_rows_fanout_kernel<T, true, true>, grid, dim3(256), 0, s, x, ldx, nchw, r, ld, Tn, C);
-    else if (vin) toc3d_launch(neck_rows_fanout_kernel<T, true, false>, grid, dim3(256), 0, s, x, ldx, nchw, r, ld, Tn, C);
-    else if (vout) toc3d_launch(neck_rows_fanout_kernel<T, false, true>, grid, dim3(256), 0, s, x, ldx, nchw, r, ld, Tn, C);
-    else toc3d_launch(neck_rows_fanout_kernel<T, false, false>, grid, dim3(256), 0, s, x, ldx, nchw, r, ld, Tn, C);
-}
+    TOC3D_REQUIRE(dtype != TOC3D_F32X3P || planes_rows_ok(act, ld), fn ": " what ": rows of (hi, lo) planes start on 128-byte boundaries (buffer aligned, leading dimension a multiple of 32)")
 
 }  // namespace
 
@@ -233,10 +196,10 @@ int toc3d_head_frustum_inputs(int dtype, const float* img2lidar, const float* in
     a.B = (int)B; a.N = (int)N; a.h = (int)h; a.w = (int)w; a.D = (int)D; a.stride = (int)stride; a.pad_h = (int)pad_h; a.pad_w = (int)pad_w;
     const int64_t total = B * N * h * w * D;
     dim3 grid((unsigned)((total + 255) / 256));
-    if (dtype == TOC3D_BF16) toc3d_launch(frustum_kernel<bf16_t>, grid, dim3(256), 0, as_stream(stream), a, (bf16_t*)pos_in, ld_pos, (bf16_t*)cone_act, ld_cone, cone);
-    else if (dtype == TOC3D_F32) toc3d_launch(frustum_kernel<float>, grid, dim3(256), 0, as_stream(stream), a, (float*)pos_in, ld_pos, (float*)cone_act, ld_cone, cone);
-    else if (dtype == TOC3D_F32X3P) toc3d_launch(frustum_kernel<f32p_t>, grid, dim3(256), 0, as_stream(stream), a, (f32p_t*)pos_in, ld_pos, (f32p_t*)cone_act, ld_cone, cone);
-    else { toc3d_set_error("toc3d_head_frustum_inputs: bad dtype"); return TOC3D_ERR_ARG; }
+    if (int rc = toc3d_dispatch_act<ACT_ANY>("toc3d_head_frustum_inputs", dtype, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            toc3d_launch(frustum_kernel<T>, grid, dim3(256), 0, as_stream(stream), a, (T*)pos_in, ld_pos, (T*)cone_act, ld_cone, cone);
+        })) return rc;
     TOC3D_LAUNCH_CHECK("toc3d_head_frustum_inputs");
     return TOC3D_OK;
 }
@@ -246,9 +209,10 @@ int toc3d_relu_inplace(int dtype, void* x, int64_t n, toc3d_stream_t stream) {
     TOC3D_REQUIRE(n <= ((1ll << 31) - 1) * 256, "toc3d_relu_inplace: too many elements for one launch");      // the grid below: at most 2^31 - 1 workgroups
     if (n == 0) return TOC3D_OK;
     dim3 grid((unsigned)((n + 255) / 256));
-    if (dtype == TOC3D_BF16) toc3d_launch(relu_kernel<bf16_t>, grid, dim3(256), 0, as_stream(stream), (bf16_t*)x, n);
-    else if (dtype == TOC3D_F32) toc3d_launch(relu_kernel<float>, grid, dim3(256), 0, as_stream(stream), (float*)x, n);
-    else { toc3d_set_error("toc3d_relu_inplace: bad dtype"); return TOC3D_ERR_ARG; }
+    if (int rc = toc3d_dispatch_act<ACT_BF16 | ACT_F32>("toc3d_relu_inplace", dtype, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            toc3d_launch(relu_kernel<T>, grid, dim3(256), 0, as_stream(stream), (T*)x, n);
+        })) return rc;
     TOC3D_LAUNCH_CHECK("toc3d_relu_inplace");
     return TOC3D_OK;
 }
@@ -257,10 +221,10 @@ int toc3d_nchw_to_rows(int dtype, const float* x, void* out, int64_t ldo, int64_
     TOC3D_REQUIRE(x && out && V > 0 && C > 0 && hw > 0 && ldo >= C && V <= 65535, "toc3d_nchw_to_rows: bad arguments");
     TOC3D_PLANES_ROWS("toc3d_nchw_to_rows", "out", out, ldo);
     dim3 grid((unsigned)((hw + 31) / 32), (unsigned)((C + 31) / 32), (unsigned)V);
-    if (dtype == TOC3D_BF16) toc3d_launch(nchw_rows_kernel<bf16_t>, grid, dim3(256), 0, as_stream(stream), x, (bf16_t*)out, ldo, (int)C, (int)hw);
-    else if (dtype == TOC3D_F32) toc3d_launch(nchw_rows_kernel<float>, grid, dim3(256), 0, as_stream(stream), x, (float*)out, ldo, (int)C, (int)hw);
-    else if (dtype == TOC3D_F32X3P) toc3d_launch(nchw_rows_kernel<f32p_t>, grid, dim3(256), 0, as_stream(stream), x, (f32p_t*)out, ldo, (int)C, (int)hw);
-    else { toc3d_set_error("toc3d_nchw_to_rows: bad dtype"); return TOC3D_ERR_ARG; }
+    if (int rc = toc3d_dispatch_act<ACT_ANY>("toc3d_nchw_to_rows", dtype, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            toc3d_launch(nchw_rows_kernel<T>, grid, dim3(256), 0, as_stream(stream), x, (T*)out, ldo, (int)C, (int)hw);
+        })) return rc;
     TOC3D_LAUNCH_CHECK("toc3d_nchw_to_rows");
     return TOC3D_OK;
 }
@@ -268,19 +232,24 @@ int toc3d_nchw_to_rows(int dtype, const float* x, void* out, int64_t ldo, int64_
 int toc3d_neck_rows_fanout(int dtype, const float* x, int64_t ldx, float* nchw, void* rows, int64_t ld_rows, int64_t V, int64_t T, int64_t C,
                            toc3d_stream_t stream) {
     TOC3D_REQUIRE(x && nchw && rows, "toc3d_neck_rows_fanout: null buffer");
-    TOC3D_REQUIRE(dtype == TOC3D_BF16 || dtype == TOC3D_F32 || dtype == TOC3D_F32X3P, "toc3d_neck_rows_fanout: bad dtype");
+    TOC3D_REQUIRE(act_served(ACT_ANY, dtype), "toc3d_neck_rows_fanout: bad dtype");
     TOC3D_REQUIRE(V > 0 && T > 0 && C > 0, "toc3d_neck_rows_fanout: bad dims (V, T, C > 0)");
     TOC3D_REQUIRE(V <= 65535 && T <= 0x7fffffffll - 31 && C <= 65535ll * 32, "toc3d_neck_rows_fanout: bad dims (V <= 65535 views, T and C within one launch's grid)");
     TOC3D_REQUIRE(ldx >= C && ld_rows >= C, "toc3d_neck_rows_fanout: bad leading dimensions (ldx >= C, ld_rows >= C)");
     TOC3D_PLANES_ROWS("toc3d_neck_rows_fanout", "rows", rows, ld_rows);
     // 4-column accesses: 16-byte loads of x; stores of 16 (f32) / 8 (bf16, each plane) bytes to rows
-    const uintptr_t row_align = dtype == TOC3D_BF16 ? 7 : 15;
-    const bool vin = C % 4 == 0 && ldx % 4 == 0 && ld_rows % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(rows) & row_align) == 0;
-    const bool vout = T % 4 == 0 && (reinterpret_cast<uintptr_t>(nchw) & 15) == 0;
+    const uintptr_t row_align = dtype == TOC3D_BF16 ? 8 : 16;
+    const bool vin = C % 4 == 0 && ldx % 4 == 0 && ld_rows % 4 == 0 && aligned(x, 16) && aligned(rows, row_align);
+    const bool vout = T % 4 == 0 && aligned(nchw, 16);
     dim3 grid((unsigned)((T + 31) / 32), (unsigned)((C + 31) / 32), (unsigned)V);
-    if (dtype == TOC3D_BF16) launch_neck_rows_fanout<bf16_t>(vin, vout, grid, as_stream(stream), x, ldx, nchw, rows, ld_rows, (int)T, (int)C);
-    else if (dtype == TOC3D_F32) launch_neck_rows_fanout<float>(vin, vout, grid, as_stream(stream), x, ldx, nchw, rows, ld_rows, (int)T, (int)C);
-    else launch_neck_rows_fanout<f32p_t>(vin, vout, grid, as_stream(stream), x, ldx, nchw, rows, ld_rows, (int)T, (int)C);
+    if (int rc = toc3d_dispatch_act<ACT_ANY>("toc3d_neck_rows_fanout", dtype, [&](auto tag) {
+            using E = typename decltype(tag)::type;          // (T is the token count here)
+            auto launch = [&](auto kernel) { toc3d_launch(kernel, grid, dim3(256), 0, as_stream(stream), x, ldx, nchw, (E*)rows, ld_rows, (int)T, (int)C); };
+            if (vin && vout) launch(neck_rows_fanout_kernel<E, true, true>);
+            else if (vin) launch(neck_rows_fanout_kernel<E, true, false>);
+            else if (vout) launch(neck_rows_fanout_kernel<E, false, true>);
+            else launch(neck_rows_fanout_kernel<E, false, false>);
+        })) return rc;
     TOC3D_LAUNCH_CHECK("toc3d_neck_rows_fanout");
     return TOC3D_OK;
 }
@@ -291,10 +260,10 @@ int toc3d_mln_apply(int dtype, const float* x, const float* gamma, const float* 
     TOC3D_PLANES_ROWS("toc3d_mln_apply", "out_act", out_act, ld_act);
     if (M == 0) return TOC3D_OK;
     dim3 grid((unsigned)((M + 3) / 4));
-    if (dtype == TOC3D_BF16) toc3d_launch(mln_kernel<bf16_t>, grid, dim3(256), 0, as_stream(stream), x, gamma, beta, (int)E, out, (bf16_t*)out_act, ld_act, (int)M);
-    else if (dtype == TOC3D_F32) toc3d_launch(mln_kernel<float>, grid, dim3(256), 0, as_stream(stream), x, gamma, beta, (int)E, out, (float*)out_act, ld_act, (int)M);
-    else if (dtype == TOC3D_F32X3P) toc3d_launch(mln_kernel<f32p_t>, grid, dim3(256), 0, as_stream(stream), x, gamma, beta, (int)E, out, (f32p_t*)out_act, ld_act, (int)M);
-    else { toc3d_set_error("toc3d_mln_apply: bad dtype"); return TOC3D_ERR_ARG; }
+    if (int rc = toc3d_dispatch_act<ACT_ANY>("toc3d_mln_apply", dtype, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            toc3d_launch(mln_kernel<T>, grid, dim3(256), 0, as_stream(stream), x, gamma, beta, (int)E, out, (T*)out_act, ld_act, (int)M);
+        })) return rc;
     TOC3D_LAUNCH_CHECK("toc3d_mln_apply");
     return TOC3D_OK;
 }

@@ -22,8 +22,7 @@
 // included -- P on ONE bf16 plane would put a 2^-9 relative rounding on every term of the P.V sum, the largest error of the whole layer; split, the kernel is at
 // 2e-5 of f64 and six post-norm layers stay at 1.5e-5 of the reference (profiles/decoder_parity.txt).
 // Softmax exp2-based on f32 scores scaled by scale * log2(e) after the MFMA (q itself is not re-rounded).
-#include "capi.h"
-#include "common.h"
+#include "act_rows.h"
 
 namespace {
 
@@ -330,8 +329,6 @@ __global__ __launch_bounds__(256) void add_pos_kernel(const float* __restrict__ 
     if (act_pos) act_pos[row * ld_act_pos + c] = to_act<T>(xv + pos[row * ldp + c]);
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 extern "C" {
@@ -354,7 +351,7 @@ int toc3d_mha_attention_ex(int dtype, const void* q, int64_t ldq, const void* k,
     const int64_t gran = dtype == TOC3D_BF16 ? 8 : 4;
     TOC3D_REQUIRE(ldq % gran == 0 && ldo % 4 == 0 && (Nk == 0 || (ldk % gran == 0 && ldv % gran == 0)) && (Nk2 == 0 || (ldk2 % gran == 0 && ldv2 % gran == 0)),
                   "toc3d_mha_attention: leading dimensions must be multiples of 8 (bf16) / 4 (f32) elements");
-    TOC3D_REQUIRE(aligned16(q) && aligned16(out) && aligned16(k) && aligned16(v) && aligned16(k2) && aligned16(v2), "toc3d_mha_attention: buffers must be 16-byte aligned");
+    TOC3D_REQUIRE(aligned(q, 16) && aligned(out, 16) && aligned(k, 16) && aligned(v, 16) && aligned(k2, 16) && aligned(v2, 16), "toc3d_mha_attention: buffers must be 16-byte aligned");
     MhaArgs a;
     a.q = (const char*)q; a.k = (const char*)k; a.v = (const char*)v; a.k2 = (const char*)k2; a.v2 = (const char*)v2; a.out = (char*)out;
     a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldk2 = ldk2; a.ldv2 = ldv2; a.ldo = ldo;
@@ -380,13 +377,11 @@ int toc3d_add_layernorm_pos(int dtype, const float* x, int64_t ldx, const float*
     TOC3D_REQUIRE(M < (1ll << 31) - 4, "toc3d_add_layernorm_pos: too many rows");
     if (M == 0) return TOC3D_OK;
     dim3 grid((unsigned)((M + 3) / 4));
-    if (dtype == TOC3D_BF16)
-        toc3d_launch(add_ln_pos_kernel<bf16_t>, grid, dim3(256), 0, as_stream(stream), x, ldx, gamma, beta, eps, pos, ldp, out, ldo, (bf16_t*)out_act, ld_act,
-                     (bf16_t*)out_act_pos, ld_act_pos, gamma2, beta2, out2, ldo2, (int)M, (int)E);
-    else if (dtype == TOC3D_F32)
-        toc3d_launch(add_ln_pos_kernel<float>, grid, dim3(256), 0, as_stream(stream), x, ldx, gamma, beta, eps, pos, ldp, out, ldo, (float*)out_act, ld_act,
-                     (float*)out_act_pos, ld_act_pos, gamma2, beta2, out2, ldo2, (int)M, (int)E);
-    else { toc3d_set_error("toc3d_add_layernorm_pos: bad dtype"); return TOC3D_ERR_ARG; }
+    if (int rc = toc3d_dispatch_act<ACT_BF16 | ACT_F32>("toc3d_add_layernorm_pos", dtype, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            toc3d_launch(add_ln_pos_kernel<T>, grid, dim3(256), 0, as_stream(stream), x, ldx, gamma, beta, eps, pos, ldp, out, ldo, (T*)out_act, ld_act,
+                         (T*)out_act_pos, ld_act_pos, gamma2, beta2, out2, ldo2, (int)M, (int)E);
+        })) return rc;
     TOC3D_LAUNCH_CHECK("toc3d_add_layernorm_pos");
     return TOC3D_OK;
 }
@@ -399,11 +394,10 @@ int toc3d_add_pos_rows(int dtype, const float* x, int64_t ldx, const float* pos,
     TOC3D_REQUIRE(E < (1ll << 31) && M <= ((1ll << 31) - 1) * 256 / E, "toc3d_add_pos_rows: too many elements for one launch");
     if (M == 0) return TOC3D_OK;
     dim3 grid((unsigned)((M * E + 255) / 256));
-    if (dtype == TOC3D_BF16)
-        toc3d_launch(add_pos_kernel<bf16_t>, grid, dim3(256), 0, as_stream(stream), x, ldx, pos, ldp, (bf16_t*)out_act, ld_act, (bf16_t*)out_act_pos, ld_act_pos, M, (int)E);
-    else if (dtype == TOC3D_F32)
-        toc3d_launch(add_pos_kernel<float>, grid, dim3(256), 0, as_stream(stream), x, ldx, pos, ldp, (float*)out_act, ld_act, (float*)out_act_pos, ld_act_pos, M, (int)E);
-    else { toc3d_set_error("toc3d_add_pos_rows: bad dtype"); return TOC3D_ERR_ARG; }
+    if (int rc = toc3d_dispatch_act<ACT_BF16 | ACT_F32>("toc3d_add_pos_rows", dtype, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            toc3d_launch(add_pos_kernel<T>, grid, dim3(256), 0, as_stream(stream), x, ldx, pos, ldp, (T*)out_act, ld_act, (T*)out_act_pos, ld_act_pos, M, (int)E);
+        })) return rc;
     TOC3D_LAUNCH_CHECK("toc3d_add_pos_rows");
     return TOC3D_OK;
 }

@@ -10,8 +10,7 @@
 // precision.  The per-token scorer is HBM-bound (one read of x); the query side is 64 x 256 numbers and is
 // latency-bound, so it is fused into one launch per stage with weights pre-transposed for coalesced reads.
 // No fast-math intrinsics: sin/cos arguments reach 5e10 and need full range reduction.
-#include "capi.h"
-#include "common.h"
+#include "act_rows.h"
 #include "../../include/toc3d_streams.h"
 
 namespace {
@@ -511,8 +510,6 @@ __global__ __launch_bounds__(256) void gumbel_noise_kernel(float* __restrict__ o
 constexpr int64_t kMaxCount = 0x7fffffff;     // the kernels index rows, columns and workgroups in 32 bits
 constexpr int64_t kMaxGridY = 65535;
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p % 16) == 0; }
-
 }  // namespace
 
 extern "C" {
@@ -581,7 +578,7 @@ int toc3d_score_tokens(const float* x, int64_t C, const float* mask, const float
     TOC3D_REQUIRE(C % 4 == 0 && views_per_frame > 0 && V % views_per_frame == 0, "toc3d_score_tokens: bad dims");
     TOC3D_REQUIRE(C > 0 && C <= kMaxCount && views_per_frame <= kMaxCount, "toc3d_score_tokens: C / views_per_frame too large or C not positive (counted in 32 bits)");
     // float4 loads of x + row * C and of wc + b * 2 C: with C % 4 == 0 every row is 16-byte aligned when its base is
-    TOC3D_REQUIRE(aligned16(x) && aligned16(wc), "toc3d_score_tokens: x and wc must be 16-byte aligned");
+    TOC3D_REQUIRE(aligned(x, 16) && aligned(wc, 16), "toc3d_score_tokens: x and wc must be 16-byte aligned");
     if (V <= 0 || T <= 0) return TOC3D_OK;
     TOC3D_REQUIRE(V <= kMaxCount && T <= kMaxCount && (V * T + 3) / 4 <= kMaxCount, "toc3d_score_tokens: too many tokens (T, V and ceil(V * T / 4) are counted in 32 bits)");
     const int64_t M = V * T;
@@ -593,7 +590,7 @@ int toc3d_score_tokens(const float* x, int64_t C, const float* mask, const float
 
 int toc3d_gumbel_noise(float* out, int64_t n, uint64_t seed, uint64_t* state, toc3d_stream_t stream) {
     TOC3D_REQUIRE(out && state && n >= 0, "toc3d_gumbel_noise: bad arguments");
-    TOC3D_REQUIRE(((uintptr_t)out % 16) == 0 && ((uintptr_t)state % 8) == 0, "toc3d_gumbel_noise: out must be 16-byte, state 8-byte aligned");
+    TOC3D_REQUIRE(aligned(out, 16) && aligned(state, 8), "toc3d_gumbel_noise: out must be 16-byte, state 8-byte aligned");
     if (n == 0) return TOC3D_OK;
     const int64_t blocks = (n + 1023) / 1024;
     TOC3D_REQUIRE(blocks <= 0x7fffffff, "toc3d_gumbel_noise: n too large");
@@ -616,15 +613,14 @@ int toc3d_score_head(int dtype, const void* f, int64_t ld, int64_t kdim, const f
     TOC3D_REQUIRE(kdim % 8 == 0 && ld >= kdim && ld % 8 == 0, "toc3d_score_head: kdim / ld must be multiples of 8");
     TOC3D_REQUIRE(kdim >= 0 && kdim <= kMaxCount, "toc3d_score_head: bad kdim (counted in 32 bits)");
     // eight elements per load: two float4 (f32) or one 16-byte bf16x8; ld % 8 == 0 keeps every row of either type 16-byte aligned when f is
-    TOC3D_REQUIRE(aligned16(f), "toc3d_score_head: f must be 16-byte aligned");
+    TOC3D_REQUIRE(aligned(f, 16), "toc3d_score_head: f must be 16-byte aligned");
     if (M <= 0) return TOC3D_OK;
     TOC3D_REQUIRE(M <= 4 * kMaxCount, "toc3d_score_head: too many rows (ceil(M / 4) is counted in 32 bits)");
     dim3 grid((unsigned)((M + 3) / 4));
-    if (dtype == TOC3D_BF16)
-        toc3d_launch(score_head_kernel<bf16_t>, grid, dim3(256), 0, as_stream(stream), (const bf16_t*)f, ld, (int)kdim, w, b, gumbel, M, pred, score, mask_out);
-    else if (dtype == TOC3D_F32)
-        toc3d_launch(score_head_kernel<float>, grid, dim3(256), 0, as_stream(stream), (const float*)f, ld, (int)kdim, w, b, gumbel, M, pred, score, mask_out);
-    else { toc3d_set_error("toc3d_score_head: bad dtype"); return TOC3D_ERR_ARG; }
+    if (int rc = toc3d_dispatch_act<ACT_BF16 | ACT_F32>("toc3d_score_head", dtype, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            toc3d_launch(score_head_kernel<T>, grid, dim3(256), 0, as_stream(stream), (const T*)f, ld, (int)kdim, w, b, gumbel, M, pred, score, mask_out);
+        })) return rc;
     TOC3D_LAUNCH_CHECK("toc3d_score_head");
     return TOC3D_OK;
 }
@@ -637,20 +633,19 @@ int toc3d_score_head_frames(int dtype, const void* f, int64_t ld, int64_t kdim, 
     TOC3D_REQUIRE(f && w && b && frame_new && pred && score && mask_out, "toc3d_score_head_frames: null buffer");
     TOC3D_REQUIRE(kdim % 8 == 0 && ld >= kdim && ld % 8 == 0, "toc3d_score_head_frames: kdim / ld must be multiples of 8");
     TOC3D_REQUIRE(kdim >= 0 && kdim <= kMaxCount, "toc3d_score_head_frames: bad kdim (counted in 32 bits)");
-    TOC3D_REQUIRE(aligned16(f), "toc3d_score_head_frames: f must be 16-byte aligned");
-    TOC3D_REQUIRE(dtype == TOC3D_BF16 || dtype == TOC3D_F32, "toc3d_score_head_frames: bad dtype");
+    TOC3D_REQUIRE(aligned(f, 16), "toc3d_score_head_frames: f must be 16-byte aligned");
+    TOC3D_REQUIRE(act_served(ACT_BF16 | ACT_F32, dtype), "toc3d_score_head_frames: bad dtype");
     TOC3D_REQUIRE(rows_per_frame > 0, "toc3d_score_head_frames: rows_per_frame must be positive");
     if (M <= 0) return TOC3D_OK;
     // whole frames only: frame_new has M / rows_per_frame entries, and row / rows_per_frame stays inside it
     TOC3D_REQUIRE(M % rows_per_frame == 0, "toc3d_score_head_frames: M must be a multiple of rows_per_frame");
     TOC3D_REQUIRE(M <= 4 * kMaxCount, "toc3d_score_head_frames: too many rows (ceil(M / 4) is counted in 32 bits)");
     dim3 grid((unsigned)((M + 3) / 4));
-    if (dtype == TOC3D_BF16)
-        toc3d_launch(score_head_frames_kernel<bf16_t>, grid, dim3(256), 0, as_stream(stream), (const bf16_t*)f, ld, (int)kdim, w, b, gumbel, frame_new,
-                     rows_per_frame, M, pred, score, mask_out);
-    else
-        toc3d_launch(score_head_frames_kernel<float>, grid, dim3(256), 0, as_stream(stream), (const float*)f, ld, (int)kdim, w, b, gumbel, frame_new,
-                     rows_per_frame, M, pred, score, mask_out);
+    if (int rc = toc3d_dispatch_act<ACT_BF16 | ACT_F32>("toc3d_score_head_frames", dtype, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            toc3d_launch(score_head_frames_kernel<T>, grid, dim3(256), 0, as_stream(stream), (const T*)f, ld, (int)kdim, w, b, gumbel, frame_new, rows_per_frame, M,
+                         pred, score, mask_out);
+        })) return rc;
     TOC3D_LAUNCH_CHECK("toc3d_score_head_frames");
     return TOC3D_OK;
 }
@@ -662,9 +657,10 @@ int toc3d_global_mean_half(int dtype, void* t, int64_t ld, int64_t V, int64_t T,
     TOC3D_REQUIRE(T <= kMaxCount, "toc3d_global_mean_half: too many tokens per view (T is counted in 32 bits)");
     TOC3D_REQUIRE(V <= kMaxGridY, "toc3d_global_mean_half: too many views (V is a grid dimension, at most 65535)");
     dim3 grid((unsigned)((C / 2 + 63) / 64), (unsigned)V);
-    if (dtype == TOC3D_BF16) toc3d_launch(global_mean_half_kernel<bf16_t>, grid, dim3(256), 0, as_stream(stream), (bf16_t*)t, ld, (int)T, (int)C);
-    else if (dtype == TOC3D_F32) toc3d_launch(global_mean_half_kernel<float>, grid, dim3(256), 0, as_stream(stream), (float*)t, ld, (int)T, (int)C);
-    else { toc3d_set_error("toc3d_global_mean_half: bad dtype"); return TOC3D_ERR_ARG; }
+    if (int rc = toc3d_dispatch_act<ACT_BF16 | ACT_F32>("toc3d_global_mean_half", dtype, [&](auto tag) {
+            using E = typename decltype(tag)::type;          // (T is the token count here)
+            toc3d_launch(global_mean_half_kernel<E>, grid, dim3(256), 0, as_stream(stream), (E*)t, ld, (int)T, (int)C);
+        })) return rc;
     TOC3D_LAUNCH_CHECK("toc3d_global_mean_half");
     return TOC3D_OK;
 }
@@ -688,9 +684,10 @@ int toc3d_im2col_3x3(int dtype, const float* x, void* out, int64_t ldo, int64_t 
     TOC3D_REQUIRE(x && out && ldo >= 9 * C, "toc3d_im2col_3x3: bad arguments");
     const int64_t M = V * h * w;
     if (M <= 0) return TOC3D_OK;
-    if (dtype == TOC3D_BF16) toc3d_launch(im2col_3x3_kernel<bf16_t>, dim3((unsigned)M), dim3(256), 0, as_stream(stream), x, (bf16_t*)out, ldo, (int)V, (int)h, (int)w, (int)C);
-    else if (dtype == TOC3D_F32) toc3d_launch(im2col_3x3_kernel<float>, dim3((unsigned)M), dim3(256), 0, as_stream(stream), x, (float*)out, ldo, (int)V, (int)h, (int)w, (int)C);
-    else { toc3d_set_error("toc3d_im2col_3x3: bad dtype"); return TOC3D_ERR_ARG; }
+    if (int rc = toc3d_dispatch_act<ACT_BF16 | ACT_F32>("toc3d_im2col_3x3", dtype, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            toc3d_launch(im2col_3x3_kernel<T>, dim3((unsigned)M), dim3(256), 0, as_stream(stream), x, (T*)out, ldo, (int)V, (int)h, (int)w, (int)C);
+        })) return rc;
     TOC3D_LAUNCH_CHECK("toc3d_im2col_3x3");
     return TOC3D_OK;
 }

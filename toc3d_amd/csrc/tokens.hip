@@ -7,8 +7,7 @@
 // (toc3d_utils.py:28-70), fast-token update (toc3d_eva_vit.py:449-467).
 //
 // All arithmetic is f32; rows are moved with 16-byte accesses, one wavefront (64 lanes) per token row.
-#include "capi.h"
-#include "common.h"
+#include "act_rows.h"
 
 // Row blocks -> XCDs (round 5).  Workgroup b of a launch runs on XCD b % 8; the GEMMs give every XCD a contiguous band of row tiles (xcd_remap / order 1), and what a producer
 // leaves in its XCD's L2 is worth 7-8 % of the frame (profiles/r05_nt_stores.txt).  With plain `row = 4 b + wave` a row kernel's rows are dealt round robin over the XCDs: its
@@ -29,7 +28,9 @@ constexpr int64_t TOKEN_ROWS_MAX = 0x7fffffffLL - 1024;
 
 // ---------------------------------------------------------------------------------------------------
 // LayerNorm of one row held by one wavefront.  v[i] = float4 #(lane + 64 i) of the row (nvec valid).
-// Two-pass statistics (mean, then centred variance), biased variance, like torch.nn.LayerNorm.
+// Two-pass statistics (mean, then centred variance), biased variance, like torch.nn.LayerNorm.  The squares of a
+// float4 are paired, (d0^2 + d1^2) + (d2^2 + d3^2); the head's row kernels (head_outputs.hip, head_queries.hip) add theirs one by one.  That
+// rounding decides near-tie top-k selections (tests/test_gpu_parity_bf16.py::test_vitl_1600_fp32_matches_reference): the forms stay apart.
 // ---------------------------------------------------------------------------------------------------
 template <int MAXV>
 TOC3D_DEV void wave_ln_stats(const f32x4 (&v)[MAXV], int nvec, int lane, int C, float eps, float& mean, float& rstd) {
@@ -48,17 +49,6 @@ TOC3D_DEV void wave_ln_stats(const f32x4 (&v)[MAXV], int nvec, int lane, int C, 
     rstd = 1.0f / sqrtf(wave_sum(q) / (float)C + eps);
 }
 
-static bool planes_rows_ok(const void* p, int64_t ld) { return ((uintptr_t)p % 128) == 0 && ld % 32 == 0; }
-
-template <typename T> TOC3D_DEV void store4(T* p, f32x4 v);
-template <> TOC3D_DEV void store4<float>(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-template <> TOC3D_DEV void store4<f32p_t>(f32p_t* p, f32x4 v) { const float x[4] = {v[0], v[1], v[2], v[3]}; store4_planes(p, x); }
-template <> TOC3D_DEV void store4<bf16_t>(bf16_t* p, f32x4 v) {
-    bf16x4 b;
-    b[0] = (bf16_t)v[0]; b[1] = (bf16_t)v[1]; b[2] = (bf16_t)v[2]; b[3] = (bf16_t)v[3];
-    *reinterpret_cast<bf16x4*>(p) = b;
-}
-
 template <typename T, int MAXV>
 TOC3D_DEV void wave_ln_write(const f32x4 (&v)[MAXV], int nvec, int lane, float mean, float rstd, const float* __restrict__ gamma,
                              const float* __restrict__ beta, T* __restrict__ out) {
@@ -68,10 +58,10 @@ TOC3D_DEV void wave_ln_write(const f32x4 (&v)[MAXV], int nvec, int lane, float m
         if (vi < nvec) {
             const f32x4 gm = *reinterpret_cast<const f32x4*>(gamma + 4 * vi);
             const f32x4 bt = *reinterpret_cast<const f32x4*>(beta + 4 * vi);
-            f32x4 y;
+            float y[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) y[e] = (v[i][e] - mean) * rstd * gm[e] + bt[e];
-            store4<T>(out + 4 * vi, y);
+            put4(out + 4 * vi, y);
         }
     }
 }
@@ -723,15 +713,14 @@ int toc3d_layernorm_rows(int dtype, const float* x, int64_t ldx, const int32_t* 
     if (M <= 0) return TOC3D_OK;
     dim3 grid((unsigned)((M + 3) / 4)), block(256);
     hipStream_t s = as_stream(stream);
-#define LNR(T, MV) toc3d_launch((ln_rows_kernel<T, MV>), grid, block, 0, s, x, ldx, row_index, row_scale, gamma, beta, eps, (T*)out, ldo, (int)M, (int)C)
-    if (dtype == TOC3D_BF16) { if (C <= 1024) LNR(bf16_t, 4); else LNR(bf16_t, 8); }
-    else if (dtype == TOC3D_F32) { if (C <= 1024) LNR(float, 4); else LNR(float, 8); }
-    else if (dtype == TOC3D_F32X3P) {            // f32 arithmetic, rows written as (hi, lo) planes: the A operand of a bf16 x 3 GEMM
-        TOC3D_REQUIRE(planes_rows_ok(out, ldo), "toc3d_layernorm_rows: rows of (hi, lo) planes start on 128-byte boundaries (out aligned, ldo a multiple of 32)");
-        if (C <= 1024) LNR(f32p_t, 4); else LNR(f32p_t, 8);
-    }
-    else { toc3d_set_error("toc3d_layernorm_rows: bad dtype"); return TOC3D_ERR_ARG; }
-#undef LNR
+    // TOC3D_F32X3P: f32 arithmetic, rows written as (hi, lo) planes: the A operand of a bf16 x 3 GEMM
+    TOC3D_REQUIRE(dtype != TOC3D_F32X3P || planes_rows_ok(out, ldo), "toc3d_layernorm_rows: rows of (hi, lo) planes start on 128-byte boundaries (out aligned, ldo a multiple of 32)");
+    if (int rc = toc3d_dispatch_act<ACT_ANY>("toc3d_layernorm_rows", dtype, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            auto launch = [&](auto kernel) { toc3d_launch(kernel, grid, block, 0, s, x, ldx, row_index, row_scale, gamma, beta, eps, (T*)out, ldo, (int)M, (int)C); };
+            if (C <= 1024) launch(ln_rows_kernel<T, 4>);
+            else launch(ln_rows_kernel<T, 8>);
+        })) return rc;
     TOC3D_LAUNCH_CHECK("toc3d_layernorm_rows");
     return TOC3D_OK;
 }
@@ -744,12 +733,14 @@ int toc3d_layernorm_act(int dtype, const void* x, int64_t ldx, const float* gamm
     if (M <= 0) return TOC3D_OK;
     dim3 grid((unsigned)((M + 3) / 4)), block(256);
     hipStream_t s = as_stream(stream);
-#define LNA(T, MC) toc3d_launch((ln_act_kernel<T, MC>), grid, block, 0, s, (const T*)x, ldx, gamma, beta, eps, (T*)out, ldo, (int)M, (int)n)
     const int mc = (int)((ldo / 8 + 63) / 64);
-    if (dtype == TOC3D_BF16) { if (mc <= 2) LNA(bf16_t, 2); else if (mc <= 6) LNA(bf16_t, 6); else LNA(bf16_t, 12); }
-    else if (dtype == TOC3D_F32) { if (mc <= 2) LNA(float, 2); else if (mc <= 6) LNA(float, 6); else LNA(float, 12); }
-    else { toc3d_set_error("toc3d_layernorm_act: bad dtype"); return TOC3D_ERR_ARG; }
-#undef LNA
+    if (int rc = toc3d_dispatch_act<ACT_BF16 | ACT_F32>("toc3d_layernorm_act", dtype, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            auto launch = [&](auto kernel) { toc3d_launch(kernel, grid, block, 0, s, (const T*)x, ldx, gamma, beta, eps, (T*)out, ldo, (int)M, (int)n); };
+            if (mc <= 2) launch(ln_act_kernel<T, 2>);
+            else if (mc <= 6) launch(ln_act_kernel<T, 6>);
+            else launch(ln_act_kernel<T, 12>);
+        })) return rc;
     TOC3D_LAUNCH_CHECK("toc3d_layernorm_act");
     return TOC3D_OK;
 }
@@ -807,21 +798,15 @@ static int launch_gather(int dtype, const float* x, int64_t C, const int32_t* to
     dim3 grid((unsigned)(nW + (rows + 15) / 16)), block(1024);
     const size_t lds = (size_t)16 * C * 4;
     hipStream_t s = as_stream(stream);
-#define TOC3D_GATHER(T)                                                                                                             \
-    do {                                                                                                                            \
-        static Toc3dLdsAttr attr;                                                                                                   \
-        attr.ensure(reinterpret_cast<const void*>(&gather_merge_ln_kernel<T, 4>), 65536);                                        \
-        toc3d_launch((gather_merge_ln_kernel<T, 4>), grid, block, lds, s, x, (int)C, tok, wgt, crow_tok, rep_row, (int)nW, (int)N, (int)k, (int)rows, \
-                     gamma, beta, eps, shortcut, (T*)a_out, lda, (int)(kept_copy != 0));                                            \
-    } while (0)
-    if (dtype == TOC3D_BF16) TOC3D_GATHER(bf16_t);
-    else if (dtype == TOC3D_F32) TOC3D_GATHER(float);
-    else if (dtype == TOC3D_F32X3P) {            // a_out as (hi, lo) planes (the q|k|v GEMM's A operand); shortcut stays f32
-        TOC3D_REQUIRE(planes_rows_ok(a_out, lda), "toc3d_gather_merge_ln: rows of (hi, lo) planes start on 128-byte boundaries (a_out aligned, lda a multiple of 32)");
-        TOC3D_GATHER(f32p_t);
-    }
-    else { toc3d_set_error("toc3d_gather_merge_ln: bad dtype"); return TOC3D_ERR_ARG; }
-#undef TOC3D_GATHER
+    // TOC3D_F32X3P: a_out as (hi, lo) planes (the q|k|v GEMM's A operand); shortcut stays f32
+    TOC3D_REQUIRE(dtype != TOC3D_F32X3P || planes_rows_ok(a_out, lda), "toc3d_gather_merge_ln: rows of (hi, lo) planes start on 128-byte boundaries (a_out aligned, lda a multiple of 32)");
+    if (int rc = toc3d_dispatch_act<ACT_ANY>("toc3d_gather_merge_ln", dtype, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            static Toc3dLdsAttr attr;                    // one per element type
+            attr.ensure(reinterpret_cast<const void*>(&gather_merge_ln_kernel<T, 4>), 65536);
+            toc3d_launch(gather_merge_ln_kernel<T, 4>, grid, block, lds, s, x, (int)C, tok, wgt, crow_tok, rep_row, (int)nW, (int)N, (int)k, (int)rows,
+                         gamma, beta, eps, shortcut, (T*)a_out, lda, (int)(kept_copy != 0));
+        })) return rc;
     TOC3D_LAUNCH_CHECK("toc3d_gather_merge_ln");
     return TOC3D_OK;
 }
@@ -858,7 +843,7 @@ int toc3d_gather_merge_ln_split(int dtype, const float* x, int64_t C, const int3
     TOC3D_REQUIRE(x && tok && wgt && crow_tok && rep_row && gamma && beta && shortcut && a_out, "toc3d_gather_merge_ln_split: null buffer");
     TOC3D_REQUIRE(C > 0 && C % 4 == 0 && C <= 1024, "toc3d_gather_merge_ln_split: C=%lld must be a multiple of 4 and <= 1024", (long long)C);
     TOC3D_REQUIRE(k >= 0 && k < N && lda >= C && lda % 4 == 0 && rows >= nW && N - k <= 1024, "toc3d_gather_merge_ln_split: bad k / lda / rows");
-    TOC3D_REQUIRE(scratch && ((uintptr_t)scratch % 256) == 0 && scratch_bytes >= toc3d_gather_merge_ln_scratch_bytes(nW, C),
+    TOC3D_REQUIRE(scratch && aligned(scratch, 256) && scratch_bytes >= toc3d_gather_merge_ln_scratch_bytes(nW, C),
                   "toc3d_gather_merge_ln_split: scratch of toc3d_gather_merge_ln_scratch_bytes(nW, C) bytes, 256-byte aligned, zeroed once by the caller");
     TOC3D_REQUIRE(nW * 4 <= TOC3D_GATHER_SPLIT_COUNTER_BYTES, "toc3d_gather_merge_ln_split: at most %d windows per launch", TOC3D_GATHER_SPLIT_COUNTER_BYTES / 4);
     TOC3D_REQUIRE(N <= TOKEN_ROWS_MAX && rows <= TOKEN_ROWS_MAX, "toc3d_gather_merge_ln_split: too many rows (N, rows: the kernel counts in 32 bits)");
@@ -869,20 +854,18 @@ int toc3d_gather_merge_ln_split(int dtype, const float* x, int64_t C, const int3
     dim3 grid((unsigned)(((nW + 7) / 8) * 8 * sp + (rows + wpb - 1) / wpb)), block(64 * wpb);
     const size_t lds = (size_t)C * 4 + 16;
     hipStream_t s = as_stream(stream);
-#define TOC3D_GSPLIT(T, SP)                                                                                                                       \
-    toc3d_launch((gather_merge_ln_split_kernel<T, 4, SP>), grid, block, lds, s, x, (int)C, tok, wgt, crow_tok, rep_row, (int)nW, (int)N, (int)k, (int)rows, \
-                 gamma, beta, eps, shortcut, (T*)a_out, lda, (int)(kept_copy != 0), partials, counters)
-#define TOC3D_GSPLIT_T(T)                                                                                            \
-    do { if (sp == 2) TOC3D_GSPLIT(T, 2); else if (sp == 4) TOC3D_GSPLIT(T, 4); else if (sp == 8) TOC3D_GSPLIT(T, 8); else TOC3D_GSPLIT(T, 16); } while (0)
-    if (dtype == TOC3D_BF16) TOC3D_GSPLIT_T(bf16_t);
-    else if (dtype == TOC3D_F32) TOC3D_GSPLIT_T(float);
-    else if (dtype == TOC3D_F32X3P) {
-        TOC3D_REQUIRE(planes_rows_ok(a_out, lda), "toc3d_gather_merge_ln_split: rows of (hi, lo) planes start on 128-byte boundaries (a_out aligned, lda a multiple of 32)");
-        TOC3D_GSPLIT_T(f32p_t);
-    }
-    else { toc3d_set_error("toc3d_gather_merge_ln_split: bad dtype"); return TOC3D_ERR_ARG; }
-#undef TOC3D_GSPLIT_T
-#undef TOC3D_GSPLIT
+    TOC3D_REQUIRE(dtype != TOC3D_F32X3P || planes_rows_ok(a_out, lda), "toc3d_gather_merge_ln_split: rows of (hi, lo) planes start on 128-byte boundaries (a_out aligned, lda a multiple of 32)");
+    if (int rc = toc3d_dispatch_act<ACT_ANY>("toc3d_gather_merge_ln_split", dtype, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            auto launch = [&](auto kernel) {
+                toc3d_launch(kernel, grid, block, lds, s, x, (int)C, tok, wgt, crow_tok, rep_row, (int)nW, (int)N, (int)k, (int)rows, gamma, beta, eps, shortcut,
+                             (T*)a_out, lda, (int)(kept_copy != 0), partials, counters);
+            };
+            if (sp == 2) launch(gather_merge_ln_split_kernel<T, 4, 2>);
+            else if (sp == 4) launch(gather_merge_ln_split_kernel<T, 4, 4>);
+            else if (sp == 8) launch(gather_merge_ln_split_kernel<T, 4, 8>);
+            else launch(gather_merge_ln_split_kernel<T, 4, 16>);
+        })) return rc;
     TOC3D_LAUNCH_CHECK("toc3d_gather_merge_ln_split");
     return TOC3D_OK;
 }
@@ -918,15 +901,15 @@ int toc3d_rebase_layernorm_rows(int dtype, float* slow, int64_t C, const int32_t
     if (rows <= 0) return TOC3D_OK;
     dim3 grid((unsigned)((rows + 3) / 4)), block(256);
     hipStream_t s = as_stream(stream);
-#define LNB(T, MV) toc3d_launch((ln_rebase_kernel<T, MV>), grid, block, 0, s, slow, (int)C, rep_index, tok, wgt, (int)N, (int)k, rep_raw1, rep_raw2, gamma, beta, eps, (T*)out, ldo, (int)rows)
-    if (dtype == TOC3D_BF16) { if (C <= 1024) LNB(bf16_t, 4); else LNB(bf16_t, 8); }
-    else if (dtype == TOC3D_F32) { if (C <= 1024) LNB(float, 4); else LNB(float, 8); }
-    else if (dtype == TOC3D_F32X3P) {
-        TOC3D_REQUIRE(planes_rows_ok(out, ldo), "toc3d_rebase_layernorm_rows: rows of (hi, lo) planes start on 128-byte boundaries (out aligned, ldo a multiple of 32)");
-        if (C <= 1024) LNB(f32p_t, 4); else LNB(f32p_t, 8);
-    }
-    else { toc3d_set_error("toc3d_rebase_layernorm_rows: bad dtype"); return TOC3D_ERR_ARG; }
-#undef LNB
+    TOC3D_REQUIRE(dtype != TOC3D_F32X3P || planes_rows_ok(out, ldo), "toc3d_rebase_layernorm_rows: rows of (hi, lo) planes start on 128-byte boundaries (out aligned, ldo a multiple of 32)");
+    if (int rc = toc3d_dispatch_act<ACT_ANY>("toc3d_rebase_layernorm_rows", dtype, [&](auto tag) {
+            using T = typename decltype(tag)::type;
+            auto launch = [&](auto kernel) {
+                toc3d_launch(kernel, grid, block, 0, s, slow, (int)C, rep_index, tok, wgt, (int)N, (int)k, rep_raw1, rep_raw2, gamma, beta, eps, (T*)out, ldo, (int)rows);
+            };
+            if (C <= 1024) launch(ln_rebase_kernel<T, 4>);
+            else launch(ln_rebase_kernel<T, 8>);
+        })) return rc;
     TOC3D_LAUNCH_CHECK("toc3d_rebase_layernorm_rows");
     return TOC3D_OK;
 }
@@ -934,8 +917,7 @@ int toc3d_rebase_layernorm_rows(int dtype, float* slow, int64_t C, const int32_t
 int toc3d_copy_bytes(void* dst, const void* src, int64_t nbytes, toc3d_stream_t stream) {
     TOC3D_REQUIRE(nbytes >= 0 && (nbytes == 0 || (dst && src)), "toc3d_copy_bytes: bad arguments");
     if (nbytes == 0) return TOC3D_OK;
-    const bool aligned = ((uintptr_t)dst % 16) == 0 && ((uintptr_t)src % 16) == 0;
-    const int64_t n16 = aligned ? nbytes / 16 : 0;
+    const int64_t n16 = aligned(dst, 16) && aligned(src, 16) ? nbytes / 16 : 0;
     const int64_t work = n16 > 0 ? n16 : nbytes;
     const int blocks = (int)((work + 255) / 256 < 2048 ? (work + 255) / 256 : 2048);
     toc3d_launch(copy_bytes_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), (char*)dst, (const char*)src, n16, nbytes);
