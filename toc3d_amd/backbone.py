@@ -22,14 +22,15 @@ from __future__ import annotations
 
 import math
 from functools import partial
-from typing import Dict
+from types import SimpleNamespace
+from typing import Dict, NamedTuple, Optional
 
 import torch
 import torch.nn as nn
 
 from . import gemm, lib
 from .gemm import DEFAULT_PRECISION, round_up              # (DEFAULT_PRECISION: re-exported, the configs and tests read it from here)
-from .plan import MODES, DerivedState, EagerExec, run_frame
+from .plan import MODES, DerivedState, EagerExec, lru, run_frame
 from .staged import MLN, dim_t
 from .synth import MOTION_DIM, QUERY_DIM, rope_tables
 
@@ -141,6 +142,21 @@ def _init_weights(m):
 # ------------------------------------------------------------------------------------------------
 # shared engine: weight packing + per-shape plan + the launch sequence
 # ------------------------------------------------------------------------------------------------
+class Windows(NamedTuple):
+    """One window list as the attention launches take it (include/toc3d.h, toc3d_window_attention*), built once where its buffers are allocated: the static dense
+    map of a window type (``plan["dense"][L]["win"]``: ``npad``, no ``count_k``) or a scorer stage's selection (``plan["sel"][(st, L)]["win"]``: ``count_k``, pads
+    in the block's pad rows).  ``rc``: RoPE position of every row (the pre-rotated path); ``stride``: slots per window.  The dicts keep the same tensors."""
+    rc: Optional[torch.Tensor]
+    rows: torch.Tensor
+    slots: torch.Tensor
+    count_q: torch.Tensor
+    count_k: Optional[torch.Tensor]
+    npad: Optional[torch.Tensor]
+    stride: int
+    nwin: int
+    max_count: int
+
+
 def schedule_defaults(precision):
     """The launch-schedule switches of the backbones and their shipped defaults per precision.  Plain attributes (``model.fold_norm2 = False`` before the
     first forward, or ``schedule=dict(...)`` at construction); every one is pinned by a test (tests/test_gpu_e2e.py, tests/test_cpu_abi.py).  The
@@ -268,47 +284,42 @@ class _BackboneBase(DerivedState, nn.Module):
     def _block_side(self, i):
         return self.global_window_size if i in self.global_attn_indexes else self.window_size
 
-    @staticmethod
-    def _f32(t):
-        return t.detach().float().contiguous()
-
     def _pack_blocks(self, dev):
         C, Hd = self.embed_dim, self.hidden_dim
         Hp = round_up(Hd, 64)
-        pack = partial(gemm.pack_weight, dts=self._dts)
+        pk = gemm.Packer(self._dts, dev)
+        f = pk.f32
         blocks = []
         for blk in self.blocks:
             a, m = blk.attn, blk.mlp
             p = {}
-            p["wqkv"] = pack(torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight], 0))
             zb = torch.zeros(C, device=dev)
             qb = a.q_bias if a.q_bias is not None else zb
             vb = a.v_bias if a.v_bias is not None else zb
-            p["bqkv"] = self._f32(torch.cat([qb, zb, vb]))
-            p["v_bias"] = self._f32(vb)
-            p["wproj"], p["bproj"] = pack(a.proj.weight), self._f32(a.proj.bias)
+            p["wqkv"], p["bqkv"] = pk.wb(torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight], 0), torch.cat([qb, zb, vb]))
+            p["v_bias"] = f(vb)
+            p["wproj"], p["bproj"] = pk.wb(a.proj.weight, a.proj.bias)
             w12 = torch.empty(2 * Hp, C, dtype=self._tdt, device=dev)
             b12 = torch.empty(2 * Hp, dtype=torch.float32, device=dev)
-            lib.call("toc3d_pack_swiglu", self._dt, self._f32(m.w1.weight), self._f32(m.w2.weight), self._f32(m.w1.bias),
-                     self._f32(m.w2.bias), Hd, C, w12, b12, Hp, C, lib.stream_ptr())
+            lib.call("toc3d_pack_swiglu", self._dt, f(m.w1.weight), f(m.w2.weight), f(m.w1.bias), f(m.w2.bias), Hd, C, w12, b12, Hp, C, lib.stream_ptr())
             p["w12"], p["b12"] = w12, b12                         # (-> planes below, after the lnfold pack may have rewritten it)
             if self.fold_norm2:                                   # gamma2-scaled interleaved weights + (c1, c2) in packed column order; replaces w12 / b12
                 p["c1_12"], p["c2_12"] = torch.empty(2 * Hp, device=dev), torch.empty(2 * Hp, device=dev)
-                lib.call("toc3d_pack_swiglu_lnfold", self._dt, self._f32(m.w1.weight), self._f32(m.w2.weight), self._f32(m.w1.bias), self._f32(m.w2.bias),
-                         self._f32(blk.norm2.weight), self._f32(blk.norm2.bias), Hd, C, w12, p["c1_12"], p["c2_12"], Hp, C, lib.stream_ptr())
+                lib.call("toc3d_pack_swiglu_lnfold", self._dt, f(m.w1.weight), f(m.w2.weight), f(m.w1.bias), f(m.w2.bias),
+                         f(blk.norm2.weight), f(blk.norm2.bias), Hd, C, w12, p["c1_12"], p["c2_12"], Hp, C, lib.stream_ptr())
             if self.fold_ffn_ln:
                 N3, K3 = m.w3.weight.shape
                 w3f = torch.empty(round_up(N3, 128), Hp, dtype=self._tdt, device=dev)
                 p["c1"], p["c2"] = torch.empty(N3, device=dev), torch.empty(N3, device=dev)
-                lib.call("toc3d_pack_weight_lnfold", self._dt, self._f32(m.w3.weight), self._f32(m.ffn_ln.weight), self._f32(m.ffn_ln.bias),
-                         self._f32(m.w3.bias), N3, K3, w3f, w3f.shape[0], Hp, p["c1"], p["c2"], lib.stream_ptr())
+                lib.call("toc3d_pack_weight_lnfold", self._dt, f(m.w3.weight), f(m.ffn_ln.weight), f(m.ffn_ln.bias),
+                         f(m.w3.bias), N3, K3, w3f, w3f.shape[0], Hp, p["c1"], p["c2"], lib.stream_ptr())
                 p["w3"] = gemm.planes(w3f, self._dts)                       # gamma-scaled; c1 / c2 carry the mean and beta / bias terms
             else:
-                p["w3"], p["b3"] = pack(m.w3.weight), self._f32(m.w3.bias)
+                p["w3"], p["b3"] = pk.wb(m.w3.weight, m.w3.bias)
             gemm.planes(w12, self._dts)
             for n, mod in (("ln1", blk.norm1), ("ln2", blk.norm2), ("lnf", m.ffn_ln)):
-                p[n + "_w"], p[n + "_b"] = self._f32(mod.weight), self._f32(mod.bias)
-            p["cos"], p["sin"] = self._f32(a.rope.freqs_cos), self._f32(a.rope.freqs_sin)
+                p[n + "_w"], p[n + "_b"] = f(mod.weight), f(mod.bias)
+            p["cos"], p["sin"] = f(a.rope.freqs_cos), f(a.rope.freqs_sin)
             p["rope_side"] = self._check_axial_rope(p["cos"], p["sin"])
             if self.attn_rot:                                     # compact axial tables [2, L, 16]: one entry per frequency pair (the q|k|v GEMM's rotating epilogue)
                 L = p["rope_side"]
@@ -344,14 +355,15 @@ class _BackboneBase(DerivedState, nn.Module):
                                "(move the module to cuda)")
         lib.load()
         P = {"dev": dev}
-        C = self.embed_dim
-        P["w_patch"] = gemm.pack_weight(self.patch_embed.proj.weight.reshape(C, -1), self._dts)
-        P["b_patch"] = self._f32(self.patch_embed.proj.bias)
+        pk = gemm.Packer(self._dts, dev)
+        P["w_patch"], P["b_patch"] = pk.wb(self.patch_embed.proj.weight.reshape(self.embed_dim, -1), self.patch_embed.proj.bias)
         P["blocks"] = self._pack_blocks(dev)
         P["pos"] = {}                                   # (h, w) -> bicubic-resized abs-pos, built on first use
         if self.pos_embed is not None:                  # source grid (cls row dropped, eva_utils.py:240-243)
-            P["pos_embed"] = self._f32(self.pos_embed[0, 1:] if self.pretrain_use_cls_token else self.pos_embed[0]).clone()
+            P["pos_embed"] = pk.f32(self.pos_embed[0, 1:] if self.pretrain_use_cls_token else self.pos_embed[0]).clone()
         return P
+
+    _pack = _pack_common                                # what forward() packs on first use (ToC3DEVAViT adds the scorers and the pad rows)
 
     def _pos_for(self, h, w, dev):
         C = self.embed_dim
@@ -382,16 +394,17 @@ class _BackboneBase(DerivedState, nn.Module):
                 d[k] = d[k][perm].contiguous()
         return d
 
-    def _base_plan(self, V, H, W, dev, max_rows):
+    def _base_plan(self, V, H, W, x, B, max_rows=0):
+        """The work plan of one view group of ``B`` frames: ``x`` its rows of the master's residual stream, the activation buffers (``max_rows``: of the compact
+        rows too) and the static dense window lists."""
         C, Hp = self.embed_dim, round_up(self.hidden_dim, 64)
         p = self.patch_size
         h, w = H // p, W // p
         T, M = h * w, V * h * w
         R = max(M, max_rows)
-        tdt = self._tdt
+        tdt, dev = self._tdt, x.device
         Kc = self.in_chans * p * p
-        plan = dict(V=V, h=h, w=w, T=T, M=M,
-                    x=torch.empty(M, C, dtype=torch.float32, device=dev),
+        plan = dict(V=V, h=h, w=w, T=T, M=M, B=B, x=x,
                     a=torch.empty(R, C, dtype=tdt, device=dev),
                     qkv=torch.empty(R, 3 * C, dtype=tdt, device=dev),
                     att=torch.empty(R, C, dtype=tdt, device=dev),
@@ -410,7 +423,23 @@ class _BackboneBase(DerivedState, nn.Module):
             c = torch.arange(w, device=dev, dtype=torch.int32).view(1, 1, w).expand(V, h, w)
             for L, d in plan["dense"].items():
                 d["rc"] = (((r % L) << 16) | (c % L)).reshape(-1).contiguous()
+        for d in plan["dense"].values():
+            d["win"] = Windows(d.get("rc"), d["rows"], d["slots"], d["count"], None, d["npad"], d["N"], d["nW"], d["max_count"])
         return plan
+
+    _plan = _base_plan                                  # what _master_plan asks for per view group (ToC3DEVAViT adds the selections and the scorer's buffers)
+
+    def _master_plan(self, V, H, W, B, dev):
+        """The plan of one input shape: the residual stream ``x`` of all views, and per view group (_group_layout) a work plan on its row slice (whole 128-byte
+        lines: C * 4 bytes per token) with its first view / frame and their counts."""
+        h, w = H // self.patch_size, W // self.patch_size
+        T = h * w
+        m = dict(V=V, h=h, w=w, T=T, M=V * T, x=torch.empty(V * T, self.embed_dim, dtype=torch.float32, device=dev), groups=[])
+        for (v0, nv, f0, nf) in self._group_layout(V, B):
+            gp = self._plan(nv, H, W, m["x"][v0 * T:(v0 + nv) * T], nf)
+            gp["v0"], gp["nv"], gp["frame0"] = v0, nv, f0
+            m["groups"].append(gp)
+        return m
 
     def _linear(self, epi, A, W, bias, out, M, N, K, **kw):
         """One linear layer with a per-shape autotuned tile variant (gemm.linear; this model owns the table)."""
@@ -474,15 +503,6 @@ class _BackboneBase(DerivedState, nn.Module):
         """One frame in the configured launch mode (toc3d_amd/plan.py: eager / recorded plan / explicit hipGraph)."""
         run_frame(master.setdefault("launch", {}).setdefault(variant, {}), self.launch_mode, n_lanes, frame_fn, self._stream_pool)
 
-    def _attention(self, P, i, *args):
-        """toc3d_window_attention for block i; with ``prefetch_weights`` the launch also pulls the weights of the GEMMs that follow it
-        (this block's proj / w1|w2 / w3, the next block's q|k|v) towards the chip (toc3d_window_attention_pf)."""
-        s = lib.stream_ptr()
-        if not self.prefetch_weights:
-            lib.call("toc3d_window_attention", *args, s)
-            return
-        lib.call("toc3d_window_attention_pf", *args, *self._prefetch_args(P, i), s)
-
     def _prefetch_args(self, P, i):
         """(n_prefetch, prefetch_ptrs, prefetch_bytes, prefetch_workgroups) of block i's attention launch: the weights of the GEMMs that follow it."""
         bp = P["blocks"][i]
@@ -491,23 +511,29 @@ class _BackboneBase(DerivedState, nn.Module):
             ts = []
         return (len(ts), *lib.ptr_arrays(ts, min_len=1), self.prefetch_weights)
 
-    def _qkv_attention(self, P, i, plan, M, rope_rc, arows, aslots, count_q, count_k, npad, pad, stride, nwin, max_count, v_bias):
-        """q|k|v projection + windowed attention of block i on plan["a"] [M, C] -> plan["att"] (eva_vit.py:97-113, toc3d_eva_vit.py:495-512)."""
+    def _qkv_attention(self, P, i, plan, M, win: Windows):
+        """q|k|v projection + windowed attention of block i on plan["a"] [M, C] -> plan["att"] (eva_vit.py:97-113, toc3d_eva_vit.py:495-512), on the window list
+        ``win``: a dense map (pads folded analytically: ``npad`` and the block's v bias) or a selection (pads read from the block's pad rows)."""
         bp = P["blocks"][i]
-        C, dt = self.embed_dim, self._dt
-        if self._rot_ok(stride):
+        C = self.embed_dim
+        rot = self._rot_ok(win.stride)                  # decided once: the rotating GEMM epilogue, the rotated pad rows and the pre-rotated attention go together
+        v_bias = None if win.npad is None else bp["v_bias"]
+        pad = None if win.count_k is None else bp["pad_rot" if rot else "pad_qkv"]
+        args = (plan["qkv"], 3 * C, plan["att"], C, win.rows, win.slots, win.count_q, win.count_k, win.npad, pad, win.stride, win.nwin, win.max_count, self.num_heads)
+        if rot:
             self._linear(lib.EPI_QKV_ROPE, plan["a"], bp["wqkv"], bp["bqkv"], plan["qkv"], M, 3 * C, C,
-                         rope=(rope_rc, bp["rope_tab"], bp["rope_side"], lib.ATTN_ROT_Q_SCALE), a_planes=self._x3p, o_planes=self._x3p)
+                         rope=(win.rc, bp["rope_tab"], bp["rope_side"], lib.ATTN_ROT_Q_SCALE), a_planes=self._x3p, o_planes=self._x3p)
             if self._x3p:       # planes in, planes out; no weight prefetch riding on this form
-                lib.call("toc3d_window_attention_rot", lib.F32X3P, plan["qkv"], 3 * C, plan["att"], C, arows, aslots, count_q, count_k, npad, pad, stride, nwin, max_count,
-                         self.num_heads, v_bias, 0, None, None, 0, lib.stream_ptr())
-                return
-            lib.call("toc3d_window_attention_rot", dt, plan["qkv"], 3 * C, plan["att"], C, arows, aslots, count_q, count_k, npad, pad, stride, nwin, max_count,
-                     self.num_heads, v_bias, *self._prefetch_args(P, i), lib.stream_ptr())
+                lib.call("toc3d_window_attention_rot", lib.F32X3P, *args, v_bias, 0, None, None, 0, lib.stream_ptr())
+            else:
+                lib.call("toc3d_window_attention_rot", self._dt, *args, v_bias, *self._prefetch_args(P, i), lib.stream_ptr())
             return
         self._linear(lib.EPI_BIAS, plan["a"], bp["wqkv"], bp["bqkv"], plan["qkv"], M, 3 * C, C, a_planes=self._x3p)
-        self._attention(P, i, self._dt_attn, plan["qkv"], 3 * C, plan["att"], C, arows, aslots, count_q, count_k, npad, pad,
-                        stride, nwin, max_count, self.num_heads, bp["cos"], bp["sin"], bp["rope_side"], v_bias, 64 ** -0.5)
+        args = (self._dt_attn, *args, bp["cos"], bp["sin"], bp["rope_side"], v_bias, 64 ** -0.5)
+        if self.prefetch_weights:   # the launch also pulls the weights of the GEMMs that follow it (this block's proj / w1|w2 / w3, the next block's q|k|v) towards the chip
+            lib.call("toc3d_window_attention_pf", *args, *self._prefetch_args(P, i), lib.stream_ptr())
+        else:
+            lib.call("toc3d_window_attention", *args, lib.stream_ptr())
 
     def _rot_ok(self, stride):
         """The pre-rotated attention path serves this window size: bf16 up to 416 keys (K and V of a head whole in LDS); fp32x3 on planes any size of the model
@@ -560,11 +586,10 @@ class _BackboneBase(DerivedState, nn.Module):
         """Block.forward (eva_vit.py:247-268): LN -> window attention (pads folded analytically) -> +res; MLP -> +res."""
         s = lib.stream_ptr()
         bp = P["blocks"][i]
-        C, M, dt = self.embed_dim, plan["M"], self._dt
+        C, M = self.embed_dim, plan["M"]
         x = plan["x"]
-        dm = plan["dense"][self._block_side(i)]
         lib.call("toc3d_layernorm_rows", self._dt_rows, x, C, None, None, bp["ln1_w"], bp["ln1_b"], self.LN_EPS, plan["a"], C, M, C, s)
-        self._qkv_attention(P, i, plan, M, dm.get("rc"), dm["rows"], dm["slots"], dm["count"], None, dm["npad"], None, dm["N"], dm["nW"], dm["max_count"], bp["v_bias"])
+        self._qkv_attention(P, i, plan, M, plan["dense"][self._block_side(i)]["win"])
         self._proj(bp, plan, M, x, None, None)
         self._mlp(bp, plan, M, x, None, None)
 
@@ -597,6 +622,43 @@ class _BackboneBase(DerivedState, nn.Module):
         if x.dim() != 4 or x.shape[1] != self.in_chans or x.shape[2] % self.patch_size or x.shape[3] % self.patch_size:
             raise ValueError(f"expected (B*Nv, {self.in_chans}, H, W) with H, W multiples of {self.patch_size}, got {tuple(x.shape)}")
         return x.float().contiguous(), x.shape[2], x.shape[3]
+
+    # -- the frame driver: what both forwards do around their block loops ------------------------------------------------------------
+    def _master(self, x, frames=None):
+        """-> (checked input, its master plan): the weights packed on first use, the plan looked up under the input's shape, dtype, ``frames`` (the ToC3D
+        backbone's; the dense one has none: every view stands alone) and ``view_groups``.  Each plan holds ~1 GB of workspaces at full size: the 8 most recently
+        used are kept."""
+        x, H, W = self._check_input(x)
+        if self._packed is None:
+            self._packed = self._pack()
+            self._plans = {}
+        V = x.shape[0]
+        B = V if frames is None else frames
+        assert V % B == 0
+        key = (tuple(x.shape), x.dtype) + (() if frames is None else (frames,)) + (self.view_groups,)
+        return x, lru(self._plans, key, lambda: self._master_plan(V, H, W, B, x.device), 8)
+
+    def _drive(self, master, x, n_lanes, blocks, ahead=None, variant=None):
+        """One frame on ``n_lanes`` lanes, lanes 0..G-1 the view groups': the stem's im2col per group on the caller's stream, in front of the frame (it reads the
+        caller's tensor); then, in the configured launch mode, ``ahead(ex)`` (what has to be issued before the groups fork), the entry waits, the stem GEMM per
+        group, ``blocks(ex)`` and the joins into lane 0.  ``variant``: which of the master's recordings this launch sequence is."""
+        P, groups = self._packed, master["groups"]
+        self._ensure_pos(P, master["h"], master["w"], x.device)
+        for gp in groups:
+            self._stem_im2col(gp, x[gp["v0"]:gp["v0"] + gp["nv"]])
+
+        def frame(ex):
+            if ahead is not None:
+                ahead(ex)
+            for g in range(1, len(groups)):
+                ex.wait(g, 0)
+            for g, gp in enumerate(groups):
+                with ex.lane(g):
+                    self._stem_gemm(gp, P)
+            blocks(ex)
+            for l in range(1, n_lanes):
+                ex.wait(0, l)
+        self._run_frame(master, n_lanes, frame, variant)
 
     def _feature_view(self, plan):
         x = plan["x"] if self.alias_outputs else plan["x"].clone()
@@ -631,52 +693,15 @@ class EVA_ViT(_BackboneBase):
 
     @torch.no_grad()
     def forward(self, x, *args, **kwargs):
-        x, H, W = self._check_input(x)
-        if self._packed is None:
-            self._packed = self._pack_common()
-            self._plans = {}
-        key = (tuple(x.shape), x.dtype, self.view_groups)
-        V = x.shape[0]
-        if key in self._plans:
-            self._plans[key] = self._plans.pop(key)              # most recently used last
-        if key not in self._plans:
-            while len(self._plans) >= 8:                         # each plan holds ~1 GB of workspaces at full size: keep the 8 most recently used
-                self._plans.pop(next(iter(self._plans)))
-            layout = self._group_layout(V, V)
-            master = self._base_plan(V, H, W, x.device, 0) if len(layout) == 1 else None
-            groups = []
-            if master is None:
-                master = dict(V=V, h=H // self.patch_size, w=W // self.patch_size)
-                master["x"] = torch.empty(V * master["h"] * master["w"], self.embed_dim, dtype=torch.float32, device=x.device)
-                for (v0, nv, _, _) in layout:
-                    gp = self._base_plan(nv, H, W, x.device, 0)
-                    gp["x"] = master["x"][v0 * gp["T"]:(v0 + nv) * gp["T"]]
-                    gp["v0"], gp["nv"] = v0, nv
-                    groups.append(gp)
-            else:
-                master["v0"], master["nv"] = 0, V
-                groups = [master]
-            master["groups"] = groups
-            self._plans[key] = master
-        master, P = self._plans[key], self._packed
+        x, master = self._master(x)
         groups = master["groups"]
-        self._ensure_pos(P, master["h"], master["w"], x.device)
-        for gp in groups:
-            self._stem_im2col(gp, x[gp["v0"]:gp["v0"] + gp["nv"]])
 
-        def frame(ex):
-            for g in range(1, len(groups)):
-                ex.wait(g, 0)
-            for g, gp in enumerate(groups):
-                with ex.lane(g):
-                    self._stem_gemm(gp, P)
+        def blocks(ex):
             for i in range(self.depth):
                 for g, gp in enumerate(groups):
                     with ex.lane(g):
-                        self._dense_block(i, gp, P)
-            for g in range(1, len(groups)):
-                ex.wait(0, g)
-        self._run_frame(master, len(groups), frame)
+                        self._dense_block(i, gp, self._packed)
+        self._drive(master, x, len(groups), blocks)
         return {self._out_features[0]: self._feature_view(master)}
 
 
@@ -754,7 +779,7 @@ class ToC3DEVAViT(_BackboneBase):
         # projection is a per-block constant, produced here by the same LayerNorm + GEMM kernels as a real row
         C = self.embed_dim
         minus1 = torch.full((1,), -1, dtype=torch.int32, device=dev)
-        keep_alive = []                                    # temporaries of the pack launches, dropped after the synchronize below
+        keep = []                                          # temporaries of the pack launches, dropped after the last synchronize below
         for i, bp in enumerate(P["blocks"]):
             if not self._accelerated(i):
                 continue
@@ -773,14 +798,14 @@ class ToC3DEVAViT(_BackboneBase):
                 bp["pad_rot"] = torch.empty(L * L, 3 * C, dtype=self._tdt, device=dev)
                 self._linear(lib.EPI_QKV_ROPE, a_rep, bp["wqkv"], bp["bqkv"], bp["pad_rot"], L * L, 3 * C, C, rope=(rc, bp["rope_tab"], L, lib.ATTN_ROT_Q_SCALE),
                              variant=0)                               # (fp32x3: A = the plain f32 LayerNorm row, W in planes, the rotated rows as planes)
-                keep_alive += [a_rep, rc]
+                keep += [a_rep, rc]
         torch.cuda.current_stream().synchronize()
         nfl = lib.load().toc3d_motion_weights_floats()
         # positional_encoding.py:18,32 -- same torch expression as the reference, evaluated on the host
         d3, d1 = dim_t(128).to(dev), dim_t(256).to(dev)
-        f, pack = self._f32, partial(gemm.pack_weight, dts=self._dts)
+        pk = gemm.Packer(self._dts, dev)
+        f = pk.f32
         P["scorers"] = []
-        keep = []
         P["motion_all"] = torch.empty(len(self.score_predictor), nfl, dtype=torch.float32, device=dev)
         P["motion_stride"] = nfl
         for si, sp in enumerate(self.score_predictor):
@@ -799,16 +824,16 @@ class ToC3DEVAViT(_BackboneBase):
             q["scale"] = QUERY_DIM ** -0.5 if self.pruning_attn_scale else 1.0
             # first-frame scorer (ScoreBasedTokenSelector.score)
             q["ln_w"], q["ln_b"] = f(sp.in_conv[0].weight), f(sp.in_conv[0].bias)
-            q["w_ic"], q["b_ic"] = pack(sp.in_conv[1].weight), f(sp.in_conv[1].bias)
-            q["w_o0"], q["b_o0"] = pack(sp.out_conv[0].weight), f(sp.out_conv[0].bias)
-            q["w_o2"], q["b_o2"] = pack(sp.out_conv[2].weight), f(sp.out_conv[2].bias)
+            q["w_ic"], q["b_ic"] = pk.wb(sp.in_conv[1].weight, sp.in_conv[1].bias)
+            q["w_o0"], q["b_o0"] = pk.wb(sp.out_conv[0].weight, sp.out_conv[0].bias)
+            q["w_o2"], q["b_o2"] = pk.wb(sp.out_conv[2].weight, sp.out_conv[2].bias)
             q["w_o4"], q["b_o4"] = f(sp.out_conv[4].weight), f(sp.out_conv[4].bias)
             P["scorers"].append(q)
         torch.cuda.current_stream().synchronize()
         return P
 
-    def _plan(self, V, H, W, B, dev):
-        C = self.embed_dim
+    def _plan(self, V, H, W, x, B):
+        C, dev = self.embed_dim, x.device
         p = self.patch_size
         h, w = H // p, W // p
         sel_geo = {}
@@ -822,11 +847,10 @@ class ToC3DEVAViT(_BackboneBase):
                 ms = int(rows_fn(V, h, w, L, k))          # compact rows: kept real tokens + one representative per window
                 sel_geo[(st, L)] = (nW, L * L, k, ms)
                 max_rows = max(max_rows, ms)
-        plan = self._base_plan(V, H, W, dev, max_rows)
+        plan = self._base_plan(V, H, W, x, B, max_rows)
         T, M = plan["T"], plan["M"]
         i32 = dict(dtype=torch.int32, device=dev)
         f32 = dict(dtype=torch.float32, device=dev)
-        plan["B"] = B
         plan["slow"] = torch.empty(max_rows, C, **f32)
         plan["rep1"] = torch.empty(max_nw, C, **f32)
         plan["rep2"] = torch.empty(max_nw, C, **f32)
@@ -843,19 +867,20 @@ class ToC3DEVAViT(_BackboneBase):
                                     rep_row=torch.empty(nW, **i32), arows=torch.empty(nW, k + 1, **i32),
                                     aslots=torch.empty(nW, k + 1, **i32), acount_q=torch.empty(nW, **i32), acount_k=torch.empty(nW, **i32),
                                     crow_rc=torch.zeros(ms, **i32))
+            s = plan["sel"][key]
+            s["win"] = Windows(s["crow_rc"], s["arows"], s["aslots"], s["acount_q"], s["acount_k"], None, k + 1, nW, s["max_q"])
         ns = len(self.pruning_loc)
         plan["pred"] = [torch.empty(M, 2, **f32) for _ in range(ns)]
         plan["u1"] = plan["u2"] = None                    # first-frame scorer scratch, allocated on demand
         return plan
 
     def _master_plan(self, V, H, W, B, dev):
-        """Shared outputs (x, masks, scores, image-level order, query-side buffers) + one work plan per view group."""
+        """The base's (x + one work plan per view group) + the shared outputs (masks, scores, image-level order), the query-side buffers and the staging buffers."""
         C, Q, ns = self.embed_dim, self.pruning_num_queries, len(self.pruning_loc)
-        h, w = H // self.patch_size, W // self.patch_size
-        T = h * w
+        m = super()._master_plan(V, H, W, B, dev)
+        T = m["T"]
         f32 = dict(dtype=torch.float32, device=dev)
-        m = dict(V=V, h=h, w=w, T=T, M=V * T, x=torch.empty(V * T, C, **f32),
-                 score=[torch.empty(V * T, **f32) for _ in range(ns)], mask=[torch.empty(V * T, **f32) for _ in range(ns)],
+        m.update(score=[torch.empty(V * T, **f32) for _ in range(ns)], mask=[torch.empty(V * T, **f32) for _ in range(ns)],
                  order=[torch.empty(V, T, dtype=torch.int64, device=dev) for _ in range(ns)],
                  prep=dict(mq=torch.empty(ns, B, Q, QUERY_DIM, **f32), wc=torch.empty(ns, B, C, 2, **f32), bc=torch.empty(ns, B, 2, **f32)))
         # Inputs that change pointer every frame are copied into fixed staging buffers in front of the frame (a few KB; the images
@@ -867,13 +892,9 @@ class ToC3DEVAViT(_BackboneBase):
                           pose=torch.empty(B, Q, 4, 4, **f32), inv=torch.empty(B, 4, 4, **f32), new=torch.zeros(B, **f32),
                           gumbel_all=torch.empty(ns, V * T, 2, **f32), rng=self._rng_state(dev))
         m["stage"]["gumbel"] = [m["stage"]["gumbel_all"][s_] for s_ in range(ns)]      # one buffer: the device-side draw fills all stages in one launch
-        m["groups"] = []
-        layout = self._group_layout(V, B)
-        for (v0, nv, f0, nf) in layout:
-            gp = self._plan(nv, H, W, nf, dev)
-            gp["v0"], gp["nv"], gp["frame0"], gp["prep"] = v0, nv, f0, m["prep"]
-            gp["x"] = m["x"][v0 * T:(v0 + nv) * T]           # row slices of x are whole 128-byte lines (C*4 bytes per token)
-            if len(layout) == 1:
+        for gp in m["groups"]:
+            gp["prep"], nv = m["prep"], gp["nv"]
+            if len(m["groups"]) == 1:
                 gp["score"], gp["mask"], gp["order"] = m["score"], m["mask"], m["order"]
             else:
                 # Groups run on different streams, i.e. on different XCDs whose L2s are not coherent with each other: two
@@ -883,7 +904,6 @@ class ToC3DEVAViT(_BackboneBase):
                 gp["score"] = [torch.empty(nv * T, **f32) for _ in range(ns)]
                 gp["mask"] = [torch.empty(nv * T, **f32) for _ in range(ns)]
                 gp["order"] = [torch.empty(nv, T, dtype=torch.int64, device=dev) for _ in range(ns)]
-            m["groups"].append(gp)
         return m
 
     @property
@@ -918,9 +938,15 @@ class ToC3DEVAViT(_BackboneBase):
     def _block_done(self, i, plan, carried):
         """After block ``i`` of one view group was issued (``carried``: its update of x is still pending in the compact rows).  No-op here."""
 
+    def _run_frame(self, master, n_lanes, frame_fn, variant=None):
+        if self._instrumented:
+            frame_fn(EagerExec(n_lanes, self._stream_pool))
+        else:
+            super()._run_frame(master, n_lanes, frame_fn, variant)
+
     def _score_stage(self, ex, lane, side, prep_lane, st, plan, P, prev_exists, gumbel, frame_new=None):
         """One scorer stage of one view group (toc3d_eva_vit.py:264-285) on ``lane``; work that does not gate the block chain
-        (image-level ranking, the selection of the window type the next block does not use) goes to the group's ``side`` lane.
+        (image-level ranking, the selection of the window type the next block does not use) goes to the group's side lane (``side``: its lane / pending / L record of forward()).
         ``frame_new`` (a mixed step: f32 flags of this group's frames, device memory): the query path scores every row, then the
         static chain runs on every row and its last launch overwrites the rows of the flagged frames only."""
         s = lib.stream_ptr()
@@ -959,21 +985,20 @@ class ToC3DEVAViT(_BackboneBase):
         # image-level keep/drop lists are only returned to the caller (vis / loss): rank them beside the blocks
         # ... and so is the selection for the window type the next block does not use (first needed two blocks later)
         first = self._block_side(self.pruning_loc[st])
-        ex.wait(side, lane)
-        plan["side_pending"] = True
-        plan["side_L"] = None
-        with ex.lane(side):
+        ex.wait(side.lane, lane)
+        side.pending, side.L = True, None
+        with ex.lane(side.lane):
             lib.call("toc3d_rank_desc", score, V, T, plan["order"][st], lib.stream_ptr())
             for L in {self.window_size, self.global_window_size} - {first}:
                 topk(L)
-                plan["side_L"] = L
+                side.L = L
         topk(first)
 
     @staticmethod
-    def _join_side(ex, lane, side, plan):
-        if plan.get("side_pending"):
-            ex.wait(lane, side)
-            plan["side_pending"] = False
+    def _join_side(ex, lane, side):
+        if side.pending:
+            ex.wait(lane, side.lane)
+            side.pending = False
 
     def _query_prep(self, ex, prep_lane, master, P, ts_key):
         """get_motion_aware_queries + the collapse of input_proj/einsum/aggregate for all stages and frames (identical
@@ -1001,10 +1026,10 @@ class ToC3DEVAViT(_BackboneBase):
         weight normalisation).  The dropped tokens receive all four updates at the end."""
         s = lib.stream_ptr()
         bp = P["blocks"][i]
-        C, dt = self.embed_dim, self._dt
-        if plan.get("side_L") == self._block_side(i):     # this window type's selection was computed on the side lane
-            self._join_side(ex, lane, side, plan)
-            plan["side_L"] = None
+        C = self.embed_dim
+        if side.L == self._block_side(i):                 # this window type's selection was computed on the side lane
+            self._join_side(ex, lane, side)
+            side.L = None
         sel = plan["sel"][(st, self._block_side(i))]
         nW, N, k, rows = sel["nW"], sel["N"], sel["k"], sel["rows"]
         slow = plan["slow"]
@@ -1018,14 +1043,10 @@ class ToC3DEVAViT(_BackboneBase):
         else:
             lib.call("toc3d_gather_merge_ln_ex", self._dt_rows, plan["x"], C, sel["tok"], sel["wgt"], sel["crow_tok"], sel["rep_row"], nW, N, k, rows,
                      bp["ln1_w"], bp["ln1_b"], self.LN_EPS, slow, plan["a"], C, 0 if self.gathered_residual else 1, s)
-        rot = self._rot_ok(k + 1)
-        self._qkv_attention(P, i, plan, rows, sel["crow_rc"], sel["arows"], sel["aslots"], sel["acount_q"], sel["acount_k"], None,
-                            bp["pad_rot"] if rot else bp["pad_qkv"], k + 1, nW, sel["max_q"], None)
+        self._qkv_attention(P, i, plan, rows, sel["win"])
         ra, rb = (plan["rep3"], plan["rep4"]) if carry_in else (plan["rep1"], plan["rep2"])
-        if self.gathered_residual and not carry_in:      # kept rows were not copied: their residual comes from x through crow_tok
-            self._proj(bp, plan, rows, slow, ra, sel["rep_index"], res=plan["x"], res_index=sel["crow_tok"])
-        else:
-            self._proj(bp, plan, rows, slow, ra, sel["rep_index"])
+        via_x = self.gathered_residual and not carry_in  # kept rows were not copied: their residual comes from x through crow_tok
+        self._proj(bp, plan, rows, slow, ra, sel["rep_index"], res=plan["x"] if via_x else None, res_index=sel["crow_tok"] if via_x else None)
         self._mlp(bp, plan, rows, slow, rb, sel["rep_index"])
         if not carry_out:
             lib.call("toc3d_scatter_update", plan["x"], C, sel["tok"], sel["prow"], nW, N, k, slow, plan["rep1"], plan["rep2"],
@@ -1041,13 +1062,6 @@ class ToC3DEVAViT(_BackboneBase):
                 temp_ego_pose=None, ego_pose_inv=None, *args, gumbel_noise=None, **kwargs):
         if "forced_scores" in kwargs:
             raise TypeError("forced_scores is a test instrument: wrap the model with toc3d_amd.testing.instrument(model)")
-        x, H, W = self._check_input(x)
-        if self._packed is None:
-            self._packed = self._pack()
-            self._plans = {}
-        P = self._packed
-        dev = x.device
-        V = x.shape[0]
         # the reference's detector passes a Python bool (petr3d.py:122,155); a tensor costs one host sync per frame
         B = temp_queries.shape[0] if temp_queries is not None else 1
         mixed = None                                             # a list / tuple of B Python bools: one per frame (B camera streams stepped together)
@@ -1062,16 +1076,8 @@ class ToC3DEVAViT(_BackboneBase):
                 mixed = flags                                    # some frames start a scene, the others continue: the third recorded mode
         else:
             prev = bool(prev_exists.bool().flatten()[0].item()) if isinstance(prev_exists, torch.Tensor) else bool(prev_exists)
-        assert V % B == 0
-        ns = len(self.pruning_loc)
-        key = (tuple(x.shape), x.dtype, B, self.view_groups)
-        if key in self._plans:
-            self._plans[key] = self._plans.pop(key)              # most recently used last
-        else:
-            while len(self._plans) >= 8:                         # each plan holds ~1 GB of workspaces at full size: keep the 8 most recently used
-                self._plans.pop(next(iter(self._plans)))
-            self._plans[key] = self._master_plan(V, H, W, B, dev)
-        plan = self._plans[key]
+        x, plan = self._master(x, B)
+        P, dev, V, ns = self._packed, x.device, x.shape[0], len(self.pruning_loc)
         groups, sg = plan["groups"], plan["stage"]
         G, T = len(groups), plan["T"]
         s0 = lib.stream_ptr()
@@ -1108,34 +1114,24 @@ class ToC3DEVAViT(_BackboneBase):
         if not prev or mixed is not None:
             for gp in groups:                                    # first-frame scorer scratch
                 if gp["u1"] is None:
-                    C = self.embed_dim
-                    gp["u1"] = torch.zeros(gp["M"], max(64, C // 2), dtype=self._tdt, device=dev)
-                    gp["u2"] = torch.zeros(gp["M"], max(64, C // 4), dtype=self._tdt, device=dev)
-        self._ensure_pos(P, plan["h"], plan["w"], dev)
-        for gp in groups:
-            self._stem_im2col(gp, x[gp["v0"]:gp["v0"] + gp["nv"]])
+                    gp["u1"], gp["u2"] = (torch.zeros(gp["M"], max(64, self.embed_dim // d), dtype=self._tdt, device=dev) for d in (2, 4))
 
         # ---- the frame: lanes 0..G-1 = view groups, G..2G-1 = their side lanes, 2G = query-side scorer prep -----------------------
-        prep_lane = 2 * G
         # side_lanes=False (A/B switch): the scorer's query preparation and the rankings run on the block chain's own lane instead of beside it
         serial = not self.side_lanes
-        side_of = (lambda g: g) if serial else (lambda g: G + g)
-        if serial:
-            prep_lane = 0
+        prep_lane = 0 if serial else 2 * G
 
-        def frame(ex):
-            for gp in groups:
-                gp["side_pending"], gp["side_L"] = False, None
+        def ahead(ex):
             if draw:
                 # part of the recorded frame: the frame counter lives in device memory, so every replay draws fresh noise (one launch for all stages)
                 lib.call("toc3d_gumbel_noise", sg["gumbel_all"], sg["gumbel_all"].numel(), self.gumbel_seed, sg["rng"], lib.stream_ptr())
             if prev and ns:
                 self._query_prep(ex, prep_lane, plan, P, ts_key)
-            for g in range(1, G):
-                ex.wait(g, 0)
-            for g, gp in enumerate(groups):
-                with ex.lane(g):
-                    self._stem_gemm(gp, P)
+
+        def blocks(ex):
+            # side-lane work of each group that is outstanding while the frame is issued: its lane, something was put there since the last join, the window
+            # type whose selection runs there -- scheduler state of this pass, not of the plan
+            sides = [SimpleNamespace(lane=g if serial else G + g, pending=False, L=None) for g in range(G)]
             st, pending = -1, False
             for i in range(self.depth):
                 if i in self.pruning_loc:
@@ -1149,15 +1145,15 @@ class ToC3DEVAViT(_BackboneBase):
                         if i in self.pruning_loc:
                             r0, r1 = gp["v0"] * T, (gp["v0"] + gp["nv"]) * T
                             new = None if mixed is None else sg["new"][gp["frame0"]:gp["frame0"] + gp["B"]]
-                            self._score_stage(ex, g, side_of(g), prep_lane, st, gp, P, prev, [gm[r0:r1] for gm in sg["gumbel"]], new)
+                            self._score_stage(ex, g, sides[g], prep_lane, st, gp, P, prev, [gm[r0:r1] for gm in sg["gumbel"]], new)
                         if self._accelerated(i):
-                            self._accel_block(ex, g, side_of(g), i, st, gp, P, carry_in=cin, carry_out=cout)
+                            self._accel_block(ex, g, sides[g], i, st, gp, P, carry_in=cin, carry_out=cout)
                         else:
                             self._dense_block(i, gp, P)
                         self._block_done(i, gp, cout)
             for g, gp in enumerate(groups):
                 with ex.lane(g):
-                    self._join_side(ex, g, side_of(g), gp)
+                    self._join_side(ex, g, sides[g])
                     if G > 1:
                         # private per-group buffers -> the contiguous outputs, on the group's own lane (write-only, disjoint
                         # bytes; nothing reads the shared buffers before the join below)
@@ -1165,13 +1161,7 @@ class ToC3DEVAViT(_BackboneBase):
                         for st_ in range(ns):
                             lib.call("toc3d_copy_bytes", plan["mask"][st_][v0 * T:(v0 + nv) * T], gp["mask"][st_], nv * T * 4, lib.stream_ptr())
                             lib.call("toc3d_copy_bytes", plan["order"][st_][v0:v0 + nv], gp["order"][st_], nv * T * 8, lib.stream_ptr())
-            for l in range(1, 2 * G + 1):
-                ex.wait(0, l)
-
-        if self._instrumented:
-            frame(EagerExec(2 * G + 1, self._stream_pool))
-        else:
-            self._run_frame(plan, 2 * G + 1, frame, variant=("mixed" if mixed is not None else prev, ts_key, draw))
+        self._drive(plan, x, 2 * G + 1, blocks, ahead, variant=("mixed" if mixed is not None else prev, ts_key, draw))
         h, w = plan["h"], plan["w"]
         cl = (lambda t: t) if self.alias_outputs else (lambda t: t.clone())
         masks = [cl(plan["mask"][s]).view(V, h, w, 1) for s in range(ns)]

@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import gemm, lib
-from .plan import MODES, DerivedState, run_frame
+from .plan import MODES, DerivedState, lru, run_frame
 
 
 class _ConvModule(nn.Module):
@@ -137,11 +137,8 @@ class CPFPN(DerivedState, nn.Module):
         if fan is not None and fan[0].shape[0] != M:
             raise ValueError(f"toc3d_amd.CPFPN.forward_fanout: rows has {fan[0].shape[0]} rows, the frame has {M} tokens")
         if in_place:
-            states = ws.setdefault("launch", {})
             skey = nhwc.data_ptr() if fan is None else (nhwc.data_ptr(), fan[0].data_ptr(), fan[1], fan[2])       # the fanned-out frame names the rows buffer too
-            if skey not in states and len(states) >= 4:
-                states.pop(next(iter(states)))
-            state = states.setdefault(skey, {})
+            state = lru(ws.setdefault("launch", {}), skey, dict, 4)
             if fan is not None:
                 state["rows"] = fan[0]                  # a recorded plan points into it: it lives as long as the plan does, whatever its owner does
             run_frame(state, self.launch_mode, 1, frame, self._stream_pool)

@@ -81,7 +81,7 @@ def save_packed(model, path: str):
     """Pack (if not done yet) and write the packed weights of ``model`` (a toc3d_amd backbone on the GPU) to ``path``."""
     from safetensors.torch import save_file
     if model._packed is None:
-        model._packed = model._pack() if hasattr(model, "_pack") else model._pack_common()
+        model._packed = model._pack()
     P = {k: v for k, v in model._packed.items() if k != "dev"}
     tensors: Dict[str, torch.Tensor] = {}
     scalars: Dict[str, Any] = {}

@@ -24,6 +24,18 @@ MODES = {"eager": None, "plan": 0, "graph": 1}     # launch_mode -> toc3d_plan_e
 MAX_LANES = 64                                     # csrc/plan.cpp MAX_LANES: frames that need more lanes launch eagerly
 
 
+def lru(cache: dict, key, make, keep=None):
+    """``cache[key]``, most recently used last: a hit moves the entry to the end; a miss drops the oldest entries until fewer than ``keep`` remain (``None``:
+    drops nothing), then stores ``make()`` -- what is dropped is free before its replacement is built."""
+    if key in cache:
+        cache[key] = cache.pop(key)
+    else:
+        while cache and keep is not None and len(cache) >= keep:
+            cache.pop(next(iter(cache)))
+        cache[key] = make()
+    return cache[key]
+
+
 class EagerExec:
     def __init__(self, n_lanes: int, pool: List[torch.cuda.Stream]):
         while len(pool) < n_lanes - 1:

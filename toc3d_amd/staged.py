@@ -4,7 +4,8 @@ the small things more than one of them (and the backbone's scorer) builds the sa
 
 A module on the base keeps what is its own: the config it accepts, its parameter containers, ``_pack(pk)`` (what it packs, with a :class:`toc3d_amd.gemm.Packer`),
 ``_alloc(key, dev)`` (the buffers of one shape), its launch sequence and the views it returns.  ``CPFPN`` and the backbones own tuning tables and multi-lane frames
-and stay on :class:`toc3d_amd.plan.DerivedState` alone.
+and stay on :class:`toc3d_amd.plan.DerivedState` alone: the backbones share their own frame driver (``backbone._BackboneBase._master`` / ``_drive``).  What all of
+them share is ``gemm.Packer`` for packing and ``plan.lru`` for the caches of plans and launch states.
 """
 from __future__ import annotations
 
@@ -77,12 +78,10 @@ class StagedModule(plan.DerivedState, nn.Module):
 
     def _run(self, key, launches, mode=None, max_states=None):
         """One frame: ``launches()`` on lane 0, in ``mode`` (default: the module's ``launch_mode``) through ``plan.run_frame`` on ``self._states[key]``.  A module
-        whose recorded plans name buffers that are not its own keeps at most ``max_states`` of them, the oldest dropped first."""
-        state = self._states.get(key)
+        whose recorded plans name buffers that are not its own keeps at most ``max_states`` of them, the oldest dropped first (``plan.lru``'s miss)."""
+        state = self._states.get(key)                              # (a hit leaves the order alone: here the oldest recording goes first, not the least used)
         if state is None:
-            while max_states is not None and len(self._states) >= max_states:
-                self._states.pop(next(iter(self._states)))
-            state = self._states[key] = {}
+            state = plan.lru(self._states, key, dict, max_states)
 
         def frame(ex):
             with ex.lane(0):
