@@ -92,6 +92,7 @@ from functools import lru_cache
 
 import torch
 
+from support import DEV
 from toc3d_amd import synth
 
 U = 2.0 ** -24
@@ -543,3 +544,24 @@ def _all_cases():
 
 
 CASES = _all_cases()
+
+
+# ---- RoPE helpers of the pre-rotated path (test_gpu_attn_rot.py, test_gpu_epilogue_tails.py) -----------------------------------------------------------------
+def compact_tables(cos, sin):
+    """[L*L, 64] reference buffers -> the [2, L, 16] tables toc3d_linear_qkv_rope consumes (what backbone._pack_blocks builds)."""
+    L = int(round(cos.shape[0] ** 0.5))
+    out = []
+    for t in (cos, sin):
+        g = t.view(L, L, 64)
+        out.append(torch.stack([g[:, 0, 0:32:2], g[0, :, 32:64:2]]))
+    return torch.stack(out).contiguous().to(DEV), L
+
+
+def rc_of(slots, L):
+    return (((slots // L) << 16) | (slots % L)).to(torch.int32).contiguous().to(DEV)
+
+
+def rope_ref(x, cos, sin):
+    """eva_utils.py:378-379 with rotate_half over pairs (2t, 2t+1); x [..., 64], cos / sin broadcastable."""
+    x2 = torch.stack([-x[..., 1::2], x[..., 0::2]], -1).flatten(-2)
+    return x * cos + x2 * sin

@@ -23,6 +23,7 @@ VARIANTS = {
     54: (96, 48, 128, 32, True), 57: (160, 80, 128, 32, True), 60: (256, 128, 256, 64, True), 61: (256, 64, 128, 64, True), 63: (128, 64, 128, 32, True),
     116: (128, 64, 128, 32, False),
 }
+TOL_F32, TOL_BF16, TOL_STATS = 2e-5, 6e-3, 1e-5      # the bars of these output classes: f32 and bf16 x 3 outputs (of the output's max), bf16-rounded outputs, row statistics
 M_ALIGNED = 576                      # whole pairs of row tiles (576 % 32 == 0): the launch that is checked against f64 and that every prefix launch is compared with
 ROWS = (1, 16, 24, 41, 48, 59, 120, 152, 161, 184, 193, 216, 257, 555)
 ROWS_SHORT = (1, 24, 41, 59, 216, 257)   # the plain epilogues on planes (every output plain f32: no paired planes stores)

@@ -1,20 +1,12 @@
 """CPU: the N>1 path (frame sharding + the one feature all-gather) with world_size 2 on gloo."""
 import os
-import socket
 
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from support import _free_port
 from toc3d_amd import dist as tdist
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _worker(rank, world, port, n_frames, q):

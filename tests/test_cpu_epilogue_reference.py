@@ -4,11 +4,7 @@ import pytest
 import torch
 
 import epilogue_cases as E
-
-
-def rnd(*shape, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(*shape, generator=g) * scale
+from support import rnd
 
 
 @pytest.mark.parametrize("ln_n,K", E.ln_shapes())

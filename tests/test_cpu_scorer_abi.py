@@ -13,22 +13,11 @@ import torch.nn.functional as F
 
 import scorer_cases as SC
 from oracle import toc3d_oracle as O
+from support import _call, _refused
 from toc3d_amd import configs, lib, synth
 
 A = 0x10000                                  # 256-byte aligned stand-in for a device buffer
-ERR_ARG = -1
 I31 = (1 << 31) - 1                          # the largest count the kernels' 32-bit indices hold
-
-
-def _call(name, *args):
-    l = lib.load()
-    rc = getattr(l, name)(*args)
-    return rc, l.toc3d_last_error().decode()
-
-
-def _refused(name, args, reason):
-    rc, msg = _call(name, *args)
-    assert rc == ERR_ARG and name in msg and reason in msg, (rc, msg)
 
 
 # ---- toc3d_pack_motion_weights / toc3d_motion_queries ------------------------------------------------------

@@ -11,6 +11,7 @@ import torch
 import torch.nn as nn
 
 import toc3d_amd
+from support import FakeNeck
 from toc3d_amd import lib, synth
 
 A = 0x10000                                  # 256-byte aligned stand-in for a device buffer (never dereferenced: the checks run before any launch)
@@ -135,20 +136,6 @@ class FakeBackbone(nn.Module):
         self.log.append(("backbone", tuple(x.shape), kw["prev_exists"], tuple(kw["temp_queries"].shape), tuple(kw["ego_pose_inv"].shape), kw.get("gumbel_noise")))
         feats = torch.zeros(x.shape[0], 8, 2, 5)
         return toc3d_amd.ToC3DViTReturnType({"last_feat": feats}, ["m0", "m1", "m2"], None, ["k0", "k1", "k2"], ["d0", "d1", "d2"])
-
-
-class FakeNeck(nn.Module):
-    def __init__(self, log):
-        super().__init__()
-        self.log = log
-
-    def forward(self, inputs):
-        raise AssertionError("the detector runs the neck with the fan-out")
-
-    def forward_fanout(self, inputs, rows, ld_rows, dtype):
-        self.log.append(("neck", tuple(inputs[0].shape), rows, ld_rows, dtype))
-        out0 = torch.full((inputs[0].shape[0], 4, 2, 5), float(len(self.log)))
-        return out0, out0[:, :, ::2, ::2]
 
 
 class FakeHead(nn.Module):

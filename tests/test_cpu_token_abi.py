@@ -7,22 +7,11 @@ import pytest
 import torch
 
 import token_cases as T
+from support import _call, _refused
 from toc3d_amd import lib
 
 A = 0x10000                                  # 256-byte aligned stand-in for a device buffer
-ERR_ARG = -1
 BIG = (1 << 31) - 1024                       # first count the token kernels refuse (they count rows in 32 bits)
-
-
-def _call(name, *args):
-    l = lib.load()
-    rc = getattr(l, name)(*args)
-    return rc, l.toc3d_last_error().decode()
-
-
-def _refused(name, args, reason, fn=None):
-    rc, msg = _call(name, *args)
-    assert rc == ERR_ARG and (fn or name) in msg and reason in msg, (rc, msg)
 
 
 # ---- toc3d_layernorm_rows ---------------------------------------------------------------------------

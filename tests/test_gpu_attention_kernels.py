@@ -19,47 +19,18 @@ import pytest
 import torch
 
 import attention_cases as AC
-from test_gpu_ops import DEV, S
+from support import DEV, S, planes_f64, planes_halves, sent, to_planes, worst_report
 from toc3d_amd import lib
 
 pytestmark = pytest.mark.gpu
 DT = {("rot", "bf16"): lib.BF16, ("rot", "x3p"): lib.F32X3P, ("plain", "f32"): lib.F32, ("plain", "bf16"): lib.BF16, ("plain", "x3"): lib.F32X3,
       ("plain", "x3p"): lib.F32X3P, ("plain", "x3wo"): lib.F32X3WO}
-WORST = {}
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _report():
-    yield
-    print("\n[attention kernels] worst measured error as a fraction of its derived bound (<= 1.0 required)")
-    for key in sorted(WORST):
-        print(f"[attention kernels] {key:<52s} {WORST[key]:.3f}")
-
-
-def sent(rows, cols, bf):
-    if bf:
-        return torch.full((rows, cols), 0x7FC1, dtype=torch.int16, device=DEV).view(torch.bfloat16)
-    return torch.full((rows, cols), 0x7FC17FC1, dtype=torch.int32, device=DEV).view(torch.float32)
+note, _report = worst_report("attention kernels", 52)
 
 
 def halves(t):
     """CPU tensor [R, ld] (bf16 or f32) -> its 16-bit halves as int16 [R, ld or 2 ld]."""
     return t.contiguous().view(torch.int16)
-
-
-def to_planes(x):
-    """f32 device tensor [rows, ld] -> (hi, lo) planes, through the library's own converter."""
-    x = x.contiguous().clone()
-    lib.call("toc3d_x3_planes", x, x.shape[1], x, x.shape[1], x.shape[0], x.shape[1], S())
-    return x
-
-
-def from_planes(t):
-    """CPU f32-typed planes buffer [R, ld] -> (f64 values hi + lo, the hi halves, the lo halves as int16 [R, ld])."""
-    R, ld = t.shape
-    b = t.contiguous().view(torch.int16).view(R, ld // 32, 2, 32)
-    hi, lo = b[:, :, 0, :].reshape(R, ld), b[:, :, 1, :].reshape(R, ld)
-    return hi.contiguous().view(torch.bfloat16).double() + lo.contiguous().view(torch.bfloat16).double(), hi, lo
 
 
 def upload(case, x):
@@ -68,8 +39,8 @@ def upload(case, x):
         return x.to(torch.bfloat16).to(DEV)
     d = x.float().to(DEV)
     if case.path == "rot":
-        d = to_planes(d)
-        assert torch.equal(from_planes(d.cpu())[0], x), "the reference's operands are the planes the device reads"
+        d = to_planes(d, in_place=True)
+        assert torch.equal(planes_f64(d.cpu()), x), "the reference's operands are the planes the device reads"
     return d
 
 
@@ -104,7 +75,7 @@ def run_case(case):
     keep[b["written"]] = False
     assert bool((halves(o[keep]) == 0x7FC1).all()), f"{case}: a row that is a pad, in no list or beyond its window's count was written"
     if planes_out:
-        vals, hi, lo = from_planes(o)
+        vals, (hi, lo) = planes_f64(o), planes_halves(o)
         assert bool((hi[:, C:] == 0x7FC1).all() and (lo[:, C:] == 0x7FC1).all()), f"{case}: guard columns [C, ldo) were written"
     else:
         vals = o.double()
@@ -120,7 +91,7 @@ def run_case(case):
     print(f"[attention kernels] {case.name:<34s} {AC.body_of(case):<26s} worst |dev - ref| / bound = {worst:.3f}")
     assert worst <= 1.0, f"{case}: {int((ratio > 1).sum())} elements beyond their bound, the worst at {worst:.3f} x (row {int(ratio.flatten(1).amax(1).argmax())} of the written rows)"
     key = f"{AC.body_of(case)} {case.kind} {case.family}"
-    WORST[key] = max(WORST.get(key, 0.0), worst)
+    note(key, worst)
 
 
 @pytest.mark.parametrize("case", AC.CASES, ids=str)

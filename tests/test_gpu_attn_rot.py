@@ -7,7 +7,8 @@ import torch
 from oracle import toc3d_oracle as O
 from toc3d_amd import configs, lib, synth
 
-from test_gpu_ops import DEV, S, as_act, pack, relerr, rnd
+from attention_cases import compact_tables, rc_of, rope_ref
+from support import DEV, S, as_act, pack, planes_values, relerr, rnd, to_planes
 
 pytestmark = pytest.mark.gpu
 BF, TBF = lib.BF16, torch.bfloat16
@@ -16,53 +17,19 @@ F32T = torch.float32
 PRECS = ["bf16", "x3"]
 
 
-def planes_decode(t):
-    """A (hi, lo) planes buffer (f32-typed tensor [rows, ld], ld % 32 == 0; include/toc3d.h TOC3D_DTYPE_F32X3P) -> the f32 values hi + lo."""
-    rows, ld = t.shape
-    b = t.contiguous().view(torch.bfloat16).view(rows, ld // 32, 2, 32).float()
-    return (b[:, :, 0] + b[:, :, 1]).reshape(rows, ld)
-
-
-def planes_encode(x):
-    """f32 device tensor [rows, ld] -> planes, through the library's own converter."""
-    x = x.contiguous().clone()
-    lib.call("toc3d_x3_planes", x, x.shape[1], x, x.shape[1], x.shape[0], x.shape[1], S())
-    return x
-
-
 def pack_p(w, prec):
-    return pack(w, BF, TBF) if prec == "bf16" else planes_encode(pack(w, lib.F32, F32T))
+    return pack(w, BF, TBF) if prec == "bf16" else to_planes(pack(w, lib.F32, F32T), in_place=True)
 
 
 def act_p(x, prec, planes=True):
     if prec == "bf16":
         return as_act(x, TBF)
     a = as_act(x, F32T)
-    return planes_encode(a) if planes else a
+    return to_planes(a, in_place=True) if planes else a
 
 
 def values(t, prec):
-    return t.float() if prec == "bf16" else planes_decode(t)
-
-
-def compact_tables(cos, sin):
-    """[L*L, 64] reference buffers -> the [2, L, 16] tables toc3d_linear_qkv_rope consumes (what backbone._pack_blocks builds)."""
-    L = int(round(cos.shape[0] ** 0.5))
-    out = []
-    for t in (cos, sin):
-        g = t.view(L, L, 64)
-        out.append(torch.stack([g[:, 0, 0:32:2], g[0, :, 32:64:2]]))
-    return torch.stack(out).contiguous().to(DEV), L
-
-
-def rc_of(slots, L):
-    return (((slots // L) << 16) | (slots % L)).to(torch.int32).contiguous().to(DEV)
-
-
-def rope_ref(x, cos, sin):
-    """eva_utils.py:378-379 with rotate_half over pairs (2t, 2t+1); x [..., 64], cos / sin broadcastable."""
-    x2 = torch.stack([-x[..., 1::2], x[..., 0::2]], -1).flatten(-2)
-    return x * cos + x2 * sin
+    return t.float() if prec == "bf16" else planes_values(t)
 
 
 def qkv_rope(a_d, wqkv_p, bqkv, M, C, rc, tab, L, variant=0, prec="bf16", a_planes=True):
@@ -92,7 +59,7 @@ def test_qkv_projection_with_rope_in_the_epilogue_on_planes():
     tab, _ = compact_tables(cos, sin)
     w_d = pack_p(W, "x3")
     out = qkv_rope(act_p(A, "x3"), w_d, b.to(DEV), M, C, rc_of(slots, L), tab, L, prec="x3")
-    assert relerr(planes_decode(out), ref) < 5e-5
+    assert relerr(planes_values(out), ref) < 5e-5
     out_plain_a = qkv_rope(act_p(A, "x3", planes=False), w_d, b.to(DEV), M, C, rc_of(slots, L), tab, L, prec="x3", a_planes=False)
     assert torch.equal(out_plain_a.view(torch.int32), out.view(torch.int32)), "A split in the kernel or delivered as planes: the same bits"
     for v in (1, 8, 9, 10, 14, 16, 17, 19, 22, 26, 28, 29, 33, 45, 47, 49, 52, 53, 54, 55, 56, 57, 58, 59, 60, 61, 62, 63, 116, 117, 149, 152, 155, 160, 161):
@@ -261,7 +228,7 @@ def test_rot_attention_on_planes_is_bit_stable_with_co_resident_workgroups(L):
     V, h, w, C, heads = 12, 20, 50, 128, 2
     M, N = V * h * w, L * L
     nW = V * (-(-h // L)) * (-(-w // L))
-    qkv = planes_encode(rnd(M, 3 * C, seed=3).to(DEV))
+    qkv = to_planes(rnd(M, 3 * C, seed=3).to(DEV), in_place=True)
     rows = torch.empty(nW, N, dtype=torch.int32, device=DEV)
     slots, count, npad = torch.empty_like(rows), torch.empty(nW, dtype=torch.int32, device=DEV), torch.empty(nW, dtype=torch.int32, device=DEV)
     lib.call("toc3d_window_map_dense", V, h, w, L, rows, slots, count, npad, S())
@@ -280,7 +247,7 @@ def test_rot_attention_on_planes_is_bit_stable_with_co_resident_workgroups(L):
     torch.cuda.synchronize()
     for o in outs[1:]:
         assert torch.equal(o.view(torch.int32), outs[0].view(torch.int32))
-    v = planes_decode(outs[0])
+    v = planes_values(outs[0])
     assert bool(torch.isfinite(v).all()) and float(v.abs().max()) > 0
 
 
@@ -310,7 +277,7 @@ def test_rot_attention_deferred_rescale_is_the_exact_softmax(n, np_pad, prec):
         q, k, v = (t.to(TBF).float() for t in (q, k, v))      # the same bf16-representable operands: hi = the value, lo = 0
     qkv = torch.cat([q.reshape(M, C), k.reshape(M, C), v.reshape(M, C)], 1).to(TBF).to(DEV).contiguous()
     if prec == "x3":
-        qkv = planes_encode(qkv.float())
+        qkv = to_planes(qkv.float(), in_place=True)
     rows = torch.arange(M, dtype=torch.int32).view(nW, n)
     stride = (n + 15) // 16 * 16
     rows_p = torch.zeros(nW, stride, dtype=torch.int32)

@@ -12,34 +12,14 @@ import pytest
 import torch
 
 import toc3d_amd
-from test_cpu_decoder import rel_max, restated_decoder
+from decoder_cases import _heads, build, restated_decoder, run
+from support import DEV, rel_l2, rel_max
 from toc3d_amd import lib, synth
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-
-
-def rel_l2(a, b):
-    a, b = torch.as_tensor(a).double().cpu(), torch.as_tensor(b).double().cpu()
-    return ((a - b).norm() / b.norm()).item()
-
-
-def build(sizes, precision="fp32x3", launch_mode="plan", seed=0):
-    m = toc3d_amd.build_transformer(dict(synth.decoder_cfg(**sizes), precision=precision, launch_mode=launch_mode))
-    m.load_state_dict(synth.decoder_state_dict(sizes, seed=seed), strict=True)
-    return m.to(DEV).eval()
-
-
-def run(m, inp):
-    d = lambda t: None if t is None else t.to(DEV)
-    return m(d(inp["memory"]), d(inp["tgt"]), d(inp["query_pos"]), d(inp["pos_embed"]), None, d(inp["temp_memory"]), d(inp["temp_pos"]))
 
 
 # ---- the kernel alone ------------------------------------------------------------------------------------------------------------------
-def _heads(t, H):
-    return t.view(t.shape[0], t.shape[1], H, 32).transpose(1, 2)
-
-
 def _attention(q, k, v, H):
     """softmax(q.k^T / sqrt(32)).v per head in the dtype of the operands (f64: the arbiter; bf16: torch's eager bf16 ops, the control)."""
     p = torch.softmax(_heads(q, H) @ _heads(k, H).transpose(-1, -2) * 32 ** -0.5, -1)

@@ -12,7 +12,7 @@ the module tests (tests/test_gpu_decoder.py) never reach, and the module itself 
    up to terms below 2^-126, which f32 flushes and f64 keeps.
 3. toc3d_add_layernorm_pos / toc3d_add_pos_rows / toc3d_relu_inplace: lane tails (E not a multiple of 64), the last workgroup of four rows partly filled, every
    combination of the optional outputs, leading dimensions all different and larger than E with sentinels in the padding, both act dtypes.  f32 outputs against the f64
-   LayerNorm of tests/test_cpu_decoder.py at the project's 2e-5 (tests/test_gpu_ops.py::test_layernorm_rows), bf16 act outputs bit-equal to torch's RNE rounding of
+   LayerNorm of tests/support.py at the project's 2e-5 (tests/test_gpu_ops.py::test_layernorm_rows), bf16 act outputs bit-equal to torch's RNE rounding of
    the kernel's own f32 result.  Offsets stop at 16 and are left out below E = 63: an f32 LayerNorm itself is outside 2e-5 at offset 1000 or at E = 2 with an offset.
 4. PETRTemporalTransformer at E 128 / F 1024 (split-K FFN at a width that is not 256) and E 192 / F 320 with B 2, 45 queries, 19 memory rows, 333 tokens.
 
@@ -29,8 +29,8 @@ import pytest
 import torch
 
 import toc3d_amd  # noqa: F401
-from test_cpu_decoder import layer_norm, rel_max, restated_decoder
-from test_gpu_decoder import DEV, _heads, build, rel_l2, run
+from decoder_cases import _heads, build, restated_decoder, run
+from support import DEV, layer_norm, rel_l2, rel_max
 from toc3d_amd import lib, synth
 
 pytestmark = pytest.mark.gpu

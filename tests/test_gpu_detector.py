@@ -19,10 +19,10 @@ import pytest
 import torch
 
 import toc3d_amd
+from support import DEV, to_dev
 from toc3d_amd import lib, synth
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BANK = ("memory_embedding", "memory_reference_point", "memory_timestamp", "memory_egopose", "memory_velo")
 TINY = synth.DETECTOR_TINY
@@ -118,10 +118,6 @@ def build_chain(sizes, precision, launch_mode="plan"):
     backbone, neck, head = (m.to(DEV).eval() for m in (backbone, neck, head))
     schedule(backbone, neck, sizes, precision, launch_mode)
     return backbone, neck, head
-
-
-def to_dev(frame):
-    return {k: v.to(DEV) for k, v in frame["data"].items()}
 
 
 def run_detector(det, frames):

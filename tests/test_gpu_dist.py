@@ -3,24 +3,15 @@ collective is still issued (force_collective), which exercises what the CPU / gl
 the flattened (world*Nv, ...) output view, the side stream and the event hand-offs of toc3d_amd.dist.FeatureGather, and bench.py's
 timed_steps protocol on a CUDA device."""
 import os
-import socket
 
 import pytest
 import torch
 import torch.distributed as dist
 
+from support import DEV, _free_port
 from toc3d_amd import dist as tdist
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def test_feature_gather_on_rccl_single_rank():

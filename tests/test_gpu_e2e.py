@@ -13,28 +13,10 @@ import torch
 
 import toc3d_amd
 from oracle import toc3d_oracle as O
+from support import DEV, iou, rel_l2, rel_max
 from toc3d_amd import configs, lib, synth
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-
-
-def rel_max(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return ((a - b).abs().max() / b.abs().max()).item()
-
-
-def rel_l2(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return ((a - b).norm() / b.norm()).item()
-
-
-def iou(a, b):
-    res = []
-    for ra, rb in zip(a.cpu().numpy(), np.asarray(b)):
-        sa, sb = set(ra.tolist()), set(rb.tolist())
-        res.append(len(sa & sb) / max(1, len(sa | sb)))
-    return min(res)
 
 
 def build(name, precision):

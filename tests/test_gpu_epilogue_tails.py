@@ -24,10 +24,10 @@ import pytest
 import torch
 
 import epilogue_cases as E
+from attention_cases import compact_tables, rc_of, rope_ref
+from epilogue_cases import TOL_BF16, TOL_F32, TOL_STATS
+from support import CAN32, DEV, S, a_planes, bits, canary, check_untouched, is_canary, o_planes, pack, planes_f64, relerr, rnd, to_planes, w_planes
 from toc3d_amd import lib, synth
-
-from test_gpu_attn_rot import compact_tables, rc_of, rope_ref
-from test_gpu_ops import DEV, S, pack, planes_decode, relerr, rnd, to_planes
 
 pytestmark = pytest.mark.gpu
 BF16, X3, X3W, X3P, X3WO, X3WA = lib.BF16, lib.F32X3, lib.F32X3W, lib.F32X3P, lib.F32X3WO, lib.F32X3WA
@@ -37,20 +37,6 @@ FORMS = {"bf16": (BF16, BF16, BF16), "f32x3": (X3, X3, X3), "f32x3w": (X3W, X3W,
 SWIGLU_EPIS = (lib.EPI_SWIGLU, lib.EPI_SWIGLU_STATS, lib.EPI_SWIGLU_STATS_LN)
 EPS = 1e-6
 MA = E.M_ALIGNED
-CAN32, CAN16 = 0x41104110, 0x4110            # the canary: bf16 9.0 in every 16-bit half, so a planes buffer decodes to hi = lo = 9.0 (as f32: 9.016...)
-TOL_F32, TOL_BF16, TOL_STATS = 2e-5, 6e-3, 1e-5
-
-
-def a_planes(dt):
-    return dt in (X3P, X3WA)
-
-
-def o_planes(dt):
-    return dt in (X3P, X3WO)
-
-
-def w_planes(dt):
-    return dt in (X3W, X3P, X3WO, X3WA)
 
 
 def tdt_of(dt):
@@ -66,47 +52,9 @@ def refusal(dt, epi, v):
     return None
 
 
-def canary(rows, ld, tdt):
-    if tdt == torch.bfloat16:
-        return torch.full((rows, ld), 9.0, dtype=tdt, device=DEV)
-    t = torch.empty(rows, ld, dtype=torch.float32, device=DEV)
-    t.view(torch.int32).fill_(CAN32)
-    return t
-
-
-def is_canary(t):
-    return (t.view(torch.int16) == CAN16) if t.dtype == torch.bfloat16 else (t.view(torch.int32) == CAN32)
-
-
-def bits(t):
-    return t.view(torch.int16) if t.dtype == torch.bfloat16 else t.view(torch.int32)
-
-
 def values(t, planes):
     """The numbers a buffer holds, as f64: plain act / f32 values, or hi + lo of a planes image."""
-    if planes:
-        hi, lo = planes_decode(t)
-        return hi.double() + lo.double()
-    return t.double()
-
-
-def check_untouched(tag, buf, M, N, planes, zero_ok=False):
-    """(c) rows >= M keep the canary; so do the columns >= N of rows < M (zero_ok: each element the canary or exactly zero)."""
-    assert bool(is_canary(buf[M:]).all()), f"{tag}: rows >= M = {M} were written"
-    if buf.shape[1] == N:
-        return
-    if planes:
-        hi, lo = planes_decode(buf[:M])
-        hi, lo = hi[:, N:], lo[:, N:]
-        ok = (hi == 9.0) & (lo == 9.0)
-        if zero_ok:
-            ok |= (hi == 0) & (lo == 0)
-    else:
-        pad = buf[:M, N:]
-        ok = is_canary(pad)
-        if zero_ok:
-            ok |= pad == 0
-    assert bool(ok.all()), f"{tag}: {int((~ok).sum())} padding elements in columns [{N}, {buf.shape[1]}) hold neither the canary{' nor zero' if zero_ok else ''} (M = {M})"
+    return planes_f64(t) if planes else t.double()
 
 
 def check_stats(tag, st, M, slots, cap):

@@ -18,20 +18,13 @@ import pytest
 import torch
 
 import toc3d_amd
+from head_queries_cases import BANK
+from support import DEV, rel_max_zero_ok
 from toc3d_amd import synth
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-BANK = ("memory_embedding", "memory_reference_point", "memory_timestamp", "memory_egopose", "memory_velo")
 TINY, TINY_SHAPE = synth.HEAD_TINY, synth.HEAD_TINY_SHAPE
-
-
-def rel_max(a, b):
-    a, b = torch.as_tensor(a).double().cpu(), torch.as_tensor(b).double().cpu()
-    if not b.any():
-        return 0.0 if not a.any() else float("inf")
-    return ((a - b).abs().max() / b.abs().max()).item()
 
 
 def build(sizes, seed=0, **kw):
@@ -69,7 +62,7 @@ def check_against_fixture(tag, res, g, g64, sizes, rows=None):
         for k in BANK:
             pairs.append((k, bank[k][:, ::rows] if rows else bank[k], 1e-4 if k in ("memory_timestamp", "memory_egopose") else 1e-3))
         for k, v, tol in pairs:
-            e, e64 = rel_max(v, g[f"f{f}_{k}"]), rel_max(v, g64[f"f{f}_{k}"])
+            e, e64 = rel_max_zero_ok(v, g[f"f{f}_{k}"]), rel_max_zero_ok(v, g64[f"f{f}_{k}"])
             worst[k] = max(worst.get(k, 0.0), e)
             print(f"[{tag}] frame {f} {k}: rel max vs the f32 reference {e:.2e} (vs its f64 twin {e64:.2e}), bar {tol:.0e}")
             assert e < tol, (tag, f, k, e)
@@ -83,7 +76,7 @@ def check_against_fixture(tag, res, g, g64, sizes, rows=None):
             assert n == g[f"f{f}_b{b}_labels"].shape[0], f"{tag} frame {f} sample {b}: {n} boxes decoded, the reference keeps {g[f'f{f}_b{b}_labels'].shape[0]}"
             assert torch.equal(labels[b, :n], torch.from_numpy(g[f"f{f}_b{b}_labels"])) and torch.equal(qidx[b, :n], torch.from_numpy(g[f"f{f}_b{b}_query"])), \
                 f"{tag} frame {f} sample {b}: decoded labels / query order differ from the reference's"
-            eb, es = rel_max(boxes[b, :n], g[f"f{f}_b{b}_bboxes"]), rel_max(scores[b, :n], g[f"f{f}_b{b}_scores"])
+            eb, es = rel_max_zero_ok(boxes[b, :n], g[f"f{f}_b{b}_bboxes"]), rel_max_zero_ok(scores[b, :n], g[f"f{f}_b{b}_scores"])
             print(f"[{tag}] frame {f} sample {b}: {n} boxes, rel max boxes {eb:.2e} scores {es:.2e}")
             assert eb < 1e-3 and es < 1e-3
     return worst
@@ -163,7 +156,7 @@ def test_c_shipped_sizes_frame0_fp32x3_against_the_reference():
     assert tuple(out["all_cls_scores"].shape) == (6, 1, 900, 10) and tuple(out["all_bbox_preds"].shape) == (6, 1, 900, 10)
     for k in ("all_cls_scores", "all_bbox_preds"):
         for key, v in ((f"f0_{k}_last", out[k][-1]), (f"f0_{k}", out[k][:-1, :, ::rows])):
-            e, e64 = rel_max(v, g[key]), rel_max(v, g["f64_" + key])
+            e, e64 = rel_max_zero_ok(v, g[key]), rel_max_zero_ok(v, g["f64_" + key])
             print(f"[full fp32x3] frame 0 {key}: rel max vs the f32 reference {e:.2e} (vs its f64 twin {e64:.2e}), bar 1e-03")
             assert tuple(v.shape) == g[key].shape and e < 1e-3, (key, e)
 

@@ -1,6 +1,6 @@
 """GPU: toc3d_amd.HeadOutputs / toc3d_amd.NMSFreeCoder and the kernels of csrc/head_outputs.hip against the REAL reference's fixtures
 (tests/golden/head_outputs_*.npz, written by tools/gen_golden_head_outputs.py), against f64 torch, and against the plain-torch restatement of
-tests/test_cpu_head_outputs.py.  Error measure as in tests/test_gpu_decoder.py: max-abs error over max-abs reference, per output group (class logits, centres,
+tests/head_outputs_cases.py.  Error measure as in tests/test_gpu_decoder.py: max-abs error over max-abs reference, per output group (class logits, centres,
 sizes, rotation, velocity -- columns of different scale); the bf16 bounds are relative to a torch-bf16 control on the same card.
 
 Every test prints the figures it asserts on (run with -s); profiles/head_outputs_parity.txt holds that output as measured on an MI355X."""
@@ -11,14 +11,12 @@ import pytest
 import torch
 
 import toc3d_amd
-from test_cpu_decoder import rel_max
-from test_cpu_head_outputs import GROUPS, group_errors, inverse_sigmoid, restated_branches, restated_decode, rows_without_inf
-from test_gpu_decoder import build as build_decoder
-from test_gpu_decoder import rel_l2
+from decoder_cases import build as build_decoder
+from head_outputs_cases import GROUPS, group_errors, inverse_sigmoid, restated_branches, restated_decode, rows_without_inf
+from support import DEV, planes_bf16, rel_l2, rel_max
 from toc3d_amd import lib, synth
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 FLT_MAX = float(np.finfo(np.float32).max)
 
 
@@ -47,7 +45,7 @@ def _full(golden_dir):
 # ---- the module against the reference's fixtures ----------------------------------------------------------------------------------------------
 def test_tiny_fp32x3_matches_reference_golden(golden_dir):
     """fp32x3 (the default) < 1e-3 per output group, the project's parity bar, on both levels -- replayed plan; the cleaned outs_dec exactly (NaN -> 0,
-    +-inf -> +-FLT_MAX).  The two rows that held +-inf are compared on the cleaned tensor only (test_cpu_head_outputs.rows_without_inf says why)."""
+    +-inf -> +-FLT_MAX).  The two rows that held +-inf are compared on the cleaned tensor only (head_outputs_cases.rows_without_inf says why)."""
     g = np.load(os.path.join(golden_dir, "head_outputs_tiny.npz"))
     sizes, shape = synth.HEAD_OUTPUTS_TINY, synth.HEAD_OUTPUTS_TINY_SHAPE
     inp = synth.head_outputs_inputs(sizes, shape)
@@ -127,12 +125,6 @@ def test_last_level_plan_replay_and_reruns_are_bit_identical(golden_dir, precisi
 
 
 # ---- the row kernels alone, against f64 ----------------------------------------------------------------------------------------------------------
-def _planes(buf, M, E):
-    """(hi, lo) of the first E columns of an f32-shaped buffer [rows, ld] written as planes (include/toc3d.h: 128-byte groups of 32 elements, hi then lo)."""
-    raw = buf[:M].contiguous().view(torch.bfloat16).view(M, -1, 64)[:, :E // 32]
-    return raw[..., :32].reshape(M, E), raw[..., 32:].reshape(M, E)
-
-
 @pytest.mark.parametrize("E", [64, 192, 256])
 def test_nan_to_num_rows_is_exact_in_every_output_form(E):
     M, ldx, ldo, lda = 13, E + 8, E + 4, E + 32
@@ -150,7 +142,7 @@ def test_nan_to_num_rows_is_exact_in_every_output_form(E):
         assert torch.equal(out[:M, :E].cpu(), want) and bool((out[M:] == 777.0).all()) and bool((out[:, E:] == 777.0).all())
         assert bool((act[M:] == 777.0).all())
         if dt == lib.F32X3P:
-            hi, lo = _planes(act, M, E)
+            hi, lo = planes_bf16(act, M, E)
             assert torch.equal(hi.cpu(), want.bfloat16()) and torch.equal(lo.cpu(), (want - want.bfloat16().float()).bfloat16())
             assert bool((act[:M, E:] == 777.0).all())
         else:
@@ -183,7 +175,7 @@ def test_ln_relu_rows_against_f64(E):
     print(f"[ln_relu_rows E={E}] rel max err vs f64 {err:.2e}")
     assert err < 1e-4 and bool((f32 >= 0).all())
     assert torch.equal(got[lib.BF16][:M, :2 * E], f32.bfloat16()), "the bf16 form is the f32 form rounded once"
-    hi, lo = _planes(got[lib.F32X3P], M, 2 * E)
+    hi, lo = planes_bf16(got[lib.F32X3P], M, 2 * E)
     assert torch.equal(hi, f32.bfloat16()) and torch.equal(lo, (f32 - f32.bfloat16().float()).bfloat16())
     solo = torch.full((M, E), 777.0, device=DEV)                                       # the LayerNorm half alone (E_relu = 0)
     lib.call("toc3d_head_ln_relu_rows", lib.F32, x, ldx, gamma, beta, 1e-5, solo, E, M, E, 0, lib.stream_ptr())

@@ -14,16 +14,10 @@ import torch
 import toc3d_amd
 from toc3d_amd import lib, synth
 
-from test_gpu_epilogue_tails import bits, canary, is_canary
-from test_gpu_ops import DEV, S, planes_decode, rnd
+from support import DEV, S, bits, canary, is_canary, planes_decode, rel_max, rnd
 
 pytestmark = pytest.mark.gpu
 TOKENS = {1: (1, 1, 1, 1), 5: (1, 1, 1, 5), 24: (2, 2, 2, 3)}          # tokens -> (B, N, h, w)
-
-
-def rel_max(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return ((a - b).abs().max() / b.abs().max()).item()
 
 
 def check_planes(tag, planes, plain, M, width):

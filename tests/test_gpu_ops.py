@@ -11,45 +11,11 @@ import pytest
 import torch
 
 from oracle import toc3d_oracle as O
+from support import DEV, S, _pack_scorer, _run_topk, as_act, pack, planes_decode, relerr, rnd, ru, to_planes
 from toc3d_amd import configs, lib, synth
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 DTYPES = [("fp32", lib.F32, torch.float32), ("bf16", lib.BF16, torch.bfloat16)]
-
-
-def S():
-    return lib.stream_ptr()
-
-
-def rnd(*shape, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(*shape, generator=g) * scale
-
-
-def relerr(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return ((a - b).abs().max() / b.abs().max().clamp_min(1e-30)).item()
-
-
-def ru(a, b):
-    return (a + b - 1) // b * b
-
-
-def pack(w, dt, tdt):
-    N, K = w.shape
-    out = torch.empty(ru(N, 128), ru(K, 64), dtype=tdt, device=DEV)
-    lib.call("toc3d_pack_weight", dt, w.to(DEV).contiguous(), N, K, out, out.shape[0], out.shape[1], S())
-    return out
-
-
-def as_act(x, tdt, Kp=None):
-    """f32 CPU [M,K] -> act on device with K zero-padded to Kp."""
-    M, K = x.shape
-    Kp = Kp or ru(K, 64)
-    out = torch.zeros(M, Kp, dtype=tdt, device=DEV)
-    out[:, :K] = x.to(DEV).to(tdt)
-    return out
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -273,25 +239,6 @@ def test_rank_desc_is_a_stable_descending_sort():
         assert torch.equal(order.cpu(), ref)
 
 
-def _topk_bufs(V, h, w, L, k):
-    N = L * L
-    nW = V * (-(-h // L)) * (-(-w // L))
-    ms = int(lib.load().toc3d_window_topk_rows(V, h, w, L, k))
-    i32 = dict(dtype=torch.int32, device=DEV)
-    return dict(nW=nW, N=N, ms=ms, order=torch.empty(nW, N, **i32), tok=torch.empty(nW, N, **i32), wgt=torch.empty(nW, N, device=DEV),
-                prow=torch.empty(nW, N, **i32), crow_tok=torch.full((ms,), -9, **i32), rep_index=torch.full((ms,), -9, **i32),
-                rep_row=torch.empty(nW, **i32), arows=torch.full((nW, k + 1), -9, **i32), aslots=torch.full((nW, k + 1), -9, **i32),
-                acount_q=torch.empty(nW, **i32), acount_k=torch.empty(nW, **i32))
-
-
-def _run_topk(scores, V, h, w, L, k):
-    b = _topk_bufs(V, h, w, L, k)
-    b["crow_rc"] = torch.full((b["ms"],), -9, dtype=torch.int32, device=DEV)
-    lib.call("toc3d_window_topk", scores.to(DEV), V, h, w, L, k, b["order"], b["tok"], b["wgt"], b["prow"], b["crow_tok"], b["rep_index"],
-             b["rep_row"], b["arows"], b["aslots"], b["acount_q"], b["acount_k"], b["crow_rc"], S())
-    return b
-
-
 @pytest.mark.parametrize("L,ratio", [(16, 0.5), (16, 0.3), (20, 0.4), (20, 0.7), (7, 0.5), (14, 0.6), (33, 0.3), (64, 0.1)])
 def test_window_topk_matches_oracle(L, ratio):
     V, h, w = 3, 20, 50
@@ -442,23 +389,6 @@ def test_attention_virtual_pad_keys_equal_explicit_pad_rows(name, dt, tdt):
 
 
 # ---------------------------------------------------------------------------------------------------
-def _pack_scorer(sd, pre):
-    f = lambda k: sd[pre + k].to(DEV).float().contiguous()
-    l = lib.load()
-    mw = torch.empty(l.toc3d_motion_weights_floats(), device=DEV)
-    d3 = torch.arange(128, dtype=torch.float32)
-    d3 = (10000 ** (2 * torch.div(d3, 2, rounding_mode="floor") / 128)).to(DEV)
-    d1 = torch.arange(256, dtype=torch.float32)
-    d1 = (10000 ** (2 * torch.div(d1, 2, rounding_mode="floor") / 256)).to(DEV)
-    srcs = [f("query_embedding.0.weight"), f("query_embedding.0.bias"), f("query_embedding.2.weight"), f("query_embedding.2.bias")]
-    for m in ("ego_pose_pe.", "ego_pose_queries."):
-        srcs += [f(m + "reduce.0.weight"), f(m + "reduce.0.bias"), f(m + "gamma.weight"), f(m + "gamma.bias"), f(m + "beta.weight"), f(m + "beta.bias")]
-    srcs += [f("time_embedding.0.weight"), f("time_embedding.0.bias"), f("time_embedding.1.weight"), f("time_embedding.1.bias"), f("pc_range"), d3, d1]
-    lib.call("toc3d_pack_motion_weights", *srcs, mw, S())
-    torch.cuda.synchronize()
-    return mw
-
-
 @pytest.mark.parametrize("epoch", [False, True])
 def test_query_scorer_against_reference_fixture(golden_dir, epoch):
     """Motion-aware queries + collapsed cross-attention scorer + Gumbel mask vs the REAL reference's outputs."""
@@ -1179,20 +1109,6 @@ def test_linear_bf16x3_products_on_f32_operands(M, N, K):
     assert relerr(out, torch.nn.functional.gelu(ref)) < 2e-5
     with pytest.raises(RuntimeError, match="bf16 x 3"):
         lib.call("toc3d_linear_fused", lib.F32X6, lib.EPI_RESIDUAL_STATS, 0, a_d, Kp, w_d, Kp, b.to(DEV), out, N, None, 0, 0, None, None, M, N, Kp, 0, *lib.NO_FUSED, S())   # (x 3 serves the folded-LayerNorm epilogues 4-7 since rounds 3 / 4; x 6 does not)
-
-
-def to_planes(t):
-    """f32 [rows, K] on the device -> a new buffer in (hi, lo) planes (toc3d_x3_planes, out of place)."""
-    out = torch.empty_like(t)
-    lib.call("toc3d_x3_planes", t, t.shape[1], out, out.shape[1], t.shape[0], t.shape[1], S())
-    return out
-
-
-def planes_decode(p):
-    """(hi, lo) planes -> (hi, lo) as f32 tensors [rows, K] (the layout of include/toc3d.h, TOC3D_DTYPE_F32X3W / F32X3P, read back on the host side)."""
-    rows, K = p.shape
-    b = p.contiguous().view(torch.bfloat16).view(rows, K // 32, 2, 32)
-    return b[:, :, 0, :].reshape(rows, K).float(), b[:, :, 1, :].reshape(rows, K).float()
 
 
 def test_x3_planes_layout_and_in_place():

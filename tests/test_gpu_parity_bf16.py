@@ -20,29 +20,11 @@ import torch
 
 import toc3d_amd
 from oracle import toc3d_oracle as O
+from support import DEV, iou, rel_l2, rel_max
 from toc3d_amd import configs, synth
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 ARGS = ("x", "temp_queries", "temp_ref_points", "temp_vel", "temp_timestamp", "temp_ego_pose", "ego_pose_inv")
-
-
-def rel_l2(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return ((a - b).norm() / b.norm()).item()
-
-
-def rel_max(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return ((a - b).abs().max() / b.abs().max()).item()
-
-
-def iou(a, b):
-    res = []
-    for ra, rb in zip(np.asarray(a.cpu()), np.asarray(b)):
-        sa, sb = set(ra.tolist()), set(rb.tolist())
-        res.append(len(sa & sb) / max(1, len(sa | sb)))
-    return min(res)
 
 
 def build(name, precision, stress=False):

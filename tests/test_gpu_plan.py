@@ -9,10 +9,10 @@ import pytest
 import torch
 
 import toc3d_amd
+from support import DEV
 from toc3d_amd import configs, lib, synth
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 
 
 def build(name, precision="bf16", mode="eager", groups=1):

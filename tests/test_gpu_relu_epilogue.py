@@ -7,8 +7,8 @@ toc3d_linear_ex and toc3d_linear_fused; its third value, the split-K variant, se
 
   * the output is BIT-EQUAL to EPI_BIAS followed by toc3d_relu_inplace on the same variant -- inputs centred (about half the pre-activations negative), one column
     NaN (a NaN bias: relu gives 0), one column a tiny negative and one a negative f32 denormal (zero weights: relu gives +0);
-  * it lies within the bars tests/test_gpu_epilogue_tails.py holds these output classes to (bf16-rounded 6e-3, f32 and the bf16 x 3 / x 6 forms 2e-5 of the output's
-    max) against f64 relu(A.W^T + b) on the operands the kernel reads;
+  * it lies within the bars tests/test_gpu_epilogue_tails.py holds these output classes to (TOL_* of tests/epilogue_cases.py:
+    bf16-rounded 6e-3, f32 and the bf16 x 3 / x 6 forms 2e-5 of the output's max) against f64 relu(A.W^T + b) on the operands the kernel reads;
   * canaries around the written region (spare rows and columns) are untouched."""
 import functools
 
@@ -17,8 +17,8 @@ import torch
 
 from toc3d_amd import gemm, lib
 
-from test_gpu_epilogue_tails import TOL_BF16, TOL_F32, a_planes, bits, canary, check_untouched
-from test_gpu_ops import DEV, S, pack, relerr, rnd, ru, to_planes
+from epilogue_cases import TOL_BF16, TOL_F32
+from support import DEV, S, a_planes, bits, canary, check_untouched, pack, relerr, rnd, ru, to_planes
 
 pytestmark = pytest.mark.gpu
 MS, NS, KS = (1, 63, 64, 65, 129), (8, 64, 72, 130), (64, 192)

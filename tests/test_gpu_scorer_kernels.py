@@ -49,55 +49,17 @@ import pytest
 import torch
 
 import scorer_cases as SC
-from test_gpu_ops import DEV, S, _pack_scorer, rnd
+from support import DEV, S, _pack_scorer, d, is_sent, rnd, same_bits, sent, worst_report
 from toc3d_amd import lib
 
 pytestmark = pytest.mark.gpu
 U = SC.U
 G = 3                                                    # guard rows on both sides of every output
-SENT32, SENT16 = 0x7FC17FC1, 0x7FC1
-WORST = {}
-
-
-def note(key, ratio):
-    WORST[key] = max(WORST.get(key, 0.0), float(ratio))
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _report():
-    yield
-    print("\n[scorer kernels] worst measured error as a fraction of its bound (<= 1.0 required)")
-    for key in sorted(WORST):
-        print(f"[scorer kernels] {key:<58s} {WORST[key]:.3f}")
-
-
-def sent(rows, cols, bf16=False):
-    """[rows, cols] filled with a NaN whose 16-bit halves are both 0x7fc1 (a bf16 NaN; 0x7fc17fc1 is an f32 NaN)."""
-    if bf16:
-        return torch.full((rows, cols), SENT16, dtype=torch.int16, device=DEV).view(torch.bfloat16)
-    return torch.full((rows, cols), SENT32, dtype=torch.int32, device=DEV).view(torch.float32)
-
-
-def is_sent(t):
-    t = t.cpu().contiguous()
-    return bool((t.view(torch.int16) == SENT16).all()) if t.dtype == torch.bfloat16 else bool((t.view(torch.int32) == SENT32).all())
-
-
-def bits(t):
-    t = t.contiguous()
-    return t.view(torch.int16) if t.dtype == torch.bfloat16 else t.view(torch.int32)
-
-
-def same_bits(a, b):
-    return torch.equal(bits(a.cpu()), bits(b.cpu()))
+note, _report = worst_report("scorer kernels", 58, bound="bound")
 
 
 def guards_clean(full, n):
     return is_sent(full[:G]) and is_sent(full[G + n:])
-
-
-def d(t):
-    return None if t is None else t.to(DEV).contiguous()
 
 
 def check(tag, got, ref, tol):

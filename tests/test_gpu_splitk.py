@@ -10,7 +10,7 @@ import pytest
 import torch
 
 from toc3d_amd import lib
-from test_gpu_ops import DEV, S, as_act, pack, relerr, rnd
+from support import DEV, S, as_act, pack, relerr, rnd
 
 pytestmark = pytest.mark.gpu
 

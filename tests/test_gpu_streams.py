@@ -18,17 +18,16 @@
 Every test prints the figures it asserts on (run with -s)."""
 import os
 
-import numpy as np
 import pytest
 import torch
 
 import scorer_cases as SC
 import toc3d_amd
 from oracle import toc3d_oracle as O
+from support import DEV, iou, rel_max, to_dev
 from toc3d_amd import configs, lib, synth
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 S = lambda: torch.cuda.current_stream().cuda_stream
 SENTINEL = 0x7FC0BEEF                         # a NaN no kernel produces: the buffers are compared as bits
@@ -122,19 +121,6 @@ def run_backbone(m, inp, prev, times=3):
     return dict(keep=[k.clone() for k in out.keep_idx], mask=[t.clone() for t in out.token_masks], feat=out.img_feats["last_feat"].clone())
 
 
-def rel_max(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return ((a - b).abs().max() / b.abs().max()).item()
-
-
-def iou(a, b):
-    res = []
-    for ra, rb in zip(a.cpu().numpy(), np.asarray(b)):
-        sa, sb = set(ra.tolist()), set(rb.tolist())
-        res.append(len(sa & sb) / max(1, len(sa | sb)))
-    return min(res)
-
-
 BACKBONE_CASES = [(p, g, lm) for p in ("fp32", "fp32x3", "bf16") for g in (1, 2) for lm in ("plan", "eager")] + [("fp32x3", 4, "plan"), ("bf16", 4, "eager")]
 
 
@@ -214,10 +200,6 @@ def build_detector(precision, launch_mode="plan"):
         det.img_backbone.load_tuning(path)
         det.img_neck._tuned.update(det.img_backbone._tuned)
     return det
-
-
-def to_dev(frame):
-    return {k: v.to(DEV) for k, v in frame["data"].items()}
 
 
 def snapshot(det, outs, results, B):

@@ -40,7 +40,7 @@ import torch
 
 import token_cases as T
 from oracle import toc3d_oracle as O
-from test_gpu_ops import DEV, S, _run_topk, rnd
+from support import DEV, S, _run_topk, bits, is_sent, planes_halves, rnd, sent, worst_report
 from toc3d_amd import lib
 
 pytestmark = pytest.mark.gpu
@@ -52,41 +52,16 @@ COLS = [4, 60, 252, 256, 260, 508, 516, 1020, 1024]
 KINDS = ["f32", "bf16", "planes"]
 DT = {"f32": lib.F32, "bf16": lib.BF16, "planes": lib.F32X3P}
 OUT_ROUND = {"f32": 0.0, "bf16": 2.0 ** -8, "planes": 2.0 ** -16}
-WORST = {}
+note, _report = worst_report("token kernels", 58)
 
 
-def note(key, ratio):
-    WORST[key] = max(WORST.get(key, 0.0), float(ratio))
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _report():
-    yield
-    print("\n[token kernels] worst measured error as a fraction of its derived bound (<= 1.0 required)")
-    for key in sorted(WORST):
-        print(f"[token kernels] {key:<58s} {WORST[key]:.3f}")
-
-
-# ---- buffers with sentinels ---------------------------------------------------------------------------
-def sent(rows, cols, kind):
-    """[rows, cols] of the output type filled with a NaN whose 16-bit halves are both 0x7fc1 (a bf16 NaN; 0x7fc17fc1 is an f32 NaN)."""
-    if kind == "bf16":
-        return torch.full((rows, cols), 0x7FC1, dtype=torch.int16, device=DEV).view(torch.bfloat16)
-    return torch.full((rows, cols), 0x7FC17FC1, dtype=torch.int32, device=DEV).view(torch.float32)
-
-
-def is_sent(t):
-    t = t.cpu()
-    return (t.view(torch.int16) == 0x7FC1).all() if t.dtype == torch.bfloat16 else (t.contiguous().view(torch.int32) == 0x7FC17FC1).all()
-
-
+# ---- buffers with sentinels (support.sent / is_sent) ----------------------------------------------------
 def decode(a, kind, C):
     """Output rows [R, ld] (CPU) -> (values f64 [R, C], True if nothing of the columns [C, ld) was written)."""
     R, ld = a.shape
     if kind != "planes":
-        return a[:, :C].double(), bool(is_sent(a[:, C:])) if ld > C else True
-    b = a.contiguous().view(torch.int16).view(R, ld // 32, 2, 32)
-    hi, lo = b[:, :, 0, :].reshape(R, ld), b[:, :, 1, :].reshape(R, ld)
+        return a[:, :C].double(), is_sent(a[:, C:]) if ld > C else True
+    hi, lo = planes_halves(a)
     clean = bool((hi[:, C:] == 0x7FC1).all() and (lo[:, C:] == 0x7FC1).all())
     hv, lv = hi[:, :C].contiguous().view(torch.bfloat16).double(), lo[:, :C].contiguous().view(torch.bfloat16).double()
     assert bool((lv.abs() <= 2.0 ** -8 * hv.abs()).all()), "lo plane is the bf16 remainder of the hi plane"
@@ -197,17 +172,13 @@ def gather_inputs(sel, C, seed=11):
 
 def launch_gather(sel, xd, C, kind, lda, kept_copy, gw, gb, split=None, scratch=None):
     ms = sel["ms"]
-    short, a = sent(ms + 2 * G, C, "f32"), sent(ms + 2 * G, lda, kind)
+    short, a = sent(ms + 2 * G, C, False), sent(ms + 2 * G, lda, kind == "bf16")
     head = (DT[kind], xd, C, sel["tok"], sel["wgt"], sel["crow_tok"], sel["rep_row"], sel["nW"], sel["N"], sel["k"], ms, gw, gb, EPS, short[G:], a[G:], lda, kept_copy)
     if split is None:
         lib.call("toc3d_gather_merge_ln_ex", *head, S())
     else:
         lib.call("toc3d_gather_merge_ln_split", *head, scratch, scratch.numel() * 4, split, S())
     return short, a
-
-
-def bits(t):
-    return t.view(torch.int16) if t.dtype == torch.bfloat16 else t.view(torch.int32)
 
 
 def check_gather(tag, sel, x, rep, mag, C, kind, lda, kept_copy, short_full, a_full, gw, gb):
@@ -335,7 +306,7 @@ def rebase_case(tag, sel, C, kind, ldo, seed=31):
     slow_full = rows_like_x(ms + 2 * G, C, seed)
     r1, r2 = raw_like(nW, C, seed + 1), raw_like(nW, C, seed + 2)
     gw, gb = params(C)
-    sd, out = slow_full.to(DEV), sent(ms + 2 * G, ldo, kind)
+    sd, out = slow_full.to(DEV), sent(ms + 2 * G, ldo, kind == "bf16")
     lib.call("toc3d_rebase_layernorm_rows", DT[kind], sd[G:], C, sel["rep_index"], sel["tok"], sel["wgt"], N, k, r1.to(DEV), r2.to(DEV),
              gw.float().to(DEV), gb.float().to(DEV), EPS, out[G:], ldo, ms, S())
     got, out = sd.cpu(), out.cpu()
@@ -401,7 +372,7 @@ def test_rebase_equals_scatter_and_regather(C, L, k):
     s2, _ = launch_gather(sel, xd, C, "f32", C, 1, gwd, gbd)
     rows = s2[G:G + ms]
     rows[reps.to(DEV)] = (rows[reps.to(DEV)] + r1d) + r2d
-    a2 = sent(ms, C, "f32")
+    a2 = sent(ms, C, False)
     lib.call("toc3d_rebase_layernorm_rows", lib.F32, rows, C, sel["rep_index"], sel["tok"], sel["wgt"], N, k, r1d, r2d, gwd, gbd, EPS, a2, C, ms, S())
     p1, p2, o1, o2 = s1b[G:G + ms].cpu(), rows.cpu(), a1b[G:G + ms].cpu(), a2.cpu()
     keptm = ref["crow_tok"] != -2
@@ -450,7 +421,7 @@ def test_layernorm_rows_wide(C, kind):
         scale = 0.5 + torch.rand(n_src, generator=g)
         for use_idx, use_scale in ((False, False), (True, False), (True, True), (False, True)):
             for ldo, _ in ld_pair(C, kind):
-                out = sent(M + 2 * G, ldo, kind)
+                out = sent(M + 2 * G, ldo, kind == "bf16")
                 lib.call("toc3d_layernorm_rows", DT[kind], xd, ldx, idx.to(DEV) if use_idx else None, scale.to(DEV) if use_scale else None, gwd, gbd, EPS,
                          out[G:], ldo, M, C, S())
                 out = out.cpu()
