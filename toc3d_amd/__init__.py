@@ -1,7 +1,7 @@
 """toc3d_amd -- MI355X (gfx950) implementation of the ToC3D / EVA-02 ViT backbone hot path.
 
 Importing the package registers ``ToC3DEVAViT``, ``EVA_ViT`` (BACKBONES), ``CPFPN`` (NECKS), ``PETRTemporalTransformer`` (TRANSFORMER), ``NMSFreeCoder``
-(BBOX_CODERS), ``StreamPETRHead`` (HEADS) and ``Petr3D`` (DETECTORS) under the reference's type names, like ``projects/mmdet3d_plugin`` does on import (``tools/test.py:133-145``).
+(BBOX_CODERS), ``StreamPETRHead`` and ``FocalHead`` (HEADS) and ``Petr3D`` (DETECTORS) under the reference's type names, like ``projects/mmdet3d_plugin`` does on import (``tools/test.py:133-145``).
 """
 from .backbone import EVA_ViT, ToC3DEVAViT, ToC3DViTReturnType
 from .neck import CPFPN
@@ -12,6 +12,7 @@ from .decoder import PETRTemporalTransformer
 from .head_outputs import HeadOutputs, NMSFreeCoder
 from .head_queries import HeadQueries
 from .head import StreamPETRHead
+from .focal_head import FocalHead
 from .detector import Petr3D
 from .registry import (BACKBONES, BBOX_CODERS, DETECTORS, HEADS, NECKS, TRANSFORMER, build_backbone, build_bbox_coder, build_detector, build_head, build_neck,
                        build_transformer, register_all)
@@ -20,4 +21,4 @@ register_all()
 
 __all__ = ["ToC3DEVAViT", "EVA_ViT", "CPFPN", "ToC3DViTReturnType", "BACKBONES", "NECKS", "build_backbone", "build_neck", "prepare_images", "TemporalMemory", "HeadTokenEmbedding",
            "PETRTemporalTransformer", "TRANSFORMER", "build_transformer", "HeadOutputs", "HeadQueries", "NMSFreeCoder", "BBOX_CODERS", "build_bbox_coder",
-           "StreamPETRHead", "HEADS", "build_head", "Petr3D", "DETECTORS", "build_detector"]
+           "StreamPETRHead", "FocalHead", "HEADS", "build_head", "Petr3D", "DETECTORS", "build_detector"]

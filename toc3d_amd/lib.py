@@ -151,6 +151,13 @@ STREAMS_ABI = 1                 # == TOC3D_STREAMS_ABI
 _STREAMS_SIGS = {
     "toc3d_score_head_frames": "ipllppppllpppp",
 }
+# include/toc3d_focal.h (the 2-D auxiliary head, toc3d_amd.FocalHead): a side header as toc3d_streams.h is, for the same reason, bound the same way
+FOCAL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "toc3d_focal.h")
+FOCAL_ABI = 1                   # == TOC3D_FOCAL_ABI
+_FOCAL_SIGS = {
+    "toc3d_focal_gn_stats": "iplllllfpp",
+    "toc3d_focal_heads": "iplppppppppllllplppppp",
+}
 
 _lib = None
 
@@ -237,11 +244,30 @@ def _bind_streams(lib):
     lib._toc3d_streams_bound = True
 
 
+def _bind_focal(lib):
+    """The entry points of include/toc3d_focal.h, bound when the first of them is called."""
+    try:
+        lib.toc3d_focal_abi.restype = _I
+        abi = lib.toc3d_focal_abi()
+        fns = {name: getattr(lib, name) for name in _FOCAL_SIGS}
+    except AttributeError:
+        abi, fns = None, {}
+    if abi != FOCAL_ABI:
+        raise RuntimeError(f"{LIB_PATH} reports focal ABI {abi}, this package binds {FOCAL_ABI} (include/toc3d_focal.h): "
+                           "rebuild the library (`make -C toc3d_amd/csrc`)")
+    for name, fn in fns.items():
+        fn.restype = _I
+        fn.argtypes = [_CT[c] for c in _FOCAL_SIGS[name]]
+    lib._toc3d_focal_bound = True
+
+
 def call(name: str, *args):
     """Invoke a C-ABI entry point; tensors are passed as device pointers; raises on a non-zero return."""
     lib = load()
     if name in _STREAMS_SIGS and not getattr(lib, "_toc3d_streams_bound", False):
         _bind_streams(lib)
+    if name in _FOCAL_SIGS and not getattr(lib, "_toc3d_focal_bound", False):
+        _bind_focal(lib)
     rc = getattr(lib, name)(*[_conv(a) for a in args])
     if rc != 0:
         raise RuntimeError(f"{name} failed ({rc}): {lib.toc3d_last_error().decode()}")

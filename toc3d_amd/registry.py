@@ -1,5 +1,6 @@
 """Registry surface: ``ToC3DEVAViT`` / ``EVA_ViT`` on mmdet's BACKBONES, ``CPFPN`` on NECKS, ``PETRTemporalTransformer`` on TRANSFORMER, ``NMSFreeCoder`` on
-BBOX_CODERS, ``StreamPETRHead`` on HEADS (the reference: ``@HEADS.register_module()``, ``dense_heads/streampetr_head.py:32``), ``Petr3D`` on DETECTORS
+BBOX_CODERS, ``StreamPETRHead`` and ``FocalHead`` on HEADS (the reference: ``@HEADS.register_module()``, ``dense_heads/streampetr_head.py:32``,
+``dense_heads/focal_head.py:20``), ``Petr3D`` on DETECTORS
 (``@DETECTORS.register_module()``, ``detectors/petr3d.py:23``).
 
 The reference registers its classes with ``@BACKBONES.register_module()`` (``toc3d_eva_vit.py:25``,
@@ -61,11 +62,12 @@ def register_all():
     from .backbone import EVA_ViT, ToC3DEVAViT
     from .decoder import PETRTemporalTransformer
     from .detector import Petr3D
+    from .focal_head import FocalHead
     from .head import StreamPETRHead
     from .head_outputs import NMSFreeCoder
     from .neck import CPFPN
     for reg, cls in ((BACKBONES, ToC3DEVAViT), (BACKBONES, EVA_ViT), (NECKS, CPFPN), (TRANSFORMER, PETRTemporalTransformer), (BBOX_CODERS, NMSFreeCoder),
-                     (HEADS, StreamPETRHead), (DETECTORS, Petr3D)):
+                     (HEADS, StreamPETRHead), (HEADS, FocalHead), (DETECTORS, Petr3D)):
         try:
             reg.register_module(name=cls.__name__, force=True, module=cls)
         except TypeError:

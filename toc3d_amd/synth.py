@@ -599,6 +599,44 @@ def head_inputs(sizes: dict = None, shape: dict = None, seed: int = 0):
     return dict(frames=frames, img_metas=[dict(pad_shape=[(h * 16, w * 16, 3)]) for _ in range(B)])
 
 
+# ---- the 2-D auxiliary head (toc3d_amd.FocalHead) --------------------------------------------------------------------------------------------------------------
+# the sizes and shapes of the two fixtures (tools/gen_golden_focal_head.py); full = img_roi_head of the shipped configs on 6 x 20 x 50 tokens
+FOCAL_HEAD_FULL = dict(num_classes=10, in_channels=256, embed_dims=256, stride=16, infer_ratio=0.5)
+FOCAL_HEAD_TINY = dict(num_classes=3, in_channels=64, embed_dims=64, stride=16, infer_ratio=0.3)
+FOCAL_HEAD_FULL_SHAPE = dict(B=1, N=6, h=20, w=50)
+FOCAL_HEAD_TINY_SHAPE = dict(B=1, N=2, h=3, w=5)
+
+
+def focal_head_state_dict(sizes: dict, seed: int = 0):
+    """Seeded weights under the reference's sixteen names (``img_roi_head.*``, focal_head.py:119-134).  No zero biases, GroupNorm weights 1 + noise; the class
+    and centerness logits are a few units wide around -2 and 0, so the sampling weights spread over (0, 1) instead of crowding at the floor of an untrained head."""
+    g = torch.Generator().manual_seed(15000 + seed)
+    C, E, NC = sizes["in_channels"], sizes["embed_dims"], sizes["num_classes"]
+    r = lambda *s: torch.randn(*s, generator=g)
+    sd = OrderedDict()
+    sd["cls.weight"], sd["cls.bias"] = r(NC, E, 1, 1) * 3.0 * E ** -0.5, -2.0 + 0.3 * r(NC)
+    for tower in ("shared_reg", "shared_cls"):
+        sd[f"{tower}.0.weight"], sd[f"{tower}.0.bias"] = r(E, C, 3, 3) * (2.0 / (9 * C)) ** 0.5, 0.1 * r(E)
+        sd[f"{tower}.1.weight"], sd[f"{tower}.1.bias"] = 1.0 + 0.1 * r(E), 0.1 * r(E)
+    sd["centerness.weight"], sd["centerness.bias"] = r(1, E, 1, 1) * 3.0 * E ** -0.5, 0.2 * r(1)
+    sd["ltrb.weight"], sd["ltrb.bias"] = r(4, E, 1, 1) * 2.0 * E ** -0.5, -1.5 + 0.3 * r(4)
+    sd["center2d.weight"], sd["center2d.bias"] = r(2, E, 1, 1) * E ** -0.5, 0.1 * r(2)
+    return sd
+
+
+def focal_head_inputs(sizes: dict, shape: dict, seed: int = 0):
+    """Seeded ``img_feats`` (B, N, C, h, w) (unit variance, as the neck's level 0) and ``location`` (B*N, h, w, 2): the normalised pixel centres of
+    ``misc.locations`` (models/utils/misc.py:59-84) at the head's stride on a pad_shape of (h * stride, w * stride), what ``Petr3D.prepare_location`` builds."""
+    g = torch.Generator().manual_seed(15500 + seed)
+    B, N, h, w, s = shape["B"], shape["N"], shape["h"], shape["w"], sizes["stride"]
+    feats = torch.randn(B, N, sizes["in_channels"], h, w, generator=g)
+    shifts_x = (torch.arange(0, s * w, step=s, dtype=torch.float32) + s // 2) / (w * s)
+    shifts_y = (torch.arange(0, h * s, step=s, dtype=torch.float32) + s // 2) / (h * s)
+    shift_y, shift_x = torch.meshgrid(shifts_y, shifts_x, indexing="ij")
+    location = torch.stack((shift_x.reshape(-1), shift_y.reshape(-1)), dim=1).reshape(h, w, 2)
+    return dict(img_feats=feats, location=location[None].repeat(B * N, 1, 1, 1))
+
+
 # ---- the assembled detector (toc3d_amd.Petr3D) -------------------------------------------------------------------------------------------------------------
 # the sizes of the detector fixture (tools/gen_golden_detector.py): the tiny backbone at 6 x 320 x 800 (the shape every tiny backbone fixture is proven at), the
 # tiny neck, and a head whose topk_proposals equals the backbone's pruning_num_queries, so the backbone reads real proposals from frame 1 on
