@@ -22,7 +22,9 @@ Differences to the reference, by design:
   centres itself (``toc3d_head_frustum_inputs``) and never reads it;
 * ``rec_ego_pose`` handed to ``post_update_memory`` holds ``num_query + num_propagated`` identities, not the reference's ``num_query + 2 * num_propagated``
   (:447-449), of which it can only index the former (see :class:`toc3d_amd.HeadQueries`);
-* ``topk_indexes`` (``img_roi_head``), training (``prepare_for_dn``, losses) and ``self.training`` raise; ``precision`` is ``"fp32x3"`` (default) or ``"bf16"``;
+* ``topk_indexes`` (``img_roi_head``) raises unless the head is built with ``token_sampling=True`` -- a keyword of this package: the list then goes to the token
+  side (:class:`toc3d_amd.HeadTokenEmbedding`) and the decoder's cross-attention runs on its K keys per sample; training (``prepare_for_dn``, losses) and
+  ``self.training`` raise; ``precision`` is ``"fp32x3"`` (default) or ``"bf16"``;
 * ``coords_d`` is read from the parameter (a checkpoint's values win, as in the reference); ``pc_range`` / ``position_range`` reach the kernels as host copies
   of the config's values; as an extension to the reference, a checkpoint whose ranges differ from the config's by more than 1 % (more than a half / bf16
   rounding of the same numbers) is refused at load instead of being silently ignored.
@@ -61,11 +63,12 @@ class StreamPETRHead(_plan.DerivedState, nn.Module):
                  code_weights=None, bbox_coder=None, loss_cls=None, loss_bbox=None, loss_iou=None, train_cfg=None, test_cfg=dict(max_per_img=100),
                  depth_step=0.8, depth_num=64, LID=False, depth_start=1, position_range: Sequence[float] = (-65, -65, -8.0, 65, 65, 8.0), scalar=5,
                  noise_scale=0.4, noise_trans=0.0, dn_weight=1.0, split=0.5, init_cfg=None, normedlinear=False, precision=gemm.DEFAULT_PRECISION,
-                 launch_mode="plan", levels="all", **kwargs):
+                 launch_mode="plan", levels="all", token_sampling=False, **kwargs):
         """Every keyword of the reference's ``__init__`` (:65-111); the ``pts_bbox_head=dict(...)`` block of the shipped configs builds it unchanged.  The loss,
         assigner, denoising (``with_dn``, ``scalar``, ``noise_*``, ``dn_weight``, ``split``), ``train_cfg`` and unknown keys (``with_position``) are accepted and
         ignored -- only ``loss_cls['use_sigmoid']`` is read (the reference sizes the class branch from it, :200-203; a missing ``loss_cls`` means the
-        reference's default, a softmax classifier, and is refused like one).  Extra: ``precision``, ``launch_mode``, and ``levels`` of :class:`toc3d_amd.HeadOutputs`."""
+        reference's default, a softmax classifier, and is refused like one).  Extra: ``precision``, ``launch_mode``, ``levels`` of :class:`toc3d_amd.HeadOutputs`, and
+        ``token_sampling``: accept ``forward(..., topk_indexes=...)`` (off by default: the call raises as it always did)."""
         super().__init__()
         if precision not in _SUPPORTED:
             raise NotImplementedError(f"{_NAME}: precision {precision!r} is not implemented: the decoder and the class / box branches run in "
@@ -85,7 +88,7 @@ class StreamPETRHead(_plan.DerivedState, nn.Module):
         self.train_cfg, self.test_cfg, self.fp16_enabled, self.embed_dims = None, test_cfg, False, embed_dims
         self.depth_step, self.depth_num, self.position_dim, self.LID, self.depth_start, self.stride = depth_step, depth_num, depth_num * 3, LID, depth_start, stride
         self.num_pred, self.normedlinear, self.bg_cls_weight, self.sync_cls_avg_factor = 6, normedlinear, 0, sync_cls_avg_factor     # :192 -- six, whatever the decoder's depth
-        self.precision, self.launch_mode, self.levels = precision, launch_mode, levels
+        self.precision, self.launch_mode, self.levels, self.token_sampling = precision, launch_mode, levels, bool(token_sampling)
 
         self.transformer = registry.build_transformer(transformer, precision=precision, launch_mode=launch_mode)                        # :205
         self.bbox_coder = registry.build_bbox_coder(bbox_coder)                                                                          # :213
@@ -185,19 +188,23 @@ class StreamPETRHead(_plan.DerivedState, nn.Module):
         (pad_h, pad_w[, 3]).  ``memory_center`` is accepted and left as it is (module docstring).  Returns ``dict(all_cls_scores (L, B, Q, num_classes),
         all_bbox_preds (L, B, Q, code_size), dn_mask_dict=None)`` with Q = num_query + num_propagated and L = the decoder's layers (1 with ``levels="last"``).
         ``img_feats_rows=True``: the token rows of ``img_feats`` already sit in :meth:`img_feats_rows_buffer` of its shape (a detector's neck put them there); the
-        tensor gives the shape and the device and is not read."""
+        tensor gives the shape and the device and is not read.
+        ``topk_indexes`` (B, K, 1) or (B, K) int64 on the device (``FocalHead``'s), with ``token_sampling=True`` only: the token side and the decoder's
+        cross-attention run on the K listed tokens of every sample; queries, outputs and both memory updates are what they are without it."""
         if self.training:
             raise RuntimeError(f"{_NAME}: training mode is not implemented (call .eval(): denoising queries and the losses are out of scope)")
-        if topk_indexes is not None:
-            raise NotImplementedError(f"{_NAME}: topk_indexes (token selection by img_roi_head) is not implemented; the shipped configs pass None at eval")
+        if topk_indexes is not None and not self.token_sampling:
+            raise NotImplementedError(f"{_NAME}: topk_indexes (token selection by img_roi_head) is not implemented on a head built without token_sampling=True; "
+                                      "the shipped configs pass None at eval")
         x = data["img_feats"]
         if img_feats_rows:
             (B, N, C, h, w) = x.shape
             if C != self.in_channels or not x.is_cuda:
                 raise ValueError(f"{_NAME}: img_feats {tuple(x.shape)} on {x.device} do not fit in_channels={self.in_channels} on the GPU")
-            memory, pos_embed, _ = self._tokens.forward_rows((B, N, h, w), data["intrinsics"], data["lidar2img"], img_metas[0]["pad_shape"][0], x.device)
+            memory, pos_embed, _ = self._tokens.forward_rows((B, N, h, w), data["intrinsics"], data["lidar2img"], img_metas[0]["pad_shape"][0], x.device,
+                                                             topk_indexes=topk_indexes)
         else:
-            memory, pos_embed, _ = self._tokens(x, data["intrinsics"], data["lidar2img"], img_metas[0]["pad_shape"][0])
+            memory, pos_embed, _ = self._tokens(x, data["intrinsics"], data["lidar2img"], img_metas[0]["pad_shape"][0], topk_indexes=topk_indexes)
         bank = self._memory(x.device)
         bank.pre_update_memory(data)
         tgt, query_pos, reference_points, temp_memory, temp_pos, rec_ego_pose = self._queries.forward_from(bank)

@@ -158,6 +158,13 @@ _FOCAL_SIGS = {
     "toc3d_focal_gn_stats": "iplllllfpp",
     "toc3d_focal_heads": "iplppppppppllllplppppp",
 }
+# include/toc3d_sampled.h (the head's token side on FocalHead's sampled tokens, toc3d_amd.HeadTokenEmbedding(topk_indexes=...)): a side header likewise
+SAMPLED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "toc3d_sampled.h")
+SAMPLED_ABI = 1                 # == TOC3D_SAMPLED_ABI
+_SAMPLED_SIGS = {
+    "toc3d_head_frustum_inputs_sampled": "ippppplllllllllplplpp",
+    "toc3d_gather_token_rows": "iplpllllplp",
+}
 
 _lib = None
 
@@ -261,6 +268,23 @@ def _bind_focal(lib):
     lib._toc3d_focal_bound = True
 
 
+def _bind_sampled(lib):
+    """The entry points of include/toc3d_sampled.h, bound when the first of them is called."""
+    try:
+        lib.toc3d_sampled_abi.restype = _I
+        abi = lib.toc3d_sampled_abi()
+        fns = {name: getattr(lib, name) for name in _SAMPLED_SIGS}
+    except AttributeError:
+        abi, fns = None, {}
+    if abi != SAMPLED_ABI:
+        raise RuntimeError(f"{LIB_PATH} reports sampled ABI {abi}, this package binds {SAMPLED_ABI} (include/toc3d_sampled.h): "
+                           "rebuild the library (`make -C toc3d_amd/csrc`)")
+    for name, fn in fns.items():
+        fn.restype = _I
+        fn.argtypes = [_CT[c] for c in _SAMPLED_SIGS[name]]
+    lib._toc3d_sampled_bound = True
+
+
 def call(name: str, *args):
     """Invoke a C-ABI entry point; tensors are passed as device pointers; raises on a non-zero return."""
     lib = load()
@@ -268,6 +292,8 @@ def call(name: str, *args):
         _bind_streams(lib)
     if name in _FOCAL_SIGS and not getattr(lib, "_toc3d_focal_bound", False):
         _bind_focal(lib)
+    if name in _SAMPLED_SIGS and not getattr(lib, "_toc3d_sampled_bound", False):
+        _bind_sampled(lib)
     rc = getattr(lib, name)(*[_conv(a) for a in args])
     if rc != 0:
         raise RuntimeError(f"{name} failed ({rc}): {lib.toc3d_last_error().decode()}")
