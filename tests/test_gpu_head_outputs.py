@@ -361,7 +361,8 @@ def test_decode_of_the_modules_own_output_and_get_bboxes(golden_dir):
 def test_streaming_two_frames_decoder_head_outputs_memory():
     """Two frames of PETRTemporalTransformer -> HeadOutputs -> TemporalMemory.post_update_memory at tiny sizes, tensors handed over as they come.  After each
     frame the bank's first topk_proposals rows are exactly the outs_dec[-1] rows ranked by the module's own class scores (max sigmoid over the classes as
-    toc3d_memory_scores computes it, descending, ties to the lowest query)."""
+    toc3d_memory_scores computes it, descending, ties to the lowest query).  The expected order below comes from toc3d_memory_scores itself: that kernel is pinned
+    on its own, per element against f64, by tests/test_gpu_head_row_kernels.py::test_memory_scores."""
     dsz, dshape, hsz = synth.DECODER_TINY, synth.DECODER_TINY_SHAPE, synth.HEAD_OUTPUTS_TINY
     B, Q, E, TOPK = dshape["B"], dshape["num_query"] + dshape["num_propagated"], dsz["embed_dims"], 8
     mcfg = dict(memory_len=dshape["Nm"], topk_proposals=TOPK, num_propagated=dshape["num_propagated"], embed_dims=E)
