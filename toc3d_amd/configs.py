@@ -40,6 +40,7 @@ EVA_TINY = dict(type="EVA_ViT", **_TINY)
 
 CPFPN_CFG = dict(type="CPFPN", in_channels=[1024], out_channels=256, num_outs=2)   # ToC3D_faster.py:70-74
 CPFPN_TINY = dict(type="CPFPN", in_channels=[128], out_channels=32, num_outs=2)
+CPFPN_TINY64 = dict(type="CPFPN", in_channels=[128], out_channels=64, num_outs=2)      # the tiny neck at the narrowest width FocalHead's conv takes (64-channel K-tiles)
 
 NAMED = {
     "toc3d_faster": TOC3D_FASTER,

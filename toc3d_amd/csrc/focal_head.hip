@@ -11,14 +11,13 @@
 //                         channels of the 1x1 convs as f32 FMA chains from LDS-resident weights (17 columns would pad an MFMA tile to 128), then the sigmoids, the
 //                         box geometry and the sampling weight.
 // exp / log are the libm forms (no fast-math intrinsics): sample_weight decides a ranking.
-#include "act_rows.h"
+#include "focal_row.h"
 
 #include "../../include/toc3d_focal.h"
 
 namespace {
 
 constexpr int GN_THREADS = 1024, GN_GROUPS = 8;          // groups per workgroup: 32 groups per tower, so a workgroup never straddles two towers
-constexpr int FH_ROWS = 32;                              // pixel rows per workgroup of focal_heads_kernel (4 wavefronts x 8), all of one view
 
 // the sum of a group's partial sums part[r * wc + g * cpg + c], r < R, c < cpg (at most 128 of them), by one wavefront: every lane returns it
 TOC3D_DEV float group_sum(const float* part, int R, int wc, int g, int cpg, int lane) {
@@ -64,7 +63,6 @@ __global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(const float* __res
     }
 }
 
-TOC3D_DEV float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 TOC3D_DEV float clamp01(float x) { x = x < 0.f ? 0.f : x; return x > 1.f ? 1.f : x; }          // torch.where(x < 0, 0, x), torch.where(x > 1, 1, x): a NaN stays
 
 struct FocalArgs {
@@ -77,11 +75,6 @@ struct FocalArgs {
     int64_t ldc;
     float *box, *ctr2d, *ctrness, *weight;
     int T, E, NC, chunks;                // chunks = ceil(T / FH_ROWS) workgroups per view
-};
-
-// one wavefront per row; a lane owns the 4 consecutive columns 4 lane + 256 i (i < 4: E <= 1024) of each tower
-struct Row4 {
-    f32x4 v[4];
 };
 
 __global__ __launch_bounds__(256) void focal_heads_kernel(const FocalArgs a) {
@@ -98,61 +91,20 @@ __global__ __launch_bounds__(256) void focal_heads_kernel(const FocalArgs a) {
     if (threadIdx.x < NC + 1) s_b[threadIdx.x] = a.b_cls[threadIdx.x];
     if (threadIdx.x >= 64 && threadIdx.x < 70) s_b[NC + 1 + threadIdx.x - 64] = a.b_reg[threadIdx.x - 64];
     __syncthreads();
-    // the group of each of a lane's columns (the same in both towers, and for every row: the divisions are done once)
-    const int cpg = E / 32;
     int grp[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int c = 4 * lane + 256 * i + e;
-            grp[i][e] = c < E ? c / cpg : 0;
-        }
+    focal_lane_groups(lane, E, grp);
     const int r_end = min(a.T, (chunk + 1) * FH_ROWS);
     for (int r = chunk * FH_ROWS + wave; r < r_end; r += 4) {
         const int64_t row = (int64_t)v * a.T + r;
         const float* xr = a.x + row * a.ldx;
         Row4 h[2];
-        // relu(GroupNorm(x)) of both towers on load (columns past E stay 0)
+        // relu(GroupNorm(x)) of both towers on load (focal_row.h)
 #pragma unroll
-        for (int hb = 0; hb < 2; ++hb) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int c = 4 * lane + 256 * i;
-                if (c < E) {
-                    const f32x4 xv = *reinterpret_cast<const f32x4*>(xr + hb * E + c);
-                    const f32x4 g = *reinterpret_cast<const f32x4*>(a.gamma + hb * E + c), b = *reinterpret_cast<const f32x4*>(a.beta + hb * E + c);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float* st = s_st + (hb * 32 + grp[i][e]) * 2;
-                        h[hb].v[i][e] = fmaxf((xv[e] - st[0]) * st[1] * g[e] + b[e], 0.f);
-                    }
-                } else {
-                    h[hb].v[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-                }
-            }
-        }
-        auto dot = [&](const Row4& u, const float* w) {                          // every lane returns the whole row's u . w
-            float p = 0.f;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int col = 4 * lane + 256 * i;
-                if (col < E) {
-                    const f32x4 wv = *reinterpret_cast<const f32x4*>(w + col);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) p = fmaf(u.v[i][e], wv[e], p);
-                }
-            }
-            return wave_sum(p);
-        };
+        for (int hb = 0; hb < 2; ++hb) focal_load_tower(h[hb], xr + hb * E, a.gamma + hb * E, a.beta + hb * E, s_st + hb * 64, grp, lane, E);
+        auto dot = [&](const Row4& u, const float* w) { return focal_dot(u, w, lane, E); };
         // cls | centerness from the class half; lane n keeps class n, every lane the running maximum (cls_logits.topk(1), :178)
-        float mine = 0.f, best = -INFINITY;
-        for (int n = 0; n < NC; ++n) {
-            const float p = dot(h[0], s_w + n * E) + s_b[n];
-            if (lane == n) mine = p;
-            best = fmaxf(best, p);
-        }
-        const float ctr = dot(h[0], s_w + NC * E) + s_b[NC];
+        float mine, best;
+        const float ctr = focal_class_logits(h[0], s_w, s_b, NC, lane, E, mine, best);
         // ltrb | center2d from the box half
         float o[6];
 #pragma unroll
@@ -165,7 +117,7 @@ __global__ __launch_bounds__(256) void focal_heads_kernel(const FocalArgs a) {
         const float s0 = __shfl(sg, 0), s1 = __shfl(sg, 1), s2 = __shfl(sg, 2), s3 = __shfl(sg, 3);
         if (lane < NC) a.cls[row * a.ldc + lane] = mine;
         if (lane == 4 || lane == 5) a.ctr2d[row * 2 + lane - 4] = sg;
-        const float wgt = __fmul_rn(__shfl(sg, 6), __shfl(sg, 7));
+        const float wgt = focal_sample_weight(__shfl(sg, 6), __shfl(sg, 7));
         if (lane == 0) {
             // apply_ltrb (misc.py:26-43), then mmdet's bbox_xyxy_to_cxcywh: (x1 + x2) / 2, (y1 + y2) / 2, x2 - x1, y2 - y1
             const float x1 = clamp01(loc[0] - s0), y1 = clamp01(loc[1] - s1), x2 = clamp01(loc[0] + s2), y2 = clamp01(loc[1] + s3);

@@ -12,10 +12,16 @@ The head then runs on those rows (``forward(..., img_feats_rows=True)``): the tr
 bit of the frame are the chain's.
 
 Differences to the reference, by design:
-* inference only: training mode, ``forward_train``, ``forward(return_loss=True)``, ``aux_2d_only=False`` and ``token_select_vis=True`` raise
-  ``NotImplementedError``; ``use_grid_mask`` is accepted (GridMask is the identity outside training, ``grid_mask.py:85``); ``test_time_print`` is accepted and ignored;
-* ``img_roi_head=dict(type='FocalHead', ...)`` is accepted and nothing is built from it: with ``aux_2d_only=True`` the reference returns ``topk_indexes=None`` at
-  eval without calling it (:319-320).  A checkpoint's ``img_roi_head.*`` keys are dropped from the unexpected keys of ``load_state_dict``; nothing else is forgiven;
+* inference only: training mode, ``forward_train``, ``forward(return_loss=True)`` and ``token_select_vis=True`` raise ``NotImplementedError``;
+  ``use_grid_mask`` is accepted (GridMask is the identity outside training, ``grid_mask.py:85``); ``test_time_print`` is accepted and ignored;
+* with ``aux_2d_only=True`` (the default) ``img_roi_head=dict(type='FocalHead', ...)`` is accepted and nothing is built from it: the reference returns
+  ``topk_indexes=None`` at eval without calling it (:319-320).  A checkpoint's ``img_roi_head.*`` keys are then dropped from the unexpected keys of
+  ``load_state_dict``; nothing else is forgiven;
+* with ``aux_2d_only=False`` the block builds ``self.img_roi_head`` (:class:`toc3d_amd.FocalHead`, its sixteen tensors in the state dict and loaded strictly) and
+  the head with ``token_sampling=True``: every frame FocalHead ranks the tokens and the head's token side and cross-attention run on the
+  ``int(N*h*w * infer_ratio)`` best of each sample (:521-541).  ``simple_test_pts`` reads ``topk_indexes`` alone (:524-525), so it takes FocalHead's
+  selection-only frame (``select_rows`` on the neck's rows, ``select`` on a foreign tensor): the class tower only, the bits of the full forward's list.
+  ``forward_roi_head`` stays the reference's method and returns the full dict.  ``location`` (:311-316) is built once per shape and kept as derived state;
 * the ``pts_*`` parts and ``img_rpn_head`` are accepted as ``None`` only; backbones and necks other than this package's are refused at construction;
 * ``prev_exists`` reaches the backbone as the Python bool the scene-token comparison already is: no host synchronisation;
 * ``extract_img_feat(img)`` does not squeeze the caller's ``img`` in place (:102 does);
@@ -33,6 +39,7 @@ import torch.nn as nn
 from . import plan as _plan
 from . import registry
 from .backbone import EVA_ViT, ToC3DEVAViT
+from .focal_head import FocalHead
 from .head import StreamPETRHead
 from .neck import CPFPN
 
@@ -65,8 +72,6 @@ class Petr3D(_plan.DerivedState, nn.Module):
         present = [k for k in _ABSENT if given[k] is not None]
         if present:
             raise NotImplementedError(f"{_NAME}: {', '.join(present)} not implemented: the camera-only detector of the shipped configs passes None")
-        if not aux_2d_only:
-            raise NotImplementedError(f"{_NAME}: aux_2d_only=False (token selection by img_roi_head at eval, petr3d.py:319-323) is not implemented")
         if token_select_vis:
             raise NotImplementedError(f"{_NAME}: token_select_vis=True (petr3d.py:562-579) is not implemented")
         if position_level != 0:
@@ -74,10 +79,17 @@ class Petr3D(_plan.DerivedState, nn.Module):
         if not all(isinstance(c, dict) for c in (img_backbone, img_neck, pts_bbox_head)):
             raise ValueError(f"{_NAME}: needs img_backbone=dict(...), img_neck=dict(...) and pts_bbox_head=dict(...)")
         if img_roi_head is not None and not (isinstance(img_roi_head, dict) and img_roi_head.get("type") == "FocalHead"):
-            raise NotImplementedError(f"{_NAME}: img_roi_head is accepted as dict(type='FocalHead', ...) or None only (nothing is built from it)")
+            raise NotImplementedError(f"{_NAME}: img_roi_head is accepted as dict(type='FocalHead', ...) or None only")
         kw = {} if precision is None else dict(precision=precision)
+        # aux_2d_only=False: FocalHead selects the head's tokens at eval (:319-323).  Built first: what it refuses about its own config is the first thing said
+        # (with aux_2d_only=True, or without the config block, nothing is built and the reference calls nothing: :319)
+        roi = registry.build_head(img_roi_head, **kw) if not aux_2d_only and img_roi_head is not None else None
+        if roi is not None and not isinstance(roi, FocalHead):
+            raise NotImplementedError(f"{_NAME}: img_roi_head builds this package's FocalHead only, got {type(roi).__name__}")
         head_cfg = dict(pts_bbox_head)                                      # MVXTwoStageDetector.__init__: the head gets the pts slice of train_cfg / test_cfg
         head_cfg.update(train_cfg=train_cfg.get("pts") if train_cfg else None, test_cfg=test_cfg.get("pts") if test_cfg else None)
+        if roi is not None:
+            head_cfg["token_sampling"] = True                              # the head takes the roi head's topk_indexes
         self.img_backbone = registry.build_backbone(img_backbone, **kw)
         self.img_neck = registry.build_neck(img_neck, **kw)
         self.pts_bbox_head = registry.build_head(head_cfg, **kw)
@@ -86,6 +98,10 @@ class Petr3D(_plan.DerivedState, nn.Module):
                                       f"{type(self.img_backbone).__name__}, {type(self.img_neck).__name__}, {type(self.pts_bbox_head).__name__}")
         if self.img_neck.out_channels != self.pts_bbox_head.in_channels:
             raise ValueError(f"{_NAME}: the neck's out_channels {self.img_neck.out_channels} != the head's in_channels {self.pts_bbox_head.in_channels}")
+        if roi is not None:
+            if roi.in_channels != self.img_neck.out_channels:
+                raise ValueError(f"{_NAME}: the neck's out_channels {self.img_neck.out_channels} != img_roi_head's in_channels {roi.in_channels}")
+            self.img_roi_head = roi
         self.precision = precision
         self.train_cfg, self.test_cfg = train_cfg, test_cfg
         self.use_grid_mask = use_grid_mask
@@ -97,10 +113,15 @@ class Petr3D(_plan.DerivedState, nn.Module):
         self._drop_derived()
         self.eval()
 
-    with_img_neck, with_img_roi_head, with_pts_bbox = True, False, True
+    with_img_neck, with_pts_bbox = True, True
 
-    # ---- derived state: the parts keep their own; the detector's is the scene it is in and the tensor whose rows sit in the head's workspace --------------
-    _DERIVED = dict(prev_scene_token=None, prev_scene_tokens=None, _fanned=None, last_frame=None)
+    @property
+    def with_img_roi_head(self):
+        return getattr(self, "img_roi_head", None) is not None
+
+    # ---- derived state: the parts keep their own; the detector's is the scene it is in, the tensor whose rows sit in the head's workspace and the roi head's
+    # location (key, tensor) ------------------------------------------------------------------------------------------------------------------------------
+    _DERIVED = dict(prev_scene_token=None, prev_scene_tokens=None, _fanned=None, last_frame=None, _location=None)
 
     def train(self, mode=True):
         if mode:
@@ -113,10 +134,15 @@ class Petr3D(_plan.DerivedState, nn.Module):
         self.pts_bbox_head.init_weights()
         for part in (self.img_backbone, self.img_neck):
             part._drop_derived()
+        if self.with_img_roi_head:
+            self.img_roi_head.init_weights()
         self._drop_derived()
 
     def load_state_dict(self, state_dict, strict=True, **kw):
-        """``strict=True`` forgives exactly the ``img_roi_head.*`` keys of a shipped checkpoint: nothing at eval reads them (module docstring)."""
+        """Without an ``img_roi_head`` module (``aux_2d_only=True``) ``strict=True`` forgives exactly the ``img_roi_head.*`` keys of a shipped checkpoint: nothing
+        at eval reads them (module docstring).  With one they load like every other key: a checkpoint without them is a "Missing key" error."""
+        if self.with_img_roi_head:
+            return super().load_state_dict(state_dict, strict=strict, **kw)
         kept = type(state_dict)((k, v) for k, v in state_dict.items() if not k.startswith("img_roi_head."))
         if hasattr(state_dict, "_metadata"):
             kept._metadata = state_dict._metadata
@@ -175,15 +201,76 @@ class Petr3D(_plan.DerivedState, nn.Module):
         location = torch.stack((shift_x.reshape(-1), shift_y.reshape(-1)), dim=1).reshape(h, w, 2)
         return location[None].repeat(bs * n, 1, 1, 1)
 
+    @torch.no_grad()
     def forward_roi_head(self, location, **data):
-        return {"topk_indexes": None}                                                                                                    # :319-320 (aux_2d_only at eval)
+        """:318-323: ``{'topk_indexes': None}`` with ``aux_2d_only`` or without an ``img_roi_head``; otherwise FocalHead's full dict -- from the neck's rows
+        (``forward_rows``) when ``data['img_feats']`` is the tensor :meth:`extract_img_feat` returned last, from the tensor (``forward``) otherwise.
+        (:meth:`simple_test_pts` does not call this: it reads ``topk_indexes`` alone and takes FocalHead's selection-only path.)"""
+        if self.aux_2d_only or not self.with_img_roi_head:
+            return {"topk_indexes": None}                                                                                                # :319-320
+        x = data["img_feats"]
+        rows = self._roi_rows(x) if self._is_fanned(x) else None
+        if rows is None:
+            return self.img_roi_head(location, **data)
+        return self.img_roi_head.forward_rows(location, rows[0], rows[1], x.shape[0], x.shape[1], x.shape[3], x.shape[4])
+
+    # ---- token selection (aux_2d_only=False) ---------------------------------------------------------------------------------------------------------------
+    def _is_fanned(self, x):
+        """``x`` is the tensor :meth:`extract_img_feat` returned last, and its rows are still the head's (new weights or a move of the head alone give it a
+        new workspace)."""
+        fanned = self._fanned
+        return bool(fanned is not None and x is fanned[0]
+                    and self.pts_bbox_head.img_feats_rows_buffer(x.shape[0], x.shape[1], x.shape[3], x.shape[4], x.device)[0] is fanned[1])
+
+    def _roi_rows(self, x):
+        """``(rows, ld)`` of the fanned frame as FocalHead's conv reads them: on ``"bf16"`` the bf16 rows the fan-out wrote into the head's workspace, otherwise
+        the neck's own plain-f32 conv rows (the head's f32 rows may be (hi, lo) planes).  None where neither fits (``ld != in_channels``)."""
+        B, N, _, h, w = x.shape
+        roi = self.img_roi_head
+        if roi.precision == "bf16":
+            rows, ld = self._fanned[1], self._fanned[1].shape[1]
+        else:
+            rows, ld = self.img_neck.conv_rows(B * N, h, w)
+        return (rows, ld) if ld == roi.in_channels and rows.dtype == (torch.bfloat16 if roi.precision == "bf16" else torch.float32) else None
+
+    def _roi_location(self, img_metas, x):
+        """:meth:`prepare_location`, once per (pad_shape, B, N, h, w, device): derived state, not rebuilt every frame."""
+        key = (tuple(img_metas[0]["pad_shape"][0][:2]), x.shape[0], x.shape[1], x.shape[3], x.shape[4], x.device)
+        if self._location is None or self._location[0] != key:
+            self._location = (key, self.prepare_location(img_metas, img_feats=x))
+        return self._location[1]
+
+    def _check_keeps_tokens(self, img):
+        """The ``ValueError`` of a selection that keeps no token, from the image's shape: before the frame's first launch.  (The uint8 form, whose padded size
+        the backbone decides, is caught by :meth:`_select_tokens`, in front of the roi head's launches.)"""
+        if self.aux_2d_only or not self.with_img_roi_head or not isinstance(img, torch.Tensor) or img.dim() < 5 or img.dtype == torch.uint8:
+            return
+        n = img.shape[-4] * (img.shape[-2] // self.stride) * (img.shape[-1] // self.stride)
+        if int(n * self.img_roi_head.infer_ratio) == 0:
+            raise ValueError(f"{_NAME}: img_roi_head keeps int({n} tokens * infer_ratio {self.img_roi_head.infer_ratio}) = 0 tokens: the head cannot attend to none")
+
+    def _select_tokens(self, img_metas, data):
+        """``(location, topk_indexes)`` for the head: ``(None, None)`` on the ``aux_2d_only`` path (:319-320); otherwise FocalHead's ``topk_indexes`` (B, K, 1)
+        through its selection-only frame -- ``select_rows`` on the neck's rows of the fanned frame, ``select`` on any other tensor."""
+        if self.aux_2d_only or not self.with_img_roi_head:
+            return None, None
+        x, roi = data["img_feats"], self.img_roi_head
+        B, N, _, h, w = x.shape
+        if int(N * h * w * roi.infer_ratio) == 0:
+            raise ValueError(f"{_NAME}: img_roi_head keeps int({N * h * w} tokens * infer_ratio {roi.infer_ratio}) = 0 tokens: the head cannot attend to none")
+        location = self._roi_location(img_metas, x)
+        rows = self._roi_rows(x) if self._is_fanned(x) else None
+        if rows is None:
+            out = roi.select(location, img_feats=x)
+        else:
+            out = roi.select_rows(location, rows[0], rows[1], B, N, h, w)
+        return location, out["topk_indexes"]
 
     @torch.no_grad()
     def simple_test_pts(self, img_metas, **data):
         """:521-541.  The head runs on the rows the neck left in its workspace when ``data['img_feats']`` is the tensor :meth:`extract_img_feat` returned last;
         any other tensor goes through the head's own transpose."""
-        location = None                                 # (prepare_location's tensor is what the head ignores: not built every frame)
-        topk_indexes = self.forward_roi_head(location, **data)["topk_indexes"]
+        location, topk_indexes = self._select_tokens(img_metas, data)      # (aux_2d_only: None, None -- the location is what the head ignores, never built)
         if img_metas[0]["scene_token"] != self.prev_scene_token:
             self.prev_scene_token = img_metas[0]["scene_token"]
             data["prev_exists"] = data["img"].new_zeros(1)
@@ -194,11 +281,8 @@ class Petr3D(_plan.DerivedState, nn.Module):
 
     def _pts_results(self, img_metas, location, topk_indexes, data):
         """The head on ``data`` (``prev_exists`` decided by the caller) and the decoded lists, one per sample."""
-        fanned, self._fanned = self._fanned, None
-        if fanned is not None:                         # ... and the rows are still the head's (new weights or a move of the head alone give it a new workspace)
-            x = data["img_feats"]
-            fanned = x is fanned[0] and self.pts_bbox_head.img_feats_rows_buffer(x.shape[0], x.shape[1], x.shape[3], x.shape[4], x.device)[0] is fanned[1]
-        fanned = bool(fanned)
+        fanned = self._is_fanned(data["img_feats"])
+        self._fanned = None
         outs = self.pts_bbox_head(location, img_metas, topk_indexes, img_feats_rows=fanned, **data)
         bbox_list = self.pts_bbox_head.get_bboxes(outs, img_metas)
         return [bbox3d2result(bboxes, scores, labels) for bboxes, scores, labels in bbox_list]
@@ -207,6 +291,7 @@ class Petr3D(_plan.DerivedState, nn.Module):
     def simple_test(self, img_metas, gt_bboxes=None, centers2d=None, depths=None, gumbel_noise=None, **data):
         """:543-594: ``[dict(pts_bbox=dict(boxes_3d, scores_3d, labels_3d))]``.  What :meth:`extract_img_feat` returned for the frame -- the reference hands it to
         ``token_selection_vis`` (:562-579) -- stays readable as ``self.last_frame`` until the next one."""
+        self._check_keeps_tokens(data["img"])
         prev_exists = img_metas[0]["scene_token"] == self.prev_scene_token                                                               # :546-549, as the bool it is
         img_feats, token_masks, _, keep_idxes, drop_idxes = self.extract_img_feat(data["img"], 1, gt_bboxes=gt_bboxes, centers2d=centers2d, depths=depths,
                                                                                   prev_exists=prev_exists, ego_pose_inv=data["ego_pose_inv"], gumbel_noise=gumbel_noise)
@@ -230,6 +315,7 @@ class Petr3D(_plan.DerivedState, nn.Module):
         whose zeros make ``pre_update_memory`` clear exactly those samples of the bank.  ``reset_memory()`` is called only when every stream is new -- and
         when B differs from the previous step's: a change of B restarts EVERY stream (the bank is allocated per batch size; stream b of the new step is not
         known to be stream b of the old one).  Stream b is what a B = 1 detector stepped through :meth:`simple_test` computes for it."""
+        self._check_keeps_tokens(data["img"])
         B = len(img_metas)
         tokens = [m["scene_token"] for m in img_metas]
         before = self.prev_scene_tokens
@@ -245,7 +331,8 @@ class Petr3D(_plan.DerivedState, nn.Module):
         data["img_feats"] = img_feats
         self.last_frame = dict(img_feats=img_feats, token_masks=token_masks, keep_idxes=keep_idxes, drop_idxes=drop_idxes)
         data["prev_exists"] = torch.tensor([1.0 if p else 0.0 for p in prev], dtype=torch.float32, device=data["img"].device)
-        return [dict(pts_bbox=r) for r in self._pts_results(img_metas, None, None, data)]
+        location, topk_indexes = self._select_tokens(img_metas, data)
+        return [dict(pts_bbox=r) for r in self._pts_results(img_metas, location, topk_indexes, data)]
 
     def reset_streams(self, indices=None):
         """Forget the scene tokens of the streams ``indices`` (default: all): their next step starts a scene whatever token it carries."""

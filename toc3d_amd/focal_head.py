@@ -11,7 +11,10 @@ StreamPETR / ToC3D checkpoint load strictly.
 Per frame (``csrc/focal_head.hip``, ``include/toc3d_focal.h``), four launches: ONE implicit-GEMM 3x3 conv for both towers (weights stacked along Cout, the
 existing ``EPI_CONV3X3`` path) into f32 rows ``[M, 2 E]`` -> ``toc3d_focal_gn_stats`` -> ``toc3d_focal_heads`` -> ``toc3d_rank_desc`` on the sampling weight
 (descending, ties to the lower index -- ``torch.topk`` leaves the tie order open; stable-descending is the rule of this package).  ``forward`` puts
-``toc3d_nchw_to_rows`` in front; ``forward_rows`` starts from token rows.  The sequence is recorded once per shape into a launch plan and replayed with one C
+``toc3d_nchw_to_rows`` in front; ``forward_rows`` starts from token rows.  ``select_rows`` / ``select`` are the selection-only frame a detector needs
+(``Petr3D.simple_test_pts`` reads ``topk_indexes`` and nothing else, ``detectors/petr3d.py:524-525``, and the class tower alone decides it): the conv of
+``shared_cls.0`` alone -> ``toc3d_focal_gn_stats`` on one tower -> ``toc3d_focal_sample_weight`` (``csrc/focal_select.hip``, ``include/toc3d_select.h``) ->
+``toc3d_rank_desc``, with the bits of the full frame's ``topk_indexes`` and ``sample_weight``.  The sequence is recorded once per shape into a launch plan and replayed with one C
 call per frame.  ``precision`` decides the conv's products (``"fp32x3"``: bf16 x 3 on f32 rows; ``"bf16"``); everything behind the conv is f32 in both.
 
 Inference only: losses, assigner and sampler are accepted and nothing is built from them.  No CPU path.
@@ -98,6 +101,17 @@ class FocalHead(StagedModule):
         return dict(x=z(V, C, h, w), rows=z(M, C, d=self._packed["tdt"]), loc=z(M, 2), h=z(M, 2 * E), stats=z(V, 64, 2), cls=z(M, self.num_classes),
                     box=z(M, 4), ctr2d=z(M, 2), ctrness=z(M), weight=z(B, N * T), order=z(B, N * T, d=torch.int64))
 
+    def _select_workspace(self, W, key, dev):
+        """The selection-only frame's own buffers, beside the full frame's in ``W`` (built when the first selection of the shape runs)."""
+        S = W.get("select")
+        if S is None:
+            B, N, h, w = key
+            V, T, f = B * N, h * w, torch.float32
+            z = lambda *s, d=f: torch.zeros(*s, dtype=d, device=dev)
+            narrow = gemm.small_m_variant(V * T, 2 * self.embed_dims, 9 * self.in_channels, False) != 0          # (_select_launches: else the conv runs at full width into W["h"])
+            S = W["select"] = dict(hc=z(V * T, self.embed_dims) if narrow else None, stats=z(V, 32, 2), weight=z(B, N * T), order=z(B, N * T, d=torch.int64))
+        return S
+
     def _launches(self, key, W, rows, K):
         """``[(name, launch), ...]``: the four launches of one frame on the token rows ``rows`` [M, in_channels] (act dtype) and the staged ``location``
         (three when ``K == 0``: nothing is ranked)."""
@@ -115,8 +129,28 @@ class FocalHead(StagedModule):
         rank = lambda: lib.call("toc3d_rank_desc", W["weight"], B, N * T, W["order"], s())
         return [("conv3x3", conv), ("gn_stats", stats), ("heads", heads)] + ([("rank_desc", rank)] if K > 0 else [])
 
-    def _frame(self, key, W, rows, K):
-        for _, launch in self._launches(key, W, rows, K):
+    def _select_launches(self, key, W, rows, K):
+        """``[(name, launch), ...]`` of the selection-only frame: the class tower's half of :meth:`_launches`, into the buffers of :meth:`_select_workspace`."""
+        P, S, (B, N, h, w) = self._packed, W["select"], key
+        V, T, C, E = B * N, h * w, self.in_channels, self.embed_dims
+        M = V * T
+        s = lib.stream_ptr
+        # The tile of the FULL-width conv: all unsplit tiles accumulate K in one order, but a narrower N must not pick another tile family on its own.  Where the
+        # full-width shape leaves the tile to the library's heuristic (0: M >= 16k rows), that heuristic may depend on N: the conv then runs at full width into
+        # the full frame's buffer, and the two launches behind it read its first E columns (ldx = 2 E) -- the bits are the full frame's by construction.
+        variant = gemm.small_m_variant(M, 2 * E, 9 * C, False)
+        x, ldx, n = (S["hc"], E, E) if variant != 0 else (W["h"], 2 * E, 2 * E)
+
+        def conv():                                        # shared_cls.0 alone: its rows come first in the packed stack
+            gemm.linear(self, lib.EPI_CONV3X3, rows, P["conv"][0], P["conv"][1], x, M, n, 9 * C, lda=C, ldo=ldx, conv=(P["zeros"], h, w), variant=variant)
+        stats = lambda: lib.call("toc3d_focal_gn_stats", lib.F32, x, ldx, V, T, E, 1, P["eps"], S["stats"], s())
+        weight = lambda: lib.call("toc3d_focal_sample_weight", lib.F32, x, ldx, S["stats"], P["gamma"], P["beta"], P["wc"], P["bc"], V, T, E, self.num_classes,
+                                  S["weight"], s())
+        rank = lambda: lib.call("toc3d_rank_desc", S["weight"], B, N * T, S["order"], s())
+        return [("conv3x3", conv), ("gn_stats", stats), ("sample_weight", weight)] + ([("rank_desc", rank)] if K > 0 else [])
+
+    def _frame(self, key, W, rows, K, select=False):
+        for _, launch in (self._select_launches if select else self._launches)(key, W, rows, K):
             launch()
 
     def _check(self, location, B, N, h, w):
@@ -135,6 +169,12 @@ class FocalHead(StagedModule):
                     topk_indexes=W["order"][:, :K].clone().view(B, K, 1) if K > 0 else torch.empty(B, 0, 1, dtype=torch.int64, device=W["order"].device),
                     sample_weight=W["weight"].clone().view(B, N * T, 1))
 
+    def _select_outputs(self, W, key, K):
+        B, N, h, w = key
+        S = W["select"]
+        return dict(topk_indexes=S["order"][:, :K].clone().view(B, K, 1) if K > 0 else torch.empty(B, 0, 1, dtype=torch.int64, device=S["order"].device),
+                    sample_weight=S["weight"].clone().view(B, N * h * w, 1))
+
     @torch.no_grad()
     def forward(self, location, **data):
         """``data['img_feats']`` (B, N, C, h, w) f32 on the device (neck level 0), ``location`` (B*N, h, w, 2) normalised pixel centres
@@ -142,6 +182,16 @@ class FocalHead(StagedModule):
         cxcywh in [0, 1], ``pred_centers2d`` (B*N, h*w, 2), ``centerness`` (B*N, h*w, 1) logits, ``topk_indexes`` (B, K, 1) int64 with
         ``K = int(N*h*w * infer_ratio)`` -- plus ``sample_weight`` (B, N*h*w, 1), the tensor that is ranked (:180; the reference computes it and does not return
         it).  All freshly allocated: none aliases a workspace."""
+        return self._forward(location, data, False)
+
+    @torch.no_grad()
+    def select(self, location, **data):
+        """:meth:`forward` for a caller that reads ``topk_indexes`` alone: ``dict(topk_indexes (B, K, 1) int64, sample_weight (B, N*h*w, 1))``, bit for bit
+        :meth:`forward`'s, from the class tower only (module docstring).  Both freshly allocated."""
+        return self._forward(location, data, True)
+
+    def _forward(self, location, data, select):
+        """:meth:`forward` (``select=False``) or :meth:`select`: one staging, one plan per kind."""
         src = data["img_feats"]
         require_cuda(_NAME, src, location, on_device=False)
         if src.dim() != 5 or src.shape[2] != self.in_channels:
@@ -154,13 +204,15 @@ class FocalHead(StagedModule):
         with torch.cuda.device(dev):
             W = self._workspace(key, dev)
             c = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
-            lib.copy_segments([(W["x"], c(src)), (W["loc"], c(location))], lib.stream_ptr())
+            lib.copy_segments([(W["x"], c(src))] + ([] if select else [(W["loc"], c(location))]), lib.stream_ptr())
+            if select:
+                self._select_workspace(W, key, dev)
 
             def launches():
                 lib.call("toc3d_nchw_to_rows", self._packed["dt"], W["x"], W["rows"], C, B * N, C, h * w, lib.stream_ptr())
-                self._frame(key, W, W["rows"], K)
-            self._run((key, K), launches)
-            return self._outputs(W, key, K)
+                self._frame(key, W, W["rows"], K, select)
+            self._run(("select", key, K) if select else (key, K), launches)
+            return self._select_outputs(W, key, K) if select else self._outputs(W, key, K)
 
     @torch.no_grad()
     def forward_rows(self, location, rows, ld, B, N, h, w):
@@ -168,6 +220,16 @@ class FocalHead(StagedModule):
         from them, so ``ld == in_channels``), row (b, n, y, x) -- what ``toc3d_nchw_to_rows`` makes of ``img_feats``, and what the neck's conv leaves before its
         transpose.  No NCHW tensor is read; every other launch, and every bit, is :meth:`forward`'s.  A recorded plan names ``rows``: the buffer lives as long as
         the plan does."""
+        return self._forward_rows(location, rows, ld, B, N, h, w, False)
+
+    @torch.no_grad()
+    def select_rows(self, location, rows, ld, B, N, h, w):
+        """:meth:`select` on token rows, as :meth:`forward_rows` is :meth:`forward` on them: the same ``rows``, the same refusals, four launches (three when
+        ``K == 0``), recorded under a plan key of its own within the same ``MAX_ROW_STATES``."""
+        return self._forward_rows(location, rows, ld, B, N, h, w, True)
+
+    def _forward_rows(self, location, rows, ld, B, N, h, w, select):
+        """:meth:`forward_rows` (``select=False``) or :meth:`select_rows` (which stages no ``location``: the class tower does not read it)."""
         B, N, h, w, ld = (int(v) for v in (B, N, h, w, ld))
         require_cuda(_NAME, rows, location, on_device=False)
         self._check(location, B, N, h, w)
@@ -178,8 +240,11 @@ class FocalHead(StagedModule):
             if rows.dim() != 2 or tuple(rows.shape) != (B * N * h * w, ld) or ld != self.in_channels or not rows.is_contiguous() or rows.dtype != self._packed["tdt"]:
                 raise ValueError(f"{_NAME}: rows {tuple(rows.shape)} {rows.dtype} must be contiguous [{B * N * h * w}, {self.in_channels}] {self._packed['tdt']}")
             K = int(N * h * w * self.infer_ratio)
-            lib.copy_segments([(W["loc"], location.detach().to(device=dev, dtype=torch.float32).contiguous())], lib.stream_ptr())
-            skey = ("rows", key, K, rows.data_ptr())
-            self._run(skey, lambda: self._frame(key, W, rows, K), max_states=MAX_ROW_STATES)
+            if select:
+                self._select_workspace(W, key, dev)
+            else:
+                lib.copy_segments([(W["loc"], location.detach().to(device=dev, dtype=torch.float32).contiguous())], lib.stream_ptr())
+            skey = ("select_rows" if select else "rows", key, K, rows.data_ptr())
+            self._run(skey, lambda: self._frame(key, W, rows, K, select), max_states=MAX_ROW_STATES)
             self._states[skey]["rows"] = rows
-            return self._outputs(W, key, K)
+            return self._select_outputs(W, key, K) if select else self._outputs(W, key, K)

@@ -165,6 +165,12 @@ _SAMPLED_SIGS = {
     "toc3d_head_frustum_inputs_sampled": "ippppplllllllllplplpp",
     "toc3d_gather_token_rows": "iplpllllplp",
 }
+# include/toc3d_select.h (FocalHead's selection-only path, toc3d_amd.FocalHead.select_rows): a side header likewise
+SELECT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "toc3d_select.h")
+SELECT_ABI = 1                  # == TOC3D_SELECT_ABI
+_SELECT_SIGS = {
+    "toc3d_focal_sample_weight": "iplpppppllllpp",
+}
 
 _lib = None
 
@@ -285,6 +291,23 @@ def _bind_sampled(lib):
     lib._toc3d_sampled_bound = True
 
 
+def _bind_select(lib):
+    """The entry point of include/toc3d_select.h, bound when it is first called."""
+    try:
+        lib.toc3d_select_abi.restype = _I
+        abi = lib.toc3d_select_abi()
+        fns = {name: getattr(lib, name) for name in _SELECT_SIGS}
+    except AttributeError:
+        abi, fns = None, {}
+    if abi != SELECT_ABI:
+        raise RuntimeError(f"{LIB_PATH} reports select ABI {abi}, this package binds {SELECT_ABI} (include/toc3d_select.h): "
+                           "rebuild the library (`make -C toc3d_amd/csrc`)")
+    for name, fn in fns.items():
+        fn.restype = _I
+        fn.argtypes = [_CT[c] for c in _SELECT_SIGS[name]]
+    lib._toc3d_select_bound = True
+
+
 def call(name: str, *args):
     """Invoke a C-ABI entry point; tensors are passed as device pointers; raises on a non-zero return."""
     lib = load()
@@ -294,6 +317,8 @@ def call(name: str, *args):
         _bind_focal(lib)
     if name in _SAMPLED_SIGS and not getattr(lib, "_toc3d_sampled_bound", False):
         _bind_sampled(lib)
+    if name in _SELECT_SIGS and not getattr(lib, "_toc3d_select_bound", False):
+        _bind_select(lib)
     rc = getattr(lib, name)(*[_conv(a) for a in args])
     if rc != 0:
         raise RuntimeError(f"{name} failed ({rc}): {lib.toc3d_last_error().decode()}")

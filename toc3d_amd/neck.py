@@ -81,6 +81,14 @@ class CPFPN(DerivedState, nn.Module):
             raise ValueError("toc3d_amd.CPFPN.forward_fanout: rows must be a contiguous 2-D device tensor whose row length is ld_rows")
         return self._forward(inputs, (rows, int(ld_rows), int(dtype)))
 
+    def conv_rows(self, V, h, w):
+        """``(rows, ld)``: the level-0 conv's own output rows [V*h*w, out_channels], plain f32 on every precision, of the last forward at this shape -- what the
+        fan-out transposes.  A consumer that reads plain f32 token rows (``FocalHead`` on ``"fp32x3"``) takes them from here.  Valid until the next forward."""
+        ws = self._ws.get((V, h, w))
+        if ws is None:
+            raise RuntimeError(f"toc3d_amd.CPFPN.conv_rows: no forward has run at V, h, w = {V}, {h}, {w}")
+        return ws["o0"], ws["o0"].shape[1]
+
     def _forward(self, inputs, fan):
         assert len(inputs) == len(self.in_channels)
         feat = inputs[0]

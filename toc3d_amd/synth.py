@@ -644,6 +644,16 @@ DETECTOR_TINY = dict(backbone="toc3d_tiny", neck="tiny", hw=(320, 800), views=6,
                      head=dict(in_channels=32, num_query=72, memory_len=160, topk_proposals=64, num_propagated=24,
                                decoder=dict(embed_dims=256, num_heads=8, feedforward_channels=128, num_layers=2), max_num=30, post_center_range=None))
 DETECTOR_FULL = dict(backbone="toc3d_faster", neck="full", hw=(320, 800), views=6, frames=2, new_scene_at=None, head=HEAD_FULL)      # the shipped sizes (ToC3D_faster.py)
+# DETECTOR_TINY with token selection (aux_2d_only=False): the 64-channel tiny neck (FocalHead's conv reads whole 64-channel K-tiles), the head on 64 channels, and
+# a roi head that keeps 30 % of the tokens.  "roi": the FocalHead sizes that replace the shipped block's; sizes without the key build the block as shipped
+DETECTOR_TINY_ROI = dict(DETECTOR_TINY, neck="tiny64", head=dict(DETECTOR_TINY["head"], in_channels=64), roi=dict(num_classes=3, embed_dims=64, infer_ratio=0.3))
+# ... and the shipped sizes with the roi head's weights in the state dict (the block's own FocalHead: 10 classes, 256 channels)
+DETECTOR_FULL_ROI = dict(DETECTOR_FULL, roi=dict())
+
+
+def _neck_cfg(sizes):
+    from . import configs
+    return dict(full=configs.CPFPN_CFG, tiny=configs.CPFPN_TINY, tiny64=configs.CPFPN_TINY64)[sizes["neck"]]
 
 
 def detector_cfg(sizes: dict = None) -> dict:
@@ -653,13 +663,14 @@ def detector_cfg(sizes: dict = None) -> dict:
     sizes = DETECTOR_FULL if sizes is None else sizes
     pcr = list(PC_RANGE)
     backbone = dict(configs.get(sizes["backbone"]), token_selection_loss=dict(type="TokenSelectionLoss", semantic_loss=dict(type="GaussianFocalLoss", loss_weight=5.0)))
-    neck = dict(configs.CPFPN_CFG if sizes["neck"] == "full" else configs.CPFPN_TINY)
+    neck = dict(_neck_cfg(sizes))
     roi = dict(type="FocalHead", num_classes=10, in_channels=neck["out_channels"], loss_cls2d=dict(type="QualityFocalLoss", use_sigmoid=True, beta=2.0, loss_weight=2.0),
                loss_centerness=dict(type="GaussianFocalLoss", reduction="mean", loss_weight=1.0), loss_bbox2d=dict(type="L1Loss", loss_weight=5.0),
                loss_iou2d=dict(type="GIoULoss", loss_weight=2.0), loss_centers2d=dict(type="L1Loss", loss_weight=10.0),
                train_cfg=dict(assigner2d=dict(type="HungarianAssigner2D", cls_cost=dict(type="FocalLossCost", weight=2.0),
                                               reg_cost=dict(type="BBoxL1Cost", weight=5.0, box_format="xywh"), iou_cost=dict(type="IoUCost", iou_mode="giou", weight=2.0),
                                               centers2d_cost=dict(type="BBox3DL1Cost", weight=10.0))))
+    roi.update(sizes.get("roi", {}))
     train_cfg = dict(pts=dict(grid_size=[512, 512, 1], voxel_size=[0.2, 0.2, 8], point_cloud_range=pcr, out_size_factor=4,
                               assigner=dict(type="HungarianAssigner3D", cls_cost=dict(type="FocalLossCost", weight=2.0), reg_cost=dict(type="BBox3DL1Cost", weight=0.25),
                                             iou_cost=dict(type="IoUCost", weight=0.0), pc_range=pcr)))
@@ -669,13 +680,17 @@ def detector_cfg(sizes: dict = None) -> dict:
 
 def detector_state_dict(sizes: dict = None, seed: int = 0):
     """Seeded weights of the whole detector under the reference's names: ``img_backbone.*`` (``make_state_dict``), ``img_neck.*`` (``neck_state_dict``) and
-    ``pts_bbox_head.*`` (``head_state_dict``) -- the same tensors those helpers give the parts."""
+    ``pts_bbox_head.*`` (``head_state_dict``) -- the same tensors those helpers give the parts -- and, for sizes with a ``roi`` key only, the sixteen
+    ``img_roi_head.*`` tensors (``focal_head_state_dict`` at the config block's FocalHead sizes)."""
     from . import configs
     sizes = DETECTOR_FULL if sizes is None else sizes
     sd = OrderedDict()
     sd.update(("img_backbone." + k, v) for k, v in make_state_dict(configs.get(sizes["backbone"]), seed=seed).items())
-    sd.update(("img_neck." + k, v) for k, v in neck_state_dict(configs.CPFPN_CFG if sizes["neck"] == "full" else configs.CPFPN_TINY, seed=seed).items())
+    sd.update(("img_neck." + k, v) for k, v in neck_state_dict(_neck_cfg(sizes), seed=seed).items())
     sd.update(("pts_bbox_head." + k, v) for k, v in head_state_dict(sizes["head"], seed=seed).items())
+    if "roi" in sizes:
+        roi = dict(dict(in_channels=_neck_cfg(sizes)["out_channels"], num_classes=10, embed_dims=256), **sizes["roi"])
+        sd.update(("img_roi_head." + k, v) for k, v in focal_head_state_dict(roi, seed=seed).items())
     return sd
 
 

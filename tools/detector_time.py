@@ -16,6 +16,11 @@ and alternation scheme, written to profiles/detector_streams_time.json.  Per B: 
 forgotten with ``reset_streams([0])`` in front of every step, so it starts a scene while the others continue; the call is inside the bracket).  B = 1 goes through the
 unchanged ``simple_test`` -- the baseline, checked against profiles/detector_time.json within that file's own spread -- and also gives the first-frame step (a scene
 start every step) that the two-forward alternative to a mixed step would add to a steady one.  Peak device memory (``torch.cuda.max_memory_allocated``) per B.
+
+``--sampling``: instead, the detector with token selection (``aux_2d_only=False``: FocalHead's selection-only frame, the head on the ``infer_ratio`` = 0.5 best
+tokens, 3000 of 6000) against the full-token detector (``aux_2d_only=True``) with the same weights, in the same run: the continuation frame, same warm-up, median
+and alternation scheme, written to profiles/detector_sampled_time.json.  ``sampled_faster``: the sampled frame's median lies below the full-token one's by more
+than the larger of the two spreads; ``sampled_not_slower``: within the full-token form's own spread of it.  Reported either way.
 """
 import argparse
 import json
@@ -173,6 +178,52 @@ def run_streams(precision, counts, warmup, steps, repeats=3):
     return res
 
 
+def run_sampling(precision, warmup, steps, repeats=3):
+    sizes = dict(synth.DETECTOR_FULL, roi=dict(infer_ratio=0.5))
+    sd = synth.detector_state_dict(sizes)
+    frames = synth.detector_inputs(sizes)
+    metas = frames[0]["img_metas"]
+    data = [{k: v.to(DEV) for k, v in f["data"].items()} for f in frames]
+    dets, has_table = {}, True
+    for name, aux in (("full_tokens", True), ("sampled", False)):
+        det = toc3d_amd.build_detector(dict(synth.detector_cfg(sizes), aux_2d_only=aux), precision=precision)
+        det.load_state_dict(sd, strict=True)
+        det.to(DEV)
+        has_table = tuned(sizes, precision, det.img_backbone, det.img_neck) and has_table
+        for f in (0, 1):                                                   # scene start, then the continuation frame that is timed
+            det.simple_test(metas, **data[f])
+        dets[name] = det
+    legs = {name: (lambda det=det: det.simple_test(metas, **data[1])) for name, det in dets.items()}
+    runs = {name: [] for name in legs}
+    for _ in range(repeats):                                               # alternating: both forms see the same drift of the card
+        for name, fn in legs.items():
+            runs[name].append(timed(fn, warmup, steps)["median_ms"])
+    r = dict(tuned_table=bool(has_table), tokens=6000, kept_tokens=int(6000 * 0.5))
+    for name, ms in runs.items():
+        r[name] = dict(rounds_ms=ms, median_ms=median(ms), spread_ms=round(max(ms) - min(ms), 4))
+    f, s = r["full_tokens"], r["sampled"]
+    r["sampled_minus_full_ms"] = round(s["median_ms"] - f["median_ms"], 4)
+    r["sampled_faster"] = bool(s["median_ms"] + max(f["spread_ms"], s["spread_ms"]) < f["median_ms"])
+    r["sampled_not_slower"] = bool(s["median_ms"] <= f["median_ms"] + f["spread_ms"])
+    print(f"[{precision}] full tokens {f['median_ms']} ms (spread {f['spread_ms']}), sampled {s['median_ms']} ms (spread {s['spread_ms']})", file=sys.stderr, flush=True)
+    return r
+
+
+def main_sampling(a):
+    res = dict(tool="detector_time --sampling", device=torch.cuda.get_device_name(0), sizes=dict(backbone="toc3d_faster", image=[6, 320, 800], neck="CPFPN 1024 -> 256",
+                                                                                                   head={k: v for k, v in synth.HEAD_FULL.items() if k != "decoder"},
+                                                                                                   roi=dict(synth.FOCAL_HEAD_FULL)),
+               warmup=a.warmup, steps=a.steps, repeats=3)
+    for precision in a.precisions.split(","):
+        res[precision] = run_sampling(precision, a.warmup, a.steps)
+    line = json.dumps(res)
+    print(line)
+    out = a.out or os.path.join(ROOT, "profiles", "detector_sampled_time.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as fh:
+        fh.write(line + "\n")
+
+
 def main_streams(a):
     res = dict(tool="detector_time --streams", device=torch.cuda.get_device_name(0), sizes=dict(backbone="toc3d_faster", image=[6, 320, 800], neck="CPFPN 1024 -> 256",
                                                                                                   head={k: v for k, v in synth.HEAD_FULL.items() if k != "decoder"}),
@@ -200,9 +251,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--precisions", default="fp32x3,bf16")
-    ap.add_argument("--out", default=None, help="default: profiles/detector_time.json, or profiles/detector_streams_time.json with --streams")
+    ap.add_argument("--out", default=None, help="default: profiles/detector_time.json; profiles/detector_streams_time.json with --streams, profiles/detector_sampled_time.json with --sampling")
     ap.add_argument("--streams", type=int, nargs="+", default=None, help="camera streams per step to time through simple_test_streams, e.g. 1 2 4")
+    ap.add_argument("--sampling", action="store_true", help="time aux_2d_only=False at infer_ratio 0.5 against aux_2d_only=True (profiles/detector_sampled_time.json)")
     a = ap.parse_args()
+    if a.sampling:
+        return main_sampling(a)
     if a.streams:
         return main_streams(a)
     a.out = a.out or os.path.join(ROOT, "profiles", "detector_time.json")

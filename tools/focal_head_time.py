@@ -7,6 +7,13 @@ written to --out (default profiles/focal_head_time.json).
 
   python tools/focal_head_time.py                  # the timing
   python tools/focal_head_time.py --frames 20 --precision fp32x3     # just run frames (under `rocprofv3 --kernel-trace --stats -- python ...`)
+  python tools/focal_head_time.py --select         # select_rows against forward_rows -> profiles/focal_select_time.json
+
+``--select``: the selection-only frame (``FocalHead.select_rows``: the class tower's conv, one-branch statistics, ``toc3d_focal_sample_weight``, the ranking)
+against ``forward_rows`` of the same module on the same rows at ``infer_ratio`` 0.5, in both precisions: warm-up 50, the median of 200 legs, three repetitions
+alternating the two forms so both see the same drift of the card; per form the three medians, their median and their spread (max - min).
+``select_not_slower``: the selection's median lies within ``forward_rows``' own spread of it.  Then each form launch by launch (event-timed back to back, so a
+launch's figure holds its launch overhead).
 """
 import argparse
 import json
@@ -26,6 +33,47 @@ from tools.decoder_time import timed     # noqa: E402
 DEV = "cuda:0"
 
 
+def median(xs):
+    xs = sorted(xs)
+    return xs[len(xs) // 2]
+
+
+def run_select(a, module, inp, sizes, shape):
+    B, N, h, w, C = shape["B"], shape["N"], shape["h"], shape["w"], sizes["in_channels"]
+    key, K = (B, N, h, w), int(N * h * w * 0.5)
+    res = dict(tool="focal_head_time --select", device=torch.cuda.get_device_name(0), sizes=dict(sizes, infer_ratio=0.5), shape=shape, warmup=a.warmup, steps=a.steps,
+               repeats=3)
+    for precision in ("fp32x3", "bf16"):
+        m = module(precision, 0.5)
+        full = m(inp["location"], img_feats=inp["img_feats"])
+        rows = m._ws[key]["rows"].clone()
+        legs = dict(forward_rows=lambda: m.forward_rows(inp["location"], rows, C, B, N, h, w), select_rows=lambda: m.select_rows(inp["location"], rows, C, B, N, h, w))
+        got = legs["select_rows"]()
+        same = bool(torch.equal(got["topk_indexes"], full["topk_indexes"]) and torch.equal(got["sample_weight"], full["sample_weight"]))
+        runs = {name: [] for name in legs}
+        for _ in range(3):                                                 # alternating: both forms see the same drift of the card
+            for name, fn in legs.items():
+                runs[name].append(timed(fn, a.warmup, a.steps)["median_ms"])
+        r = dict(same_bits=same)
+        for name, ms in runs.items():
+            r[name] = dict(rounds_ms=ms, median_ms=median(ms), spread_ms=round(max(ms) - min(ms), 4))
+        f, s = r["forward_rows"], r["select_rows"]
+        r["select_minus_forward_ms"] = round(s["median_ms"] - f["median_ms"], 4)
+        r["select_not_slower"] = bool(s["median_ms"] <= f["median_ms"] + f["spread_ms"])
+        r["select_faster_beyond_spread"] = bool(s["median_ms"] + max(f["spread_ms"], s["spread_ms"]) < f["median_ms"])
+        me = module(precision, 0.5, "eager")
+        me(inp["location"], img_feats=inp["img_feats"])
+        me.select(inp["location"], img_feats=inp["img_feats"])
+        W = me._ws[key]
+        for form, launches in (("forward_rows", me._launches(key, W, W["rows"], K)), ("select_rows", me._select_launches(key, W, W["rows"], K))):
+            per = {name: timed(launch, a.warmup, a.steps) for name, launch in launches}
+            r[form + "_launches"] = per
+            r[form + "_launch_sum_ms"] = round(sum(v["median_ms"] for v in per.values()), 4)
+        res[precision] = r
+        print(f"[{precision}] forward_rows {f['median_ms']} ms (spread {f['spread_ms']}), select_rows {s['median_ms']} ms (spread {s['spread_ms']})", file=sys.stderr, flush=True)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--warmup", type=int, default=50)
@@ -33,8 +81,10 @@ def main():
     ap.add_argument("--frames", type=int, default=0, help="run this many forwards of --precision and exit (for a profiler)")
     ap.add_argument("--precision", default="fp32x3")
     ap.add_argument("--no-torch", action="store_true", help="skip the torch-eager control")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "focal_head_time.json"))
+    ap.add_argument("--select", action="store_true", help="time select_rows against forward_rows instead (default --out: profiles/focal_select_time.json)")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "focal_select_time.json" if a.select else "focal_head_time.json")
     sizes, shape = synth.FOCAL_HEAD_FULL, synth.FOCAL_HEAD_FULL_SHAPE
     B, N, h, w, C = shape["B"], shape["N"], shape["h"], shape["w"], sizes["in_channels"]
     sd = synth.focal_head_state_dict(sizes)
@@ -50,6 +100,14 @@ def main():
         for _ in range(a.frames):
             m(inp["location"], img_feats=inp["img_feats"])
         torch.cuda.synchronize()
+        return
+    if a.select:
+        res = run_select(a, module, inp, sizes, shape)
+        line = json.dumps(res)
+        print(line)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            fh.write(line + "\n")
         return
     res = dict(tool="focal_head_time", device=torch.cuda.get_device_name(0), sizes=sizes, shape=shape, warmup=a.warmup, steps=a.steps)
     for precision in ("fp32x3", "bf16"):
