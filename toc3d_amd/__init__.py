@@ -5,7 +5,7 @@ Importing the package registers ``ToC3DEVAViT``, ``EVA_ViT`` (BACKBONES), ``CPFP
 """
 from .backbone import EVA_ViT, ToC3DEVAViT, ToC3DViTReturnType
 from .neck import CPFPN
-from .preprocess import prepare_images
+from .preprocess import ResizeCropFlipRotImage, prepare_images, resample_tables
 from .memory import TemporalMemory
 from .head_tokens import HeadTokenEmbedding
 from .decoder import PETRTemporalTransformer
@@ -19,6 +19,6 @@ from .registry import (BACKBONES, BBOX_CODERS, DETECTORS, HEADS, NECKS, TRANSFOR
 
 register_all()
 
-__all__ = ["ToC3DEVAViT", "EVA_ViT", "CPFPN", "ToC3DViTReturnType", "BACKBONES", "NECKS", "build_backbone", "build_neck", "prepare_images", "TemporalMemory", "HeadTokenEmbedding",
+__all__ = ["ToC3DEVAViT", "EVA_ViT", "CPFPN", "ToC3DViTReturnType", "BACKBONES", "NECKS", "build_backbone", "build_neck", "prepare_images", "ResizeCropFlipRotImage", "resample_tables", "TemporalMemory", "HeadTokenEmbedding",
            "PETRTemporalTransformer", "TRANSFORMER", "build_transformer", "HeadOutputs", "HeadQueries", "NMSFreeCoder", "BBOX_CODERS", "build_bbox_coder",
            "StreamPETRHead", "FocalHead", "HEADS", "build_head", "Petr3D", "DETECTORS", "build_detector"]

@@ -171,6 +171,13 @@ SELECT_ABI = 1                  # == TOC3D_SELECT_ABI
 _SELECT_SIGS = {
     "toc3d_focal_sample_weight": "iplpppppllllpp",
 }
+# include/toc3d_ingest.h (camera ingest: Pillow's resize and crop of raw uint8 frames, toc3d_amd.ResizeCropFlipRotImage): a side header likewise
+INGEST_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "toc3d_ingest.h")
+INGEST_ABI = 1                  # == TOC3D_INGEST_ABI
+INGEST_TILE_W, INGEST_TILE_H, INGEST_LDS_ROWS, INGEST_MAX_KSIZE = 64, 32, 168, 32       # == TOC3D_INGEST_TILE_W, _TILE_H, _LDS_ROWS, _MAX_KSIZE
+_INGEST_SIGS = {
+    "toc3d_resize_crop_u8": "pllll" + "plll" + "ppl" + "ppl" + "l" + "p",
+}
 
 _lib = None
 
@@ -308,6 +315,23 @@ def _bind_select(lib):
     lib._toc3d_select_bound = True
 
 
+def _bind_ingest(lib):
+    """The entry point of include/toc3d_ingest.h, bound when it is first called."""
+    try:
+        lib.toc3d_ingest_abi.restype = _I
+        abi = lib.toc3d_ingest_abi()
+        fns = {name: getattr(lib, name) for name in _INGEST_SIGS}
+    except AttributeError:
+        abi, fns = None, {}
+    if abi != INGEST_ABI:
+        raise RuntimeError(f"{LIB_PATH} reports ingest ABI {abi}, this package binds {INGEST_ABI} (include/toc3d_ingest.h): "
+                           "rebuild the library (`make -C toc3d_amd/csrc`)")
+    for name, fn in fns.items():
+        fn.restype = _I
+        fn.argtypes = [_CT[c] for c in _INGEST_SIGS[name]]
+    lib._toc3d_ingest_bound = True
+
+
 def call(name: str, *args):
     """Invoke a C-ABI entry point; tensors are passed as device pointers; raises on a non-zero return."""
     lib = load()
@@ -319,6 +343,8 @@ def call(name: str, *args):
         _bind_sampled(lib)
     if name in _SELECT_SIGS and not getattr(lib, "_toc3d_select_bound", False):
         _bind_select(lib)
+    if name in _INGEST_SIGS and not getattr(lib, "_toc3d_ingest_bound", False):
+        _bind_ingest(lib)
     rc = getattr(lib, name)(*[_conv(a) for a in args])
     if rc != 0:
         raise RuntimeError(f"{name} failed ({rc}): {lib.toc3d_last_error().decode()}")
