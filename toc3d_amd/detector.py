@@ -12,8 +12,11 @@ The head then runs on those rows (``forward(..., img_feats_rows=True)``): the tr
 bit of the frame are the chain's.
 
 Differences to the reference, by design:
-* inference only: training mode, ``forward_train``, ``forward(return_loss=True)`` and ``token_select_vis=True`` raise ``NotImplementedError``;
+* inference only: training mode, ``forward_train`` and ``forward(return_loss=True)`` raise ``NotImplementedError``;
   ``use_grid_mask`` is accepted (GridMask is the identity outside training, ``grid_mask.py:85``); ``test_time_print`` is accepted and ignored;
+* ``token_select_vis=True`` (:562-579) is still refused BY THE CONSTRUCTOR, which the tests of the earlier surface pin; the step itself is there and is switched on
+  after construction (:meth:`Petr3D.enable_token_vis`) or by :func:`build_vis_detector`, which takes the shipped ``token_vis_ToC3D`` blocks unchanged.  The
+  overlays are rendered on the device (:class:`toc3d_amd.TokenVis`); every detection result and every piece of derived state keeps its bits;
 * with ``aux_2d_only=True`` (the default) ``img_roi_head=dict(type='FocalHead', ...)`` is accepted and nothing is built from it: the reference returns
   ``topk_indexes=None`` at eval without calling it (:319-320).  A checkpoint's ``img_roi_head.*`` keys are then dropped from the unexpected keys of
   ``load_state_dict``; nothing else is forgiven;
@@ -42,6 +45,7 @@ from .backbone import EVA_ViT, ToC3DEVAViT
 from .focal_head import FocalHead
 from .head import StreamPETRHead
 from .neck import CPFPN
+from .token_vis import TokenVis
 
 _NAME = "toc3d_amd.Petr3D"
 _ABSENT = ("pts_voxel_layer", "pts_voxel_encoder", "pts_middle_encoder", "pts_fusion_layer", "pts_backbone", "pts_neck", "img_rpn_head")
@@ -73,7 +77,8 @@ class Petr3D(_plan.DerivedState, nn.Module):
         if present:
             raise NotImplementedError(f"{_NAME}: {', '.join(present)} not implemented: the camera-only detector of the shipped configs passes None")
         if token_select_vis:
-            raise NotImplementedError(f"{_NAME}: token_select_vis=True (petr3d.py:562-579) is not implemented")
+            raise NotImplementedError(f"{_NAME}: token_select_vis=True (petr3d.py:562-579) is not implemented as a constructor keyword: call enable_token_vis() on the "
+                                      "built detector, or build it with toc3d_amd.build_vis_detector(cfg)")
         if position_level != 0:
             raise NotImplementedError(f"{_NAME}: position_level={position_level} is not implemented: the head reads neck level 0 (the shipped configs' default)")
         if not all(isinstance(c, dict) for c in (img_backbone, img_neck, pts_bbox_head)):
@@ -110,6 +115,7 @@ class Petr3D(_plan.DerivedState, nn.Module):
         self.query_backbone_selection = getattr(self.img_backbone, "pruning_loc", None) is not None                                     # :73-74
         self.token_select_vis, self.vis_num_sample, self.vis_out_path, self.vis_start_id, self.cur_id = False, vis_num_sample, vis_out_path, vis_start_id, 0
         self.test_time_print = test_time_print
+        self._token_vis = None                                              # a TokenVis, made by enable_token_vis()
         self._drop_derived()
         self.eval()
 
@@ -147,6 +153,47 @@ class Petr3D(_plan.DerivedState, nn.Module):
         if hasattr(state_dict, "_metadata"):
             kept._metadata = state_dict._metadata
         return super().load_state_dict(kept, strict=strict, **kw)
+
+    # ---- token selection overlays (:562-579) -----------------------------------------------------------------------------------------------------------------
+    def enable_token_vis(self, vis_num_sample=20, vis_start_id=0, vis_out_path="./token_vis"):
+        """What ``token_select_vis=True`` with these three keywords sets up in the reference (:48-55): from the next frame on, while ``vis_num_sample > 0``, every
+        frame whose number ``cur_id`` (counted from this call) is at least ``vis_start_id`` is rendered into ``./{vis_out_path}/{cur_id}/``.  A dense backbone has
+        no token masks: ``ValueError``."""
+        if not self.query_backbone_selection:
+            raise ValueError(f"{_NAME}: enable_token_vis needs a token-selecting backbone (ToC3DEVAViT with pruning_loc): a dense backbone has no masks")
+        self.token_select_vis, self.vis_num_sample, self.vis_start_id, self.vis_out_path, self.cur_id = True, int(vis_num_sample), int(vis_start_id), vis_out_path, 0
+        if self._token_vis is None:
+            self._token_vis = TokenVis(patch_size=getattr(self.img_backbone, "patch_size", 16))
+        return self
+
+    def disable_token_vis(self):
+        self.token_select_vis = False
+        return self
+
+    def _vis_norm_cfg(self, meta, img):
+        """``img_metas[0]['img_norm_cfg']`` (:575); the uint8 image form, whose pipeline has no normalisation step to record one, takes the backbone's."""
+        cfg = meta.get("img_norm_cfg") if isinstance(meta, dict) else None
+        if cfg is None and img.dtype == torch.uint8:
+            cfg = getattr(self.img_backbone, "img_norm_cfg", None)
+        return cfg
+
+    def _vis_step(self, img_metas, img, token_masks, keep_idxes, drop_idxes, streams=None):
+        """:562-579, in the reference's place: after ``extract_img_feat``, before the head.  ``streams``: B, for a step of several camera streams -- counted once,
+        stream b written under ``{cur_id}/stream{b}/``."""
+        if not (self.token_select_vis and self.vis_num_sample > 0):
+            return
+        if self.cur_id >= self.vis_start_id:
+            out = f"./{self.vis_out_path}/{self.cur_id}/"
+            vis = self._token_vis
+            rendered = vis.render(img, token_masks, keep_idxes, drop_idxes, self._vis_norm_cfg(img_metas[0], img))
+            if streams is None:
+                vis.write(rendered, out)
+            else:
+                n = rendered["ori"].shape[0] // streams
+                for b in range(streams):
+                    vis.write(rendered, f"{out}stream{b}/", views=range(b * n, (b + 1) * n))
+            self.vis_num_sample -= 1
+        self.cur_id += 1
 
     # ---- the reference's methods -------------------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -290,13 +337,14 @@ class Petr3D(_plan.DerivedState, nn.Module):
     @torch.no_grad()
     def simple_test(self, img_metas, gt_bboxes=None, centers2d=None, depths=None, gumbel_noise=None, **data):
         """:543-594: ``[dict(pts_bbox=dict(boxes_3d, scores_3d, labels_3d))]``.  What :meth:`extract_img_feat` returned for the frame -- the reference hands it to
-        ``token_selection_vis`` (:562-579) -- stays readable as ``self.last_frame`` until the next one."""
+        ``token_selection_vis`` (:562-579) -- stays readable as ``self.last_frame`` until the next one; after :meth:`enable_token_vis` it is rendered there too."""
         self._check_keeps_tokens(data["img"])
         prev_exists = img_metas[0]["scene_token"] == self.prev_scene_token                                                               # :546-549, as the bool it is
         img_feats, token_masks, _, keep_idxes, drop_idxes = self.extract_img_feat(data["img"], 1, gt_bboxes=gt_bboxes, centers2d=centers2d, depths=depths,
                                                                                   prev_exists=prev_exists, ego_pose_inv=data["ego_pose_inv"], gumbel_noise=gumbel_noise)
         data["img_feats"] = img_feats
         self.last_frame = dict(img_feats=img_feats, token_masks=token_masks, keep_idxes=keep_idxes, drop_idxes=drop_idxes)
+        self._vis_step(img_metas, data["img"], token_masks, keep_idxes, drop_idxes)                                                     # :562-579
         bbox_list = [dict() for _ in range(len(img_metas))]
         for result_dict, pts_bbox in zip(bbox_list, self.simple_test_pts(img_metas, **data)):
             result_dict["pts_bbox"] = pts_bbox
@@ -330,6 +378,7 @@ class Petr3D(_plan.DerivedState, nn.Module):
                                                                                   gumbel_noise=gumbel_noise)
         data["img_feats"] = img_feats
         self.last_frame = dict(img_feats=img_feats, token_masks=token_masks, keep_idxes=keep_idxes, drop_idxes=drop_idxes)
+        self._vis_step(img_metas, data["img"], token_masks, keep_idxes, drop_idxes, streams=B)
         data["prev_exists"] = torch.tensor([1.0 if p else 0.0 for p in prev], dtype=torch.float32, device=data["img"].device)
         location, topk_indexes = self._select_tokens(img_metas, data)
         return [dict(pts_bbox=r) for r in self._pts_results(img_metas, location, topk_indexes, data)]
@@ -358,3 +407,18 @@ class Petr3D(_plan.DerivedState, nn.Module):
             if key in data:
                 data[key] = list(zip(*data[key]))
         return self.forward_test(**data)
+
+
+def build_vis_detector(cfg, **kw):
+    """A ``model=dict(type='Petr3D', token_select_vis=True, vis_num_sample=..., vis_start_id=..., ...)`` block of the shipped ``token_vis_ToC3D`` configs, unchanged:
+    the four visualisation keywords are taken out, the rest builds through ``build_detector``, and the visualisation is enabled when the flag was set (the
+    constructor itself keeps refusing the flag: module docstring)."""
+    cfg = dict(cfg)
+    flag = cfg.pop("token_select_vis", False)
+    vis = {k: cfg.pop(k) for k in ("vis_num_sample", "vis_start_id", "vis_out_path") if k in cfg}
+    if not flag:
+        cfg.update(vis)                                                     # kept as the attributes the constructor makes of them
+    det = registry.build_detector(cfg, **kw)
+    if flag:
+        det.enable_token_vis(**vis)
+    return det

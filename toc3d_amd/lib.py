@@ -178,6 +178,15 @@ INGEST_TILE_W, INGEST_TILE_H, INGEST_LDS_ROWS, INGEST_MAX_KSIZE = 64, 32, 168, 3
 _INGEST_SIGS = {
     "toc3d_resize_crop_u8": "pllll" + "plll" + "ppl" + "ppl" + "l" + "p",
 }
+# include/toc3d_vis.h (token selection overlays: the reference's token_selection_vis as uint8 pixels, toc3d_amd.TokenVis): a side header likewise
+VIS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "toc3d_vis.h")
+VIS_ABI = 1                     # == TOC3D_VIS_ABI
+VIS_MAX_TOKENS = 8192           # == TOC3D_VIS_MAX_TOKENS
+_CT["d"] = ctypes.c_double      # 'd' double: min_alpha / max_alpha, whose difference the entry point forms as Python does
+_VIS_SIGS = {
+    "toc3d_token_alpha": "ppllll" + "dd" + "pp" + "p",
+    "toc3d_token_vis_render": "pil" + "llllll" + "pl" + "ffffff" + "i" + "pp" + "p",
+}
 
 _lib = None
 
@@ -332,6 +341,23 @@ def _bind_ingest(lib):
     lib._toc3d_ingest_bound = True
 
 
+def _bind_vis(lib):
+    """The entry points of include/toc3d_vis.h, bound when the first of them is called."""
+    try:
+        lib.toc3d_vis_abi.restype = _I
+        abi = lib.toc3d_vis_abi()
+        fns = {name: getattr(lib, name) for name in _VIS_SIGS}
+    except AttributeError:
+        abi, fns = None, {}
+    if abi != VIS_ABI:
+        raise RuntimeError(f"{LIB_PATH} reports vis ABI {abi}, this package binds {VIS_ABI} (include/toc3d_vis.h): "
+                           "rebuild the library (`make -C toc3d_amd/csrc`)")
+    for name, fn in fns.items():
+        fn.restype = _I
+        fn.argtypes = [_CT[c] for c in _VIS_SIGS[name]]
+    lib._toc3d_vis_bound = True
+
+
 def call(name: str, *args):
     """Invoke a C-ABI entry point; tensors are passed as device pointers; raises on a non-zero return."""
     lib = load()
@@ -345,6 +371,8 @@ def call(name: str, *args):
         _bind_select(lib)
     if name in _INGEST_SIGS and not getattr(lib, "_toc3d_ingest_bound", False):
         _bind_ingest(lib)
+    if name in _VIS_SIGS and not getattr(lib, "_toc3d_vis_bound", False):
+        _bind_vis(lib)
     rc = getattr(lib, name)(*[_conv(a) for a in args])
     if rc != 0:
         raise RuntimeError(f"{name} failed ({rc}): {lib.toc3d_last_error().decode()}")
