@@ -5,26 +5,17 @@
 #include "../../include/toc3d_vis.h"
 #include "capi.h"
 #include "common.h"
+#include "vis_pixel.h"                                   // sat_u8, mul_then_add, denorm_byte: the image byte, shared with box_vis.hip
 
 namespace {
 
 constexpr int MAXT = TOC3D_VIS_MAX_TOKENS;
 static_assert(MAXT % 4 == 0 && MAXT >= 5000, "the membership table is cleared in dwords and covers 1600 x 800 at patch 16");
 
-// OpenCV's saturate_cast<uchar>(float): round half to even, clip.  (fmaxf returns its other operand for a NaN: 0.)
-TOC3D_DEV uint32_t sat_u8(float v) { return (uint32_t)(int)fminf(fmaxf(rintf(v), 0.f), 255.f); }
-// x * s, rounded, then + m, rounded.  The pragma is what keeps the two apart: hipcc contracts by default, and it fuses __fadd_rn(__fmul_rn(x, s), m) as well
-// (seen in this file's assembly: v_fma_f32).  The assembly of the kernels below holds v_mul_f32 and v_add_f32 and no v_fma_f32 / v_fmac_f32 on floats.
-TOC3D_DEV float mul_then_add(float x, float s, float m) {
-#pragma clang fp contract(off)
-    const float p = x * s;
-    return p + m;
-}
 TOC3D_DEV uint32_t alpha_byte(float m, float lo, float span) {
 #pragma clang fp contract(off)
     return sat_u8(255.f * mul_then_add(m, span, lo));
 }
-TOC3D_DEV uint32_t denorm_byte(float x, float sd, float mu) { return sat_u8(mul_then_add(x, sd, mu)); }
 
 __global__ __launch_bounds__(256) void token_alpha_kernel(const float* mask, const int64_t* keep, int64_t keep_stride, int K, int T, float lo, float span,
                                                           uint8_t* alpha_mask, uint8_t* alpha_keep) {

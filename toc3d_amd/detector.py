@@ -16,7 +16,9 @@ Differences to the reference, by design:
   ``use_grid_mask`` is accepted (GridMask is the identity outside training, ``grid_mask.py:85``); ``test_time_print`` is accepted and ignored;
 * ``token_select_vis=True`` (:562-579) is still refused BY THE CONSTRUCTOR, which the tests of the earlier surface pin; the step itself is there and is switched on
   after construction (:meth:`Petr3D.enable_token_vis`) or by :func:`build_vis_detector`, which takes the shipped ``token_vis_ToC3D`` blocks unchanged.  The
-  overlays are rendered on the device (:class:`toc3d_amd.TokenVis`); every detection result and every piece of derived state keeps its bits;
+  overlays are rendered on the device (:class:`toc3d_amd.TokenVis`); every detection result and every piece of derived state keeps its bits.  The same holds
+  for :meth:`Petr3D.enable_box_vis`, which draws the decoded boxes onto the camera views and a top-down panel (:class:`toc3d_amd.BoxVis`; the reference does that
+  outside the detector, ``tools/visualize.py``);
 * with ``aux_2d_only=True`` (the default) ``img_roi_head=dict(type='FocalHead', ...)`` is accepted and nothing is built from it: the reference returns
   ``topk_indexes=None`` at eval without calling it (:319-320).  A checkpoint's ``img_roi_head.*`` keys are then dropped from the unexpected keys of
   ``load_state_dict``; nothing else is forgiven;
@@ -46,6 +48,7 @@ from .focal_head import FocalHead
 from .head import StreamPETRHead
 from .neck import CPFPN
 from .token_vis import TokenVis
+from .box_vis import BoxVis
 
 _NAME = "toc3d_amd.Petr3D"
 _ABSENT = ("pts_voxel_layer", "pts_voxel_encoder", "pts_middle_encoder", "pts_fusion_layer", "pts_backbone", "pts_neck", "img_rpn_head")
@@ -116,6 +119,8 @@ class Petr3D(_plan.DerivedState, nn.Module):
         self.token_select_vis, self.vis_num_sample, self.vis_out_path, self.vis_start_id, self.cur_id = False, vis_num_sample, vis_out_path, vis_start_id, 0
         self.test_time_print = test_time_print
         self._token_vis = None                                              # a TokenVis, made by enable_token_vis()
+        self.box_vis, self.box_vis_num_sample, self.box_vis_start_id, self.box_vis_out_path, self.box_vis_cur_id = False, 0, 0, "./box_vis", 0
+        self._box_vis = None                                                # a BoxVis, made by enable_box_vis()
         self._drop_derived()
         self.eval()
 
@@ -194,6 +199,38 @@ class Petr3D(_plan.DerivedState, nn.Module):
                     vis.write(rendered, f"{out}stream{b}/", views=range(b * n, (b + 1) * n))
             self.vis_num_sample -= 1
         self.cur_id += 1
+
+    # ---- predicted boxes on the camera views and a top-down panel (no counterpart in the reference's detector: tools/visualize.py draws from a result JSON) ----
+    def enable_box_vis(self, num_sample=20, start_id=0, out_path="./box_vis", **box_vis_kwargs):
+        """From the next frame on, while ``num_sample > 0``, every frame whose number (counted from this call, with a counter of its own: ``box_vis_cur_id``) is at
+        least ``start_id`` has its detections drawn into ``./{out_path}/{cur_id}/`` (``view{v}_pred.png``, ``bev_pred.png``); a step of several camera streams
+        writes stream b under ``{cur_id}/stream{b}/``.  ``box_vis_kwargs`` go to :class:`toc3d_amd.BoxVis`.  Every result and every piece of derived state keeps
+        its bits; the token overlays (:meth:`enable_token_vis`) may be on as well."""
+        self._box_vis = BoxVis(**box_vis_kwargs)
+        self.box_vis, self.box_vis_num_sample, self.box_vis_start_id, self.box_vis_out_path, self.box_vis_cur_id = True, int(num_sample), int(start_id), out_path, 0
+        return self
+
+    def disable_box_vis(self):
+        self.box_vis = False
+        return self
+
+    def _box_vis_step(self, img_metas, data, bbox_list, streams=None):
+        """In :meth:`_pts_results`: from the device tensors ``get_bboxes`` returned, before ``bbox3d2result`` moves them to the host.  Counts as
+        :meth:`_vis_step` does."""
+        if not (self.box_vis and self.box_vis_num_sample > 0):
+            return
+        if data.get("lidar2img") is None:
+            raise ValueError(f"{_NAME}: box visualisation is enabled but the frame carries no lidar2img (data['lidar2img'], (B, N, 4, 4)): the boxes cannot be "
+                             "projected into the views")
+        if self.box_vis_cur_id >= self.box_vis_start_id:
+            out = f"./{self.box_vis_out_path}/{self.box_vis_cur_id}/"
+            vis, img, l2i = self._box_vis, data["img"], data["lidar2img"]
+            for b, (bboxes, scores, labels) in enumerate(bbox_list):
+                cfg = self._vis_norm_cfg(img_metas[b if streams is not None else 0], img)
+                rendered = vis.render(img[b], bboxes, scores, labels, l2i[b], cfg)
+                vis.write(rendered, out if streams is None else f"{out}stream{b}/")
+            self.box_vis_num_sample -= 1
+        self.box_vis_cur_id += 1
 
     # ---- the reference's methods -------------------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -326,12 +363,14 @@ class Petr3D(_plan.DerivedState, nn.Module):
             data["prev_exists"] = data["img"].new_ones(1)
         return self._pts_results(img_metas, location, topk_indexes, data)
 
-    def _pts_results(self, img_metas, location, topk_indexes, data):
-        """The head on ``data`` (``prev_exists`` decided by the caller) and the decoded lists, one per sample."""
+    def _pts_results(self, img_metas, location, topk_indexes, data, streams=None):
+        """The head on ``data`` (``prev_exists`` decided by the caller) and the decoded lists, one per sample; after :meth:`enable_box_vis` the lists are drawn
+        while they are still on the device (``streams``: B, for a step of several camera streams)."""
         fanned = self._is_fanned(data["img_feats"])
         self._fanned = None
         outs = self.pts_bbox_head(location, img_metas, topk_indexes, img_feats_rows=fanned, **data)
         bbox_list = self.pts_bbox_head.get_bboxes(outs, img_metas)
+        self._box_vis_step(img_metas, data, bbox_list, streams)
         return [bbox3d2result(bboxes, scores, labels) for bboxes, scores, labels in bbox_list]
 
     @torch.no_grad()
@@ -381,7 +420,7 @@ class Petr3D(_plan.DerivedState, nn.Module):
         self._vis_step(img_metas, data["img"], token_masks, keep_idxes, drop_idxes, streams=B)
         data["prev_exists"] = torch.tensor([1.0 if p else 0.0 for p in prev], dtype=torch.float32, device=data["img"].device)
         location, topk_indexes = self._select_tokens(img_metas, data)
-        return [dict(pts_bbox=r) for r in self._pts_results(img_metas, location, topk_indexes, data)]
+        return [dict(pts_bbox=r) for r in self._pts_results(img_metas, location, topk_indexes, data, streams=B)]
 
     def reset_streams(self, indices=None):
         """Forget the scene tokens of the streams ``indices`` (default: all): their next step starts a scene whatever token it carries."""

@@ -187,6 +187,16 @@ _VIS_SIGS = {
     "toc3d_token_alpha": "ppllll" + "dd" + "pp" + "p",
     "toc3d_token_vis_render": "pil" + "llllll" + "pl" + "ffffff" + "i" + "pp" + "p",
 }
+# include/toc3d_boxes.h (predicted 3-D boxes drawn on the camera views and a top-down panel, toc3d_amd.BoxVis): a side header likewise
+BOXES_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "toc3d_boxes.h")
+BOXES_ABI = 1                   # == TOC3D_BOXES_ABI
+BOXES_CAMERA_EDGES, BOXES_BEV_EDGES, BOXES_MAX_SIDE, BOXES_MAX_GUARD, BOXES_MAX_THICKNESS = 12, 5, 8192, 16, 15     # == TOC3D_BOXES_CAMERA_EDGES, ...
+BOXES_TILE_W, BOXES_TILE_H = 64, 16                                                                                  # == TOC3D_BOXES_TILE_W, _TILE_H
+_BOXES_SIGS = {
+    "toc3d_box_segments": "plpplfl" + "plflll" + "l" + "ppp" + "p",
+    "toc3d_box_segments_bev": "plpplfl" + "lfl" + "l" + "ppp" + "p",
+    "toc3d_segments_render": "pil" + "lll" + "ffffff" + "i" + "iii" + "ppl" + "pl" + "ll" + "p" + "p",
+}
 
 _lib = None
 
@@ -358,6 +368,23 @@ def _bind_vis(lib):
     lib._toc3d_vis_bound = True
 
 
+def _bind_boxes(lib):
+    """The entry points of include/toc3d_boxes.h, bound when the first of them is called."""
+    try:
+        lib.toc3d_boxes_abi.restype = _I
+        abi = lib.toc3d_boxes_abi()
+        fns = {name: getattr(lib, name) for name in _BOXES_SIGS}
+    except AttributeError:
+        abi, fns = None, {}
+    if abi != BOXES_ABI:
+        raise RuntimeError(f"{LIB_PATH} reports boxes ABI {abi}, this package binds {BOXES_ABI} (include/toc3d_boxes.h): "
+                           "rebuild the library (`make -C toc3d_amd/csrc`)")
+    for name, fn in fns.items():
+        fn.restype = _I
+        fn.argtypes = [_CT[c] for c in _BOXES_SIGS[name]]
+    lib._toc3d_boxes_bound = True
+
+
 def call(name: str, *args):
     """Invoke a C-ABI entry point; tensors are passed as device pointers; raises on a non-zero return."""
     lib = load()
@@ -373,6 +400,8 @@ def call(name: str, *args):
         _bind_ingest(lib)
     if name in _VIS_SIGS and not getattr(lib, "_toc3d_vis_bound", False):
         _bind_vis(lib)
+    if name in _BOXES_SIGS and not getattr(lib, "_toc3d_boxes_bound", False):
+        _bind_boxes(lib)
     rc = getattr(lib, name)(*[_conv(a) for a in args])
     if rc != 0:
         raise RuntimeError(f"{name} failed ({rc}): {lib.toc3d_last_error().decode()}")
