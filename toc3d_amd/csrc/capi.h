@@ -29,6 +29,16 @@ void toc3d_set_error(const char* fmt, ...);
 
 static inline hipStream_t as_stream(toc3d_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
+// the last argument check of an entry point whose buffers must all be device memory: a host pointer is refused, not dereferenced by a kernel
+static inline bool toc3d_device_memory(const void* p) {
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();                                         // an unknown pointer leaves an error behind: not a launch's
+        return false;
+    }
+    return at.type == hipMemoryTypeDevice;
+}
+
 // ---- launch recorder (plan.cpp) ---------------------------------------------------------------------
 // Every kernel of the library is launched through toc3d_launch().  Normally that is hipLaunchKernelGGL.  While a host
 // thread is between toc3d_plan_begin() and toc3d_plan_end(), its launches are *recorded* instead (kernel, grid, block,

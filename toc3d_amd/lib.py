@@ -197,6 +197,13 @@ _BOXES_SIGS = {
     "toc3d_box_segments_bev": "plpplfl" + "lfl" + "l" + "ppp" + "p",
     "toc3d_segments_render": "pil" + "lll" + "ffffff" + "i" + "iii" + "ppl" + "pl" + "ll" + "p" + "p",
 }
+# include/toc3d_results.h (decoded boxes to nuScenes submission records in the global frame, toc3d_amd.NuScenesResults): a side header likewise
+RESULTS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "toc3d_results.h")
+RESULTS_ABI = 1                 # == TOC3D_RESULTS_ABI
+RESULTS_MAX_BOXES, RESULTS_MAX_CLASSES, RESULTS_REC = 2048, 64, 12      # == TOC3D_RESULTS_MAX_BOXES, _MAX_CLASSES, _REC
+_RESULTS_SIGS = {
+    "toc3d_boxes_to_global": "pll" + "ppp" + "ll" + "i" + "p" + "ppp" + "l" + "d" + "pppppp" + "p",
+}
 
 _lib = None
 
@@ -385,6 +392,23 @@ def _bind_boxes(lib):
     lib._toc3d_boxes_bound = True
 
 
+def _bind_results(lib):
+    """The entry point of include/toc3d_results.h, bound when it is first called."""
+    try:
+        lib.toc3d_results_abi.restype = _I
+        abi = lib.toc3d_results_abi()
+        fns = {name: getattr(lib, name) for name in _RESULTS_SIGS}
+    except AttributeError:
+        abi, fns = None, {}
+    if abi != RESULTS_ABI:
+        raise RuntimeError(f"{LIB_PATH} reports results ABI {abi}, this package binds {RESULTS_ABI} (include/toc3d_results.h): "
+                           "rebuild the library (`make -C toc3d_amd/csrc`)")
+    for name, fn in fns.items():
+        fn.restype = _I
+        fn.argtypes = [_CT[c] for c in _RESULTS_SIGS[name]]
+    lib._toc3d_results_bound = True
+
+
 def call(name: str, *args):
     """Invoke a C-ABI entry point; tensors are passed as device pointers; raises on a non-zero return."""
     lib = load()
@@ -402,6 +426,8 @@ def call(name: str, *args):
         _bind_vis(lib)
     if name in _BOXES_SIGS and not getattr(lib, "_toc3d_boxes_bound", False):
         _bind_boxes(lib)
+    if name in _RESULTS_SIGS and not getattr(lib, "_toc3d_results_bound", False):
+        _bind_results(lib)
     rc = getattr(lib, name)(*[_conv(a) for a in args])
     if rc != 0:
         raise RuntimeError(f"{name} failed ({rc}): {lib.toc3d_last_error().decode()}")
