@@ -1,10 +1,12 @@
-"""What the test files share: device plumbing, error measures, the (hi, lo) planes layout, guard patterns and the worst-ratio report.  A plain module -- no
+"""What the test files share: device plumbing, raw C-ABI calls, the header parser, error measures, the (hi, lo) planes layout, guard patterns and the worst-ratio report.  A plain module -- no
 conftest.py, no package, no test; importing it needs no GPU.  The restated references and case generators live beside it in the ``*_cases.py`` modules.  No
 module under tests/ imports from a ``test_*`` module (tests/test_cpu_support.py checks that); a new kernel test starts from here.
 
 Two helpers are one here only where they return the same value for every argument.  Where results can differ both forms stay, under their own names: ``relerr``
 clamps its denominator and ``rel_max`` does not, ``rel_max_zero_ok`` has a branch for an all-zero reference, the canary (a finite pattern, element-wise checks) is
 not the NaN sentinel (checked as a whole), and ``to_planes`` converts out of place or in place."""
+import ctypes
+import re
 import socket
 
 import numpy as np
@@ -75,6 +77,53 @@ def _call(name, *args):
 def _refused(name, args, reason, fn=None):
     rc, msg = _call(name, *args)
     assert rc == ERR_ARG and (fn or name) in msg and reason in msg, (rc, msg)
+
+
+A = 0x10000                                  # 256-byte aligned stand-in for a device buffer (never dereferenced: the checks run before any launch)
+
+
+def raw_call(sigs, name, args):
+    """An entry point of a side header called directly, past lib.call(): bound with ``sigs[name]`` (one of lib's tables) -> (return code, last error)."""
+    l = lib.load()
+    fn = getattr(l, name)
+    fn.restype, fn.argtypes = ctypes.c_int, [lib._CT[c] for c in sigs[name]]
+    rc = fn(*args)
+    return rc, l.toc3d_last_error().decode()
+
+
+class OldLibrary:
+    """In place of lib._lib: a library from before a side header existed -- it has none of the header's symbols."""
+    def toc3d_last_error(self):
+        return b""
+
+
+# ---- headers against lib's tables ----------------------------------------------------------------------------------------------------------------
+def header_sigs(txt, sigs):
+    """{name: signature} of the ``int toc3d_*(...)`` declarations in ``txt`` (a header without comments, lib.header_text) that ``sigs`` names, in the letters of
+    lib._CT.  Declarations with other names -- the helpers lib.load() binds by hand -- are passed over; a parameter of a type not listed here fails."""
+    found = {}
+    for m in re.finditer(r"\bint\s+(toc3d_\w+)\s*\(([^;]*?)\)\s*;", txt, flags=re.S):
+        name, args = m.group(1), m.group(2)
+        if name not in sigs:
+            continue
+        sig = ""
+        for a in (x.strip() for x in args.split(",")):
+            if "*" in a or "toc3d_stream_t" in a or "toc3d_plan_t" in a:
+                sig += "p"
+            elif a.startswith("int64_t"):
+                sig += "l"
+            elif a.startswith("uint64_t"):
+                sig += "L"
+            elif a.startswith("int "):
+                sig += "i"
+            elif a.startswith("float "):
+                sig += "f"
+            elif a.startswith("double "):
+                sig += "d"
+            else:
+                raise AssertionError(f"unparsed parameter {a!r} in {name}")
+        found[name] = sig
+    return found
 
 
 class FakeNeck(torch.nn.Module):

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import toc3d_amd
+from support import OldLibrary, header_sigs
 from toc3d_amd import configs, lib
 
 
@@ -26,33 +27,33 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_ctypes_signatures_match_header():
-    txt = lib.header_text()
     sigs = dict(lib._SIGS)
     seen = 0
-    for m in re.finditer(r"\bint\s+(toc3d_\w+)\s*\(([^;]*?)\)\s*;", txt, flags=re.S):
-        name, args = m.group(1), m.group(2)
-        if name == "toc3d_abi_version":
-            continue
-        if name not in sigs:
-            continue                      # helpers with other return types are bound by hand in lib.load()
-        sig = ""
-        for a in (x.strip() for x in args.split(",")):
-            if "*" in a or "toc3d_stream_t" in a or "toc3d_plan_t" in a:
-                sig += "p"
-            elif a.startswith("int64_t"):
-                sig += "l"
-            elif a.startswith("uint64_t"):
-                sig += "L"
-            elif a.startswith("int "):
-                sig += "i"
-            elif a.startswith("float "):
-                sig += "f"
-            else:
-                raise AssertionError(f"unparsed parameter {a!r} in {name}")
+    for name, sig in header_sigs(lib.header_text(), sigs).items():        # (toc3d_abi_version and the helpers bound by hand in lib.load() are not in the table)
         assert sigs[name] == sig, name
         seen += 1
     assert seen == len(sigs)
     assert lib.load().toc3d_window_topk_rows(6, 20, 50, 16, 128) == 6 * (3 * 129 + 33 + 3 * 65 + 9)
+
+
+@pytest.mark.parametrize("key", list(lib.SIDES))
+def test_side_header_table_and_binder_agree(key, monkeypatch):
+    """What each side header's own file checks, once over lib.SIDES: no name in two tables, the header declares the table's names and its ABI symbol and nothing
+    else, the parsed signatures are the table, and a library without the symbols is told to rebuild by the one binder, naming that header."""
+    path, abi_fn, abi, sigs = lib.SIDES[key]
+    assert abi_fn == f"toc3d_{key}_abi" and os.path.basename(path) == f"toc3d_{key}.h" and abi == getattr(lib, f"{key.upper()}_ABI")
+    assert sigs is getattr(lib, f"_{key.upper()}_SIGS") and path == getattr(lib, f"{key.upper()}_HEADER_PATH") and sigs
+    for other, row in lib.SIDES.items():
+        assert other == key or not set(sigs) & set(row[3]), f"a name of {key} is also in {other}"
+    assert not set(sigs) & set(lib._SIGS)
+    assert all(lib._SIDE_OF[n] == key for n in sigs) and len(lib._SIDE_OF) == sum(len(row[3]) for row in lib.SIDES.values())
+    txt = lib.header_text(path)
+    assert set(re.findall(r"\b(toc3d_\w+)\s*\(", txt)) == set(sigs) | {abi_fn}
+    assert header_sigs(txt, sigs) == sigs
+    first = next(iter(sigs))
+    monkeypatch.setattr(lib, "_lib", OldLibrary())
+    with pytest.raises(RuntimeError, match=rf"reports {key} ABI None, this package binds {abi} \(include/toc3d_{key}\.h\): rebuild the library \(`make -C toc3d_amd/csrc`\)$"):
+        lib.call(first, *[None] * len(sigs[first]))
 
 
 def test_argument_validation_reports_errors_without_gpu():

@@ -14,42 +14,18 @@ import torch.nn as nn
 import box_vis_cases as BC
 import toc3d_amd
 import token_vis_cases as TC
-from support import FakeNeck
+from support import A, ERR_ARG, FakeNeck, OldLibrary, header_sigs, raw_call
 from toc3d_amd import box_vis as BV
 from toc3d_amd import lib, synth
 
-A = 0x10000                                  # 256-byte aligned stand-in for a device buffer (never dereferenced)
-ERR_ARG = -1
 CAM, BEV, RENDER = "toc3d_box_segments", "toc3d_box_segments_bev", "toc3d_segments_render"
 
 
 # ---- the ABI ---------------------------------------------------------------------------------------------------------------------------------------------------------
-def parse(txt, sigs):
-    found = {}
-    for m in re.finditer(r"\bint\s+(toc3d_\w+)\s*\(([^;]*?)\)\s*;", txt, flags=re.S):
-        name, args = m.group(1), m.group(2)
-        if name not in sigs:
-            continue
-        sig = ""
-        for a in (x.strip() for x in args.split(",")):
-            if "*" in a or "toc3d_stream_t" in a:
-                sig += "p"
-            elif a.startswith("int64_t"):
-                sig += "l"
-            elif a.startswith("int "):
-                sig += "i"
-            elif a.startswith("float "):
-                sig += "f"
-            else:
-                raise AssertionError(f"unparsed parameter {a!r} in {name}")
-        found[name] = sig
-    return found
-
-
 def test_boxes_header_ctypes_table_and_exports_agree():
     raw = open(lib.BOXES_HEADER_PATH).read()
     txt = lib.header_text(lib.BOXES_HEADER_PATH)
-    found = parse(txt, lib._BOXES_SIGS)
+    found = header_sigs(txt, lib._BOXES_SIGS)
     print(f"toc3d_boxes.h declares {found}")
     assert found == lib._BOXES_SIGS and list(found) == [CAM, BEV, RENDER]
     declared = set(re.findall(r"\b(toc3d_\w+)\s*\(", txt))
@@ -112,24 +88,13 @@ def render_args(**o):
 ARGS = {CAM: cam_args, BEV: bev_args, RENDER: render_args}
 
 
-def raw_call(name, args):
-    l = lib.load()
-    fn = getattr(l, name)
-    fn.restype, fn.argtypes = ctypes.c_int, [lib._CT[c] for c in lib._BOXES_SIGS[name]]
-    rc = fn(*args)
-    return rc, l.toc3d_last_error().decode()
-
-
 def test_call_binds_the_entry_points_and_an_old_library_is_told_to_rebuild(monkeypatch):
     with pytest.raises(RuntimeError, match=r"toc3d_box_segments failed \(-1\): toc3d_box_segments: null buffer"):
         lib.call(CAM, *cam_args(boxes=None))
     for name in lib._BOXES_SIGS:
         assert getattr(lib.load(), name).argtypes == [lib._CT[c] for c in lib._BOXES_SIGS[name]], "bound with the table's argument types"
 
-    class Old:                                # a library from before the header existed: it has none of the symbols
-        def toc3d_last_error(self):
-            return b""
-    monkeypatch.setattr(lib, "_lib", Old())
+    monkeypatch.setattr(lib, "_lib", OldLibrary())
     with pytest.raises(RuntimeError, match=r"toc3d_boxes\.h.*rebuild the library"):
         lib.call(RENDER, *render_args())
 
@@ -168,7 +133,7 @@ GEOM_COMMON = [
     (RENDER, dict(nseg=0, segi=None, cidx=None), "host pointer"), (RENDER, dict(t=15, guard=8), "host pointer"), (RENDER, dict(t=1, guard=1), "host pointer"),
 ])
 def test_entry_point_refusals(name, over, reason):
-    rc, msg = raw_call(name, ARGS[name](**over))
+    rc, msg = raw_call(lib._BOXES_SIGS, name, ARGS[name](**over))
     print(f"{name} {over}: rc {rc}, {msg!r}")
     assert rc == ERR_ARG and msg.startswith(name + ":") and reason in msg, (rc, msg)
 
@@ -176,9 +141,9 @@ def test_entry_point_refusals(name, over, reason):
 def test_no_boxes_is_legal_for_the_geometry():
     """n == 0: nothing is launched, no pointer is looked at (none is device memory here), and the call succeeds."""
     for name in (CAM, BEV):
-        rc, msg = raw_call(name, ARGS[name](n=0))
+        rc, msg = raw_call(lib._BOXES_SIGS, name, ARGS[name](n=0))
         assert rc == 0, (name, rc, msg)
-        rc, msg = raw_call(name, ARGS[name](n=0, boxes=None, scores=None, labels=None, segf=None, segi=None, cidx=None))
+        rc, msg = raw_call(lib._BOXES_SIGS, name, ARGS[name](n=0, boxes=None, scores=None, labels=None, segf=None, segi=None, cidx=None))
         assert rc == 0, (name, rc, msg)
 
 
@@ -191,15 +156,15 @@ def test_real_host_buffers_are_refused_and_left_alone():
     proj = (ctypes.c_float * 16)(*([1.0] * 16))
     segf, segi, cidx = (ctypes.c_float * 96)(*([7.0] * 96)), (ctypes.c_int32 * 96)(*([7] * 96)), (ctypes.c_ubyte * 24)(*([9] * 24))
     untouched = lambda: list(segf) == [7.0] * 96 and list(segi) == [7] * 96 and bytes(cidx) == bytes([9] * 24) and list(boxes) == [1.0] * 18
-    rc, msg = raw_call(CAM, cam_args(boxes=p(boxes), scores=p(scores), labels=p(labels), n=2, proj=p(proj), V=1, H=16, W=16, segf=p(segf), segi=p(segi), cidx=p(cidx)))
+    rc, msg = raw_call(lib._BOXES_SIGS, CAM, cam_args(boxes=p(boxes), scores=p(scores), labels=p(labels), n=2, proj=p(proj), V=1, H=16, W=16, segf=p(segf), segi=p(segi), cidx=p(cidx)))
     print(f"rc {rc}, {msg!r}")
     assert rc == ERR_ARG and "host pointer" in msg and untouched()
-    rc, msg = raw_call(BEV, bev_args(boxes=p(boxes), scores=p(scores), labels=p(labels), n=2, S=16, segf=p(segf), segi=p(segi), cidx=p(cidx)))
+    rc, msg = raw_call(lib._BOXES_SIGS, BEV, bev_args(boxes=p(boxes), scores=p(scores), labels=p(labels), n=2, S=16, segf=p(segf), segi=p(segi), cidx=p(cidx)))
     assert rc == ERR_ARG and "host pointer" in msg and untouched()
     src = (ctypes.c_ubyte * 768)(*([7] * 768))
     pal = (ctypes.c_ubyte * 30)(*([5] * 30))
     out = (ctypes.c_ubyte * 768)(*([9] * 768))
-    rc, msg = raw_call(RENDER, render_args(src=p(src), kind=1, src_stride=48, V=1, H=16, W=16, segi=p(segi), cidx=p(cidx), nseg=24, palette=p(pal), out=p(out)))
+    rc, msg = raw_call(lib._BOXES_SIGS, RENDER, render_args(src=p(src), kind=1, src_stride=48, V=1, H=16, W=16, segi=p(segi), cidx=p(cidx), nseg=24, palette=p(pal), out=p(out)))
     print(f"rc {rc}, {msg!r}")
     assert rc == ERR_ARG and "host pointer" in msg and untouched()
     assert bytes(out) == bytes([9] * 768) and bytes(src) == bytes([7] * 768) and bytes(pal) == bytes([5] * 30)

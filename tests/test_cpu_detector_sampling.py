@@ -14,12 +14,11 @@ import torch
 import torch.nn as nn
 
 import toc3d_amd
-from support import ERR_ARG, FakeNeck
+from support import A, ERR_ARG, FakeNeck, OldLibrary, header_sigs, raw_call
 from toc3d_amd import FocalHead, lib, synth
 from toc3d_amd.detector import Petr3D
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-A = 0x10000                                  # 256-byte aligned stand-in for a device buffer (never dereferenced)
 TINY = synth.DETECTOR_TINY_ROI
 
 
@@ -28,32 +27,9 @@ def tiny(**over):
 
 
 # ---- the ABI ---------------------------------------------------------------------------------------------------------------------------------------------------------
-def parse(txt, sigs):
-    """{name: signature} of the ``int toc3d_*(...)`` declarations that ``sigs`` names (the parser of tests/test_cpu_abi.py)."""
-    found = {}
-    for m in re.finditer(r"\bint\s+(toc3d_\w+)\s*\(([^;]*?)\)\s*;", txt, flags=re.S):
-        name, args = m.group(1), m.group(2)
-        if name not in sigs:
-            continue
-        sig = ""
-        for a in (x.strip() for x in args.split(",")):
-            if "*" in a or "toc3d_stream_t" in a:
-                sig += "p"
-            elif a.startswith("int64_t"):
-                sig += "l"
-            elif a.startswith("int "):
-                sig += "i"
-            elif a.startswith("float "):
-                sig += "f"
-            else:
-                raise AssertionError(f"unparsed parameter {a!r} in {name}")
-        found[name] = sig
-    return found
-
-
 def test_select_header_ctypes_table_and_exports_agree():
     raw = open(lib.SELECT_HEADER_PATH).read()
-    found = parse(lib.header_text(lib.SELECT_HEADER_PATH), lib._SELECT_SIGS)
+    found = header_sigs(lib.header_text(lib.SELECT_HEADER_PATH), lib._SELECT_SIGS)
     print(f"toc3d_select.h declares {found}")
     assert found == lib._SELECT_SIGS and list(found) == ["toc3d_focal_sample_weight"]
     declared = set(re.findall(r"\b(toc3d_\w+)\s*\(", lib.header_text(lib.SELECT_HEADER_PATH)))
@@ -86,10 +62,7 @@ def test_call_binds_the_entry_point_and_an_old_library_is_told_to_rebuild(monkey
     for n, sig in lib._SELECT_SIGS.items():
         assert getattr(lib.load(), n).argtypes == [lib._CT[c] for c in sig], "bound with the table's argument types (int64 counts, not C ints)"
 
-    class Old:                                # a library from before the header existed: it has none of the symbols
-        def toc3d_last_error(self):
-            return b""
-    monkeypatch.setattr(lib, "_lib", Old())
+    monkeypatch.setattr(lib, "_lib", OldLibrary())
     with pytest.raises(RuntimeError, match=r"toc3d_select\.h.*rebuild the library"):
         lib.call("toc3d_focal_sample_weight", *weight_args())
 
@@ -106,10 +79,7 @@ def test_call_binds_the_entry_point_and_an_old_library_is_told_to_rebuild(monkey
     (lib.F32, dict(T=1 << 31), "too many"), (lib.F32, dict(V=1 << 31, T=32), "too many"),
 ])
 def test_sample_weight_refusals(dtype, over, reason):
-    l = lib.load()
-    fn = l.toc3d_focal_sample_weight
-    fn.restype, fn.argtypes = ctypes.c_int, [lib._CT[c] for c in lib._SELECT_SIGS["toc3d_focal_sample_weight"]]
-    rc, msg = fn(*weight_args(dtype, **over)), l.toc3d_last_error().decode()
+    rc, msg = raw_call(lib._SELECT_SIGS, "toc3d_focal_sample_weight", weight_args(dtype, **over))
     print(f"{over or dtype}: rc {rc}, {msg!r}")
     assert rc == ERR_ARG and msg.startswith("toc3d_focal_sample_weight:") and reason in msg, (rc, msg)
 

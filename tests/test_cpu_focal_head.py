@@ -13,11 +13,10 @@ import torch
 
 import focal_head_cases as FC
 import toc3d_amd
+from support import A, ERR_ARG, OldLibrary, header_sigs, raw_call
 from toc3d_amd import FocalHead, lib, registry, synth
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-A = 0x10000                                  # 256-byte aligned stand-in for a device buffer (never dereferenced)
-ERR_ARG = -1
 F32_ROUNDING = 2e-6                          # the restatement and the reference spell the same f32 formulas: they differ by the order of a few roundings
 
 
@@ -129,32 +128,9 @@ def test_refusals():
 
 
 # ---- the ABI ---------------------------------------------------------------------------------------------------------------------------------------------------------
-def parse(txt, sigs):
-    """{name: signature} of the ``int toc3d_*(...)`` declarations that ``sigs`` names (the parser of tests/test_cpu_abi.py)."""
-    found = {}
-    for m in re.finditer(r"\bint\s+(toc3d_\w+)\s*\(([^;]*?)\)\s*;", txt, flags=re.S):
-        name, args = m.group(1), m.group(2)
-        if name not in sigs:
-            continue
-        sig = ""
-        for a in (x.strip() for x in args.split(",")):
-            if "*" in a or "toc3d_stream_t" in a:
-                sig += "p"
-            elif a.startswith("int64_t"):
-                sig += "l"
-            elif a.startswith("int "):
-                sig += "i"
-            elif a.startswith("float "):
-                sig += "f"
-            else:
-                raise AssertionError(f"unparsed parameter {a!r} in {name}")
-        found[name] = sig
-    return found
-
-
 def test_focal_header_ctypes_table_and_exports_agree():
     raw = open(lib.FOCAL_HEADER_PATH).read()
-    found = parse(lib.header_text(lib.FOCAL_HEADER_PATH), lib._FOCAL_SIGS)
+    found = header_sigs(lib.header_text(lib.FOCAL_HEADER_PATH), lib._FOCAL_SIGS)
     print(f"toc3d_focal.h declares {found}")
     assert found == lib._FOCAL_SIGS and list(found) == ["toc3d_focal_gn_stats", "toc3d_focal_heads"]
     declared = set(re.findall(r"\b(toc3d_\w+)\s*\(", lib.header_text(lib.FOCAL_HEADER_PATH)))
@@ -176,10 +152,7 @@ def test_call_binds_the_entry_points_and_an_old_library_is_told_to_rebuild(monke
     for n, sig in lib._FOCAL_SIGS.items():
         assert getattr(lib.load(), n).argtypes == [lib._CT[c] for c in sig], "bound with the table's argument types (int64 counts, not C ints)"
 
-    class Old:                                # a library from before the header existed: it has none of the symbols
-        def toc3d_last_error(self):
-            return b""
-    monkeypatch.setattr(lib, "_lib", Old())
+    monkeypatch.setattr(lib, "_lib", OldLibrary())
     with pytest.raises(RuntimeError, match=r"toc3d_focal\.h.*rebuild the library"):
         lib.call("toc3d_focal_heads", *heads_args())
 
@@ -200,14 +173,6 @@ def heads_args(dtype=lib.F32, **o):
             a["cls"], a["ld_cls"], a["box"], a["ctr2d"], a["ctrness"], a["weight"], None)
 
 
-def raw_call(name, a):
-    l = lib.load()
-    fn = getattr(l, name)
-    fn.restype, fn.argtypes = ctypes.c_int, [lib._CT[c] for c in lib._FOCAL_SIGS[name]]
-    rc = fn(*a)
-    return rc, l.toc3d_last_error().decode()
-
-
 COMMON = [(lib.BF16, {}, "bad dtype"), (lib.F32X3P, {}, "bad dtype"), (99, {}, "bad dtype"),
           (lib.F32, dict(V=0), "must be positive"), (lib.F32, dict(T=0), "must be positive"), (lib.F32, dict(T=-5), "must be positive"),
           (lib.F32, dict(E=0), "must be positive"), (lib.F32, dict(E=48), "embed_dims % 32 != 0"), (lib.F32, dict(E=250), "embed_dims % 32 != 0"),
@@ -219,7 +184,7 @@ COMMON = [(lib.BF16, {}, "bad dtype"), (lib.F32X3P, {}, "bad dtype"), (99, {}, "
     (lib.F32, dict(branches=0), "must be positive"), (lib.F32, dict(ldx=511), "ldx below"), (lib.F32, dict(T=1 << 31), "too many"),
 ])
 def test_gn_stats_refusals(dtype, over, reason):
-    rc, msg = raw_call("toc3d_focal_gn_stats", stats_args(dtype, **over))
+    rc, msg = raw_call(lib._FOCAL_SIGS, "toc3d_focal_gn_stats", stats_args(dtype, **over))
     print(f"{over or dtype}: rc {rc}, {msg!r}")
     assert rc == ERR_ARG and "toc3d_focal_gn_stats" in msg and reason in msg, (rc, msg)
 
@@ -231,6 +196,6 @@ def test_gn_stats_refusals(dtype, over, reason):
     (lib.F32, dict(x=A + 4), "aligned"), (lib.F32, dict(box=A + 8), "aligned"), (lib.F32, dict(location=A + 4), "aligned"), (lib.F32, dict(T=1 << 31), "too many"),
 ])
 def test_heads_refusals(dtype, over, reason):
-    rc, msg = raw_call("toc3d_focal_heads", heads_args(dtype, **over))
+    rc, msg = raw_call(lib._FOCAL_SIGS, "toc3d_focal_heads", heads_args(dtype, **over))
     print(f"{over or dtype}: rc {rc}, {msg!r}")
     assert rc == ERR_ARG and "toc3d_focal_heads" in msg and reason in msg, (rc, msg)

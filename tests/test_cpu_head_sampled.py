@@ -12,40 +12,16 @@ import torch
 
 import sampled_cases as SC
 import toc3d_amd
+from support import A, ERR_ARG, OldLibrary, header_sigs, raw_call
 from toc3d_amd import lib, synth
 
-A = 0x10000                                  # 256-byte aligned stand-in for a device buffer (never dereferenced)
-ERR_ARG = -1
 FRUSTUM, GATHER = "toc3d_head_frustum_inputs_sampled", "toc3d_gather_token_rows"
 
 
 # ---- the ABI ---------------------------------------------------------------------------------------------------------------------------------------------------------
-def parse(txt, sigs):
-    """{name: signature} of the ``int toc3d_*(...)`` declarations that ``sigs`` names (the parser of tests/test_cpu_abi.py)."""
-    found = {}
-    for m in re.finditer(r"\bint\s+(toc3d_\w+)\s*\(([^;]*?)\)\s*;", txt, flags=re.S):
-        name, args = m.group(1), m.group(2)
-        if name not in sigs:
-            continue
-        sig = ""
-        for a in (x.strip() for x in args.split(",")):
-            if "*" in a or "toc3d_stream_t" in a:
-                sig += "p"
-            elif a.startswith("int64_t"):
-                sig += "l"
-            elif a.startswith("int "):
-                sig += "i"
-            elif a.startswith("float "):
-                sig += "f"
-            else:
-                raise AssertionError(f"unparsed parameter {a!r} in {name}")
-        found[name] = sig
-    return found
-
-
 def test_sampled_header_ctypes_table_and_exports_agree():
     raw = open(lib.SAMPLED_HEADER_PATH).read()
-    found = parse(lib.header_text(lib.SAMPLED_HEADER_PATH), lib._SAMPLED_SIGS)
+    found = header_sigs(lib.header_text(lib.SAMPLED_HEADER_PATH), lib._SAMPLED_SIGS)
     print(f"toc3d_sampled.h declares {found}")
     assert found == lib._SAMPLED_SIGS and list(found) == [FRUSTUM, GATHER]
     declared = set(re.findall(r"\b(toc3d_\w+)\s*\(", lib.header_text(lib.SAMPLED_HEADER_PATH)))
@@ -70,10 +46,7 @@ def test_call_binds_the_entry_points_and_an_old_library_is_told_to_rebuild(monke
     for n, sig in lib._SAMPLED_SIGS.items():
         assert getattr(lib.load(), n).argtypes == [lib._CT[c] for c in sig], "bound with the table's argument types (int64 counts, not C ints)"
 
-    class Old:                                # a library from before the header existed: it has none of the symbols
-        def toc3d_last_error(self):
-            return b""
-    monkeypatch.setattr(lib, "_lib", Old())
+    monkeypatch.setattr(lib, "_lib", OldLibrary())
     with pytest.raises(RuntimeError, match=r"toc3d_sampled\.h.*rebuild the library"):
         lib.call(GATHER, *gather_args())
 
@@ -94,14 +67,6 @@ def gather_args(dtype=lib.F32, **o):
     return (dtype, a["src"], a["ld_src"], a["index"], a["B"], a["LEN"], a["K"], a["C"], a["dst"], a["ld_dst"], None)
 
 
-def raw_call(name, a):
-    l = lib.load()
-    fn = getattr(l, name)
-    fn.restype, fn.argtypes = ctypes.c_int, [lib._CT[c] for c in lib._SAMPLED_SIGS[name]]
-    rc = fn(*a)
-    return rc, l.toc3d_last_error().decode()
-
-
 P = lib.F32X3P
 PLANES_RULE = "128-byte boundaries"
 
@@ -118,7 +83,7 @@ PLANES_RULE = "128-byte boundaries"
     (lib.F32, dict(B=1 << 28, K=6000), "too many rows"),
 ])
 def test_frustum_sampled_refusals(dtype, over, reason):
-    rc, msg = raw_call(FRUSTUM, frustum_args(dtype, **over))
+    rc, msg = raw_call(lib._SAMPLED_SIGS, FRUSTUM, frustum_args(dtype, **over))
     print(f"{over or dtype}: rc {rc}, {msg!r}")
     assert rc == ERR_ARG and msg.startswith(FRUSTUM + ":") and reason in msg, (rc, msg)
 
@@ -133,7 +98,7 @@ def test_frustum_sampled_refusals(dtype, over, reason):
     (lib.F32, dict(B=1 << 30, LEN=1 << 20, K=1 << 20), "too many rows"),
 ])
 def test_gather_token_rows_refusals(dtype, over, reason):
-    rc, msg = raw_call(GATHER, gather_args(dtype, **over))
+    rc, msg = raw_call(lib._SAMPLED_SIGS, GATHER, gather_args(dtype, **over))
     print(f"{over or dtype}: rc {rc}, {msg!r}")
     assert rc == ERR_ARG and msg.startswith(GATHER + ":") and reason in msg, (rc, msg)
 

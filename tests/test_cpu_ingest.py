@@ -12,42 +12,18 @@ import torch
 
 import ingest_cases as IC
 import toc3d_amd
+from support import A, ERR_ARG, OldLibrary, header_sigs, raw_call
 from toc3d_amd import lib
 from toc3d_amd import preprocess as P
 
-A = 0x10000                                  # 256-byte aligned stand-in for a device buffer (never dereferenced)
-ERR_ARG = -1
 ENTRY = "toc3d_resize_crop_u8"
 PTRS = ("src", "dst", "coef_h", "bounds_h", "coef_v", "bounds_v")
 
 
 # ---- the ABI ---------------------------------------------------------------------------------------------------------------------------------------------------------
-def parse(txt, sigs):
-    """{name: signature} of the ``int toc3d_*(...)`` declarations that ``sigs`` names (the parser of tests/test_cpu_abi.py)."""
-    found = {}
-    for m in re.finditer(r"\bint\s+(toc3d_\w+)\s*\(([^;]*?)\)\s*;", txt, flags=re.S):
-        name, args = m.group(1), m.group(2)
-        if name not in sigs:
-            continue
-        sig = ""
-        for a in (x.strip() for x in args.split(",")):
-            if "*" in a or "toc3d_stream_t" in a:
-                sig += "p"
-            elif a.startswith("int64_t"):
-                sig += "l"
-            elif a.startswith("int "):
-                sig += "i"
-            elif a.startswith("float "):
-                sig += "f"
-            else:
-                raise AssertionError(f"unparsed parameter {a!r} in {name}")
-        found[name] = sig
-    return found
-
-
 def test_ingest_header_ctypes_table_and_exports_agree():
     raw = open(lib.INGEST_HEADER_PATH).read()
-    found = parse(lib.header_text(lib.INGEST_HEADER_PATH), lib._INGEST_SIGS)
+    found = header_sigs(lib.header_text(lib.INGEST_HEADER_PATH), lib._INGEST_SIGS)
     print(f"toc3d_ingest.h declares {found}")
     assert found == lib._INGEST_SIGS and list(found) == [ENTRY]
     declared = set(re.findall(r"\b(toc3d_\w+)\s*\(", lib.header_text(lib.INGEST_HEADER_PATH)))
@@ -81,23 +57,12 @@ def entry_args(**o):
             a["coef_v"], a["bounds_v"], a["ksize_v"], a["max_span"], None)
 
 
-def raw_call(a):
-    l = lib.load()
-    fn = getattr(l, ENTRY)
-    fn.restype, fn.argtypes = ctypes.c_int, [lib._CT[c] for c in lib._INGEST_SIGS[ENTRY]]
-    rc = fn(*a)
-    return rc, l.toc3d_last_error().decode()
-
-
 def test_call_binds_the_entry_point_and_an_old_library_is_told_to_rebuild(monkeypatch):
     with pytest.raises(RuntimeError, match=r"toc3d_resize_crop_u8 failed \(-1\): toc3d_resize_crop_u8: null buffer"):
         lib.call(ENTRY, *entry_args(src=None))
     assert getattr(lib.load(), ENTRY).argtypes == [lib._CT[c] for c in lib._INGEST_SIGS[ENTRY]], "bound with the table's argument types (int64 counts, not C ints)"
 
-    class Old:                                # a library from before the header existed: it has none of the symbols
-        def toc3d_last_error(self):
-            return b""
-    monkeypatch.setattr(lib, "_lib", Old())
+    monkeypatch.setattr(lib, "_lib", OldLibrary())
     with pytest.raises(RuntimeError, match=r"toc3d_ingest\.h.*rebuild the library"):
         lib.call(ENTRY, *entry_args())
 
@@ -113,7 +78,7 @@ def test_call_binds_the_entry_point_and_an_old_library_is_told_to_rebuild(monkey
     ({}, "host pointer"),                     # every other check passed: the made-up pointers are not device memory
 ])
 def test_entry_point_refusals(over, reason):
-    rc, msg = raw_call(entry_args(**over))
+    rc, msg = raw_call(lib._INGEST_SIGS, ENTRY, entry_args(**over))
     print(f"{over}: rc {rc}, {msg!r}")
     assert rc == ERR_ARG and msg.startswith(ENTRY + ":") and reason in msg, (rc, msg)
 
@@ -124,8 +89,9 @@ def test_real_host_buffers_are_refused_and_left_alone():
     dst = (ctypes.c_ubyte * (4 * 16 * 3))(*([9] * 192))
     tab = (ctypes.c_int32 * 64)(*([1] * 64))
     p = ctypes.addressof
-    rc, msg = raw_call(entry_args(src=p(src), dst=p(dst), src_stride=48, dst_stride=48, V=1, H0=4, W0=16, fH=4, fW=16, coef_h=p(tab), bounds_h=p(tab), ksize_h=1,
-                                  coef_v=p(tab), bounds_v=p(tab), ksize_v=1, max_span=4))
+    args = entry_args(src=p(src), dst=p(dst), src_stride=48, dst_stride=48, V=1, H0=4, W0=16, fH=4, fW=16, coef_h=p(tab), bounds_h=p(tab), ksize_h=1,
+                      coef_v=p(tab), bounds_v=p(tab), ksize_v=1, max_span=4)
+    rc, msg = raw_call(lib._INGEST_SIGS, ENTRY, args)
     print(f"rc {rc}, {msg!r}")
     assert rc == ERR_ARG and "host pointer" in msg
     assert bytes(dst) == bytes([9] * 192) and bytes(src) == bytes([7] * 192) and list(tab) == [1] * 64

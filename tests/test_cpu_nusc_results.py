@@ -16,42 +16,18 @@ import torch.nn as nn
 
 import nusc_results_cases as NC
 import toc3d_amd
-from support import FakeNeck
+from support import A, ERR_ARG, FakeNeck, OldLibrary, header_sigs, raw_call
 from toc3d_amd import lib, synth
 from toc3d_amd import nusc_results as NR
 
-A = 0x10000                                  # 256-byte aligned stand-in for a device buffer (never dereferenced)
-ERR_ARG = -1
 ENTRY = "toc3d_boxes_to_global"
 
 
 # ---- the ABI ---------------------------------------------------------------------------------------------------------------------------------------------------------
-def parse(txt, sigs):
-    found = {}
-    for m in re.finditer(r"\bint\s+(toc3d_\w+)\s*\(([^;]*?)\)\s*;", txt, flags=re.S):
-        name, args = m.group(1), m.group(2)
-        if name not in sigs:
-            continue
-        sig = ""
-        for a in (x.strip() for x in args.split(",")):
-            if "*" in a or "toc3d_stream_t" in a:
-                sig += "p"
-            elif a.startswith("int64_t"):
-                sig += "l"
-            elif a.startswith("int "):
-                sig += "i"
-            elif a.startswith("double "):
-                sig += "d"
-            else:
-                raise AssertionError(f"unparsed parameter {a!r} in {name}")
-        found[name] = sig
-    return found
-
-
 def test_results_header_ctypes_table_and_exports_agree():
     raw = open(lib.RESULTS_HEADER_PATH).read()
     txt = lib.header_text(lib.RESULTS_HEADER_PATH)
-    found = parse(txt, lib._RESULTS_SIGS)
+    found = header_sigs(txt, lib._RESULTS_SIGS)
     print(f"toc3d_results.h declares {found}")
     assert found == lib._RESULTS_SIGS and list(found) == [ENTRY]
     declared = set(re.findall(r"\b(toc3d_\w+)\s*\(", txt))
@@ -104,23 +80,12 @@ def entry_args(**o):
 POINTERS = ("boxes", "scores", "labels", "counts", "poses", "rng", "mov", "still", "rec", "score", "name", "attr", "src", "kept")
 
 
-def raw_call(args):
-    l = lib.load()
-    fn = getattr(l, ENTRY)
-    fn.restype, fn.argtypes = ctypes.c_int, [lib._CT[c] for c in lib._RESULTS_SIGS[ENTRY]]
-    rc = fn(*args)
-    return rc, l.toc3d_last_error().decode()
-
-
 def test_call_binds_the_entry_point_and_an_old_library_is_told_to_rebuild(monkeypatch):
     with pytest.raises(RuntimeError, match=r"toc3d_boxes_to_global failed \(-1\): toc3d_boxes_to_global: null buffer"):
         lib.call(ENTRY, *entry_args(boxes=None))
     assert getattr(lib.load(), ENTRY).argtypes == [lib._CT[c] for c in lib._RESULTS_SIGS[ENTRY]], "bound with the table's argument types"
 
-    class Old:                                # a library from before the header existed: it has none of the symbols
-        def toc3d_last_error(self):
-            return b""
-    monkeypatch.setattr(lib, "_lib", Old())
+    monkeypatch.setattr(lib, "_lib", OldLibrary())
     with pytest.raises(RuntimeError, match=r"toc3d_results\.h.*rebuild the library"):
         lib.call(ENTRY, *entry_args())
 
@@ -137,7 +102,7 @@ def test_call_binds_the_entry_point_and_an_old_library_is_told_to_rebuild(monkey
     (dict(B=65535, ncls=64, box_stride=11, sample_stride=4000), "host pointer"),
 ])
 def test_entry_point_refusals(over, reason):
-    rc, msg = raw_call(entry_args(**over))
+    rc, msg = raw_call(lib._RESULTS_SIGS, ENTRY, entry_args(**over))
     print(f"{over}: rc {rc}, {msg!r}")
     assert rc == ERR_ARG and msg.startswith(ENTRY + ":") and reason in msg, (rc, msg)
 
@@ -146,7 +111,7 @@ def test_no_boxes_is_legal():
     """B == 0 or K == 0: nothing is launched, no pointer is looked at (none is device memory here), and the call succeeds."""
     nulls = {p: None for p in POINTERS}
     for over in (dict(B=0), dict(K=0, sample_stride=0), dict(B=0, **nulls), dict(K=0, sample_stride=0, **nulls)):
-        rc, msg = raw_call(entry_args(**over))
+        rc, msg = raw_call(lib._RESULTS_SIGS, ENTRY, entry_args(**over))
         assert rc == 0, (over, rc, msg)
 
 
@@ -160,8 +125,9 @@ def test_real_host_buffers_are_refused_and_left_alone():
     rec, score = (ctypes.c_double * 24)(*([7.0] * 24)), (ctypes.c_float * 2)(7.0, 7.0)
     name, attr, src = ((ctypes.c_int32 * 2)(7, 7) for _ in range(3))
     kept = (ctypes.c_int64 * 1)(7)
-    rc, msg = raw_call(entry_args(boxes=p(boxes), sample_stride=18, scores=p(scores), labels=p(labels), counts=p(counts), B=1, K=2, poses=p(poses), rng=p(rng), mov=p(mov),
-                                  still=p(still), rec=p(rec), score=p(score), name=p(name), attr=p(attr), src=p(src), kept=p(kept)))
+    args = entry_args(boxes=p(boxes), sample_stride=18, scores=p(scores), labels=p(labels), counts=p(counts), B=1, K=2, poses=p(poses), rng=p(rng), mov=p(mov),
+                      still=p(still), rec=p(rec), score=p(score), name=p(name), attr=p(attr), src=p(src), kept=p(kept))
+    rc, msg = raw_call(lib._RESULTS_SIGS, ENTRY, args)
     print(f"rc {rc}, {msg!r}")
     assert rc == ERR_ARG and "host pointer" in msg
     assert list(rec) == [7.0] * 24 and list(score) == [7.0, 7.0] and list(name) == list(attr) == list(src) == [7, 7] and list(kept) == [7] and list(boxes) == [1.0] * 18

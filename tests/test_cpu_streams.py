@@ -11,44 +11,17 @@ import torch
 import torch.nn as nn
 
 import toc3d_amd
-from support import FakeNeck
+from support import A, ERR_ARG, FakeNeck, OldLibrary, header_sigs, raw_call
 from toc3d_amd import lib, synth
 
-A = 0x10000                                  # 256-byte aligned stand-in for a device buffer (never dereferenced: the checks run before any launch)
-ERR_ARG = -1
 I31 = (1 << 31) - 1
 NAME = "toc3d_score_head_frames"
 
 
 # ---- the ABI ---------------------------------------------------------------------------------------------------------------------------------------------------
-def parse(txt, sigs):
-    """The parser of tests/test_cpu_abi.py::test_ctypes_signatures_match_header: {name: signature} of the ``int toc3d_*(...)`` declarations that ``sigs`` names."""
-    found = {}
-    for m in re.finditer(r"\bint\s+(toc3d_\w+)\s*\(([^;]*?)\)\s*;", txt, flags=re.S):
-        name, args = m.group(1), m.group(2)
-        if name not in sigs:
-            continue
-        sig = ""
-        for a in (x.strip() for x in args.split(",")):
-            if "*" in a or "toc3d_stream_t" in a or "toc3d_plan_t" in a:
-                sig += "p"
-            elif a.startswith("int64_t"):
-                sig += "l"
-            elif a.startswith("uint64_t"):
-                sig += "L"
-            elif a.startswith("int "):
-                sig += "i"
-            elif a.startswith("float "):
-                sig += "f"
-            else:
-                raise AssertionError(f"unparsed parameter {a!r} in {name}")
-        found[name] = sig
-    return found
-
-
 def test_streams_header_and_ctypes_table_agree():
     raw = open(lib.STREAMS_HEADER_PATH).read()
-    found = parse(lib.header_text(lib.STREAMS_HEADER_PATH), lib._STREAMS_SIGS)
+    found = header_sigs(lib.header_text(lib.STREAMS_HEADER_PATH), lib._STREAMS_SIGS)
     print(f"toc3d_streams.h declares {found}")
     assert found == lib._STREAMS_SIGS and list(found) == [NAME]
     assert int(re.search(r"#define\s+TOC3D_STREAMS_ABI\s+(\d+)", raw).group(1)) == lib.STREAMS_ABI == 1
@@ -68,7 +41,7 @@ def test_toc3d_h_and_its_table_are_where_they_were():
     assert l.toc3d_abi_version() == 11 and l.toc3d_abi_minor() == 1
     assert "toc3d_score_head_frames" not in raw and "toc3d_streams" not in raw
     assert not set(lib._STREAMS_SIGS) & set(lib._SIGS)
-    assert parse(lib.header_text(), lib._SIGS) == lib._SIGS, "lib._SIGS is include/toc3d.h one to one"
+    assert header_sigs(lib.header_text(), lib._SIGS) == lib._SIGS, "lib._SIGS is include/toc3d.h one to one"
     print(f"toc3d.h: ABI {lib.ABI_VERSION}.{lib.ABI_MINOR}, {len(lib._SIGS)} signatures; toc3d_streams.h: {len(lib._STREAMS_SIGS)}")
 
 
@@ -78,10 +51,7 @@ def test_call_binds_the_entry_point_and_an_old_library_is_told_to_rebuild(monkey
     fn = getattr(lib.load(), NAME)
     assert fn.argtypes == [lib._CT[c] for c in lib._STREAMS_SIGS[NAME]], "bound with the table's argument types (int64 counts, not C ints)"
 
-    class Old:                                # a library from before the header existed: it has neither symbol
-        def toc3d_last_error(self):
-            return b""
-    monkeypatch.setattr(lib, "_lib", Old())
+    monkeypatch.setattr(lib, "_lib", OldLibrary())
     with pytest.raises(RuntimeError, match="rebuild the library"):
         lib.call(NAME, lib.F32, A, 64, 32, A, A, None, A, 74, 148, A, A, A, None)
 
@@ -96,14 +66,6 @@ def args(dtype=lib.F32, **o):
     return (dtype, a["f"], a["ld"], a["kdim"], a["w"], a["b"], a["gumbel"], a["frame_new"], a["rpf"], a["M"], a["pred"], a["score"], a["mask_out"], None)
 
 
-def raw_call(a):
-    l = lib.load()
-    fn = getattr(l, NAME)
-    fn.restype, fn.argtypes = ctypes.c_int, [lib._CT[c] for c in lib._STREAMS_SIGS[NAME]]
-    rc = fn(*a)
-    return rc, l.toc3d_last_error().decode()
-
-
 @pytest.mark.parametrize("dtype,over,reason", [
     *[(lib.F32, {p: None}, "null buffer") for p in PTRS],
     (lib.F32, dict(rpf=0), "rows_per_frame must be positive"), (lib.BF16, dict(rpf=-74), "rows_per_frame must be positive"),
@@ -115,13 +77,13 @@ def raw_call(a):
     (lib.F32, dict(M=4 * I31 + 4, rpf=4), "too many rows"),
 ])
 def test_score_head_frames_refusals(dtype, over, reason):
-    rc, msg = raw_call(args(dtype, **over))
+    rc, msg = raw_call(lib._STREAMS_SIGS, NAME, args(dtype, **over))
     print(f"{over or dtype}: rc {rc}, {msg!r}")
     assert rc == ERR_ARG and NAME in msg and reason in msg, (rc, msg)
 
 
 def test_score_head_frames_empty_call_returns_before_the_launch():
-    assert raw_call(args(M=0))[0] == 0 and raw_call(args(lib.BF16, M=-74))[0] == 0
+    assert raw_call(lib._STREAMS_SIGS, NAME, args(M=0))[0] == 0 and raw_call(lib._STREAMS_SIGS, NAME, args(lib.BF16, M=-74))[0] == 0
 
 
 # ---- sequencing, on recording fakes (the pattern of tests/test_cpu_detector.py) ----------------------------------------------------------------------------------

@@ -15,44 +15,17 @@ import torch.nn as nn
 
 import toc3d_amd
 import token_vis_cases as TC
-from support import FakeNeck
+from support import A, ERR_ARG, FakeNeck, OldLibrary, header_sigs, raw_call
 from toc3d_amd import configs, lib, synth
 from toc3d_amd import token_vis as TV
 
-A = 0x10000                                  # 256-byte aligned stand-in for a device buffer (never dereferenced)
-ERR_ARG = -1
 ALPHA, RENDER = "toc3d_token_alpha", "toc3d_token_vis_render"
 
 
 # ---- the ABI ---------------------------------------------------------------------------------------------------------------------------------------------------------
-def parse(txt, sigs):
-    """{name: signature} of the ``int toc3d_*(...)`` declarations that ``sigs`` names."""
-    found = {}
-    for m in re.finditer(r"\bint\s+(toc3d_\w+)\s*\(([^;]*?)\)\s*;", txt, flags=re.S):
-        name, args = m.group(1), m.group(2)
-        if name not in sigs:
-            continue
-        sig = ""
-        for a in (x.strip() for x in args.split(",")):
-            if "*" in a or "toc3d_stream_t" in a:
-                sig += "p"
-            elif a.startswith("int64_t"):
-                sig += "l"
-            elif a.startswith("int "):
-                sig += "i"
-            elif a.startswith("float "):
-                sig += "f"
-            elif a.startswith("double "):
-                sig += "d"
-            else:
-                raise AssertionError(f"unparsed parameter {a!r} in {name}")
-        found[name] = sig
-    return found
-
-
 def test_vis_header_ctypes_table_and_exports_agree():
     raw = open(lib.VIS_HEADER_PATH).read()
-    found = parse(lib.header_text(lib.VIS_HEADER_PATH), lib._VIS_SIGS)
+    found = header_sigs(lib.header_text(lib.VIS_HEADER_PATH), lib._VIS_SIGS)
     print(f"toc3d_vis.h declares {found}")
     assert found == lib._VIS_SIGS and list(found) == [ALPHA, RENDER]
     declared = set(re.findall(r"\b(toc3d_\w+)\s*\(", lib.header_text(lib.VIS_HEADER_PATH)))
@@ -98,24 +71,13 @@ def render_args(**o):
             a["ori"], a["rgba"], None)
 
 
-def raw_call(name, args):
-    l = lib.load()
-    fn = getattr(l, name)
-    fn.restype, fn.argtypes = ctypes.c_int, [lib._CT[c] for c in lib._VIS_SIGS[name]]
-    rc = fn(*args)
-    return rc, l.toc3d_last_error().decode()
-
-
 def test_call_binds_the_entry_points_and_an_old_library_is_told_to_rebuild(monkeypatch):
     with pytest.raises(RuntimeError, match=r"toc3d_token_alpha failed \(-1\): toc3d_token_alpha: null buffer"):
         lib.call(ALPHA, *alpha_args(mask=None))
     for name in (ALPHA, RENDER):
         assert getattr(lib.load(), name).argtypes == [lib._CT[c] for c in lib._VIS_SIGS[name]], "bound with the table's argument types"
 
-    class Old:                                # a library from before the header existed: it has none of the symbols
-        def toc3d_last_error(self):
-            return b""
-    monkeypatch.setattr(lib, "_lib", Old())
+    monkeypatch.setattr(lib, "_lib", OldLibrary())
     with pytest.raises(RuntimeError, match=r"toc3d_vis\.h.*rebuild the library"):
         lib.call(RENDER, *render_args())
 
@@ -141,7 +103,7 @@ U8 = dict(src_u8=1, H0=300, W0=790, src_stride=2370)
     (RENDER, {}, "host pointer"), (RENDER, U8, "host pointer"), (RENDER, dict(U8, src=A + 1), "host pointer"),
 ])
 def test_entry_point_refusals(name, over, reason):
-    rc, msg = raw_call(name, (alpha_args if name == ALPHA else render_args)(**over))
+    rc, msg = raw_call(lib._VIS_SIGS, name, (alpha_args if name == ALPHA else render_args)(**over))
     print(f"{name} {over}: rc {rc}, {msg!r}")
     assert rc == ERR_ARG and msg.startswith(name + ":") and reason in msg, (rc, msg)
 
@@ -152,13 +114,13 @@ def test_real_host_buffers_are_refused_and_left_alone():
     mask = (ctypes.c_float * 4)(*([1.0] * 4))
     keep = (ctypes.c_int64 * 4)(*([0] * 4))
     am, ak = (ctypes.c_ubyte * 4)(*([9] * 4)), (ctypes.c_ubyte * 4)(*([9] * 4))
-    rc, msg = raw_call(ALPHA, alpha_args(mask=p(mask), keep=p(keep), keep_stride=2, K=2, V=2, T=2, alpha_mask=p(am), alpha_keep=p(ak)))
+    rc, msg = raw_call(lib._VIS_SIGS, ALPHA, alpha_args(mask=p(mask), keep=p(keep), keep_stride=2, K=2, V=2, T=2, alpha_mask=p(am), alpha_keep=p(ak)))
     print(f"rc {rc}, {msg!r}")
     assert rc == ERR_ARG and "host pointer" in msg and bytes(am) == bytes(ak) == bytes([9] * 4)
     src = (ctypes.c_ubyte * (16 * 16 * 3))(*([7] * 768))
     alpha = (ctypes.c_ubyte * 16)(*([5] * 16))
     ori, rgba = (ctypes.c_ubyte * 768)(*([9] * 768)), (ctypes.c_ubyte * 1024)(*([9] * 1024))
-    rc, msg = raw_call(RENDER, render_args(src=p(src), src_u8=1, src_stride=48, V=1, H0=16, W0=16, H=16, W=16, alpha=p(alpha), A=1, ori=p(ori), rgba=p(rgba)))
+    rc, msg = raw_call(lib._VIS_SIGS, RENDER, render_args(src=p(src), src_u8=1, src_stride=48, V=1, H0=16, W0=16, H=16, W=16, alpha=p(alpha), A=1, ori=p(ori), rgba=p(rgba)))
     print(f"rc {rc}, {msg!r}")
     assert rc == ERR_ARG and "host pointer" in msg
     assert bytes(ori) == bytes([9] * 768) and bytes(rgba) == bytes([9] * 1024) and bytes(src) == bytes([7] * 768) and bytes(alpha) == bytes([5] * 16)

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import lib
-from .token_vis import _three, write_png
+from .token_vis import _image_arg, write_png
 
 __all__ = ["BoxVis", "DEFAULT_PALETTE"]
 _NAME = "toc3d_amd.BoxVis"
@@ -75,27 +75,8 @@ class BoxVis:
         -> ``dict(views (V, H, W, 3), bev (S, S, 3) or None, ...)``: device uint8 tensors, red first, in a per-shape workspace of this object, valid until the next
         call; also the segment tables the pixels were made from (``segf``, ``segi``, ``cidx`` ``(V, n, 12, ...)`` and ``bev_segf``, ``bev_segi``, ``bev_cidx``
         ``(n, 5, ...)``).  Two launches, four with ``bev`` (one and two when ``n == 0``)."""
-        if not isinstance(imgs, torch.Tensor) or not imgs.is_cuda:
-            raise RuntimeError(f"{_NAME}: images must be CUDA/HIP tensors -- the HIP extension is the only compute path")
-        dev = imgs.device
-        u8 = imgs.dtype == torch.uint8
-        if u8:
-            if img_norm_cfg is None:
-                raise ValueError(f"{_NAME}: uint8 frames need img_norm_cfg=dict(mean=..., std=..., to_rgb=...)")
-            img = imgs.reshape(-1, *imgs.shape[-3:]) if imgs.dim() != 4 else imgs
-            if img.shape[3] != 3:
-                raise ValueError(f"{_NAME}: expected uint8 HWC frames (V, H, W, 3), got {tuple(imgs.shape)}")
-            V, H, W = img.shape[:3]
-            if not (img.stride(3) == 1 and img.stride(2) == 3 and img.stride(1) >= 3 * W and img.stride(0) == H * img.stride(1)):
-                img = img.contiguous()
-            kind, stride = 1, img.stride(1)
-        else:
-            img = imgs.reshape(-1, *imgs.shape[-3:]) if imgs.dim() != 4 else imgs
-            if img.dim() != 4 or img.shape[1] != 3:
-                raise ValueError(f"{_NAME}: expected f32 NCHW images (V, 3, H, W), got {tuple(imgs.shape)}")
-            img = img.float().contiguous()
-            V, H, W = img.shape[0], img.shape[2], img.shape[3]
-            kind, stride = 0, 0
+        img, u8, V, H, W, stride, mean, std, to_rgb = _image_arg(imgs, img_norm_cfg, _NAME)
+        dev, kind = imgs.device, int(u8)
         if H > lib.BOXES_MAX_SIDE or W > lib.BOXES_MAX_SIDE:
             raise ValueError(f"{_NAME}: images {H} x {W} exceed {lib.BOXES_MAX_SIDE} (TOC3D_BOXES_MAX_SIDE)")
         box = getattr(boxes, "tensor", boxes)
@@ -118,9 +99,6 @@ class BoxVis:
         if tuple(proj.shape) != (V, 4, 4):
             raise ValueError(f"{_NAME}: lidar2img must be ({V}, 4, 4) or (1, {V}, 4, 4) for {V} views, got {tuple(proj.shape)}")
         proj = proj.to(device=dev, dtype=torch.float32).contiguous()
-        cfg = img_norm_cfg if img_norm_cfg is not None else dict(mean=[0.0, 0.0, 0.0], std=[1.0, 1.0, 1.0], to_rgb=False)
-        mean, std = _three(cfg["mean"], "mean"), _three(cfg["std"], "std")
-        to_rgb = bool(cfg.get("to_rgb", True)) if img_norm_cfg is not None else False
         S = self.bev_size
         key = (V, H, W, str(dev))
         if key not in self._ws:

@@ -238,10 +238,7 @@ __global__ __launch_bounds__(256) void segments_render_kernel(RenderArgs a) {
 #pragma unroll
             for (int k = 0; k < 4; ++k)
 #pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const int at = 3 * k + 2 - c;                        // raw frames hold blue first
-                    b[k][c] = (d[at >> 2] >> (8 * (at & 3))) & 255u;
-                }
+                for (int c = 0; c < 3; ++c) b[k][c] = group_byte(d, 3 * k + 2 - c);          // raw frames hold blue first
         } else {
 #pragma unroll
             for (int k = 0; k < 4; ++k)
@@ -271,11 +268,8 @@ __global__ __launch_bounds__(256) void segments_render_kernel(RenderArgs a) {
             b[k][0] = pal[0]; b[k][1] = pal[1]; b[k][2] = pal[2];
         }
     uint8_t* o = a.out + (((int64_t)v * a.H + y) * a.W + x) * 3;
-    if (OUTW) {                                                          // 12 bytes at a multiple of 12 behind a dword boundary
-        uint32_t* ow = reinterpret_cast<uint32_t*>(o);
-        ow[0] = b[0][0] | b[0][1] << 8 | b[0][2] << 16 | b[1][0] << 24;
-        ow[1] = b[1][1] | b[1][2] << 8 | b[2][0] << 16 | b[2][1] << 24;
-        ow[2] = b[2][2] | b[3][0] << 8 | b[3][1] << 16 | b[3][2] << 24;
+    if (OUTW) {
+        store_group(o, b);
     } else {
 #pragma unroll
         for (int k = 0; k < 4; ++k)
@@ -283,15 +277,6 @@ __global__ __launch_bounds__(256) void segments_render_kernel(RenderArgs a) {
                 o[3 * k] = (uint8_t)b[k][0]; o[3 * k + 1] = (uint8_t)b[k][1]; o[3 * k + 2] = (uint8_t)b[k][2];
             }
     }
-}
-
-bool device_memory(const void* p) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-        (void)hipGetLastError();                                         // an unknown pointer leaves an error behind: not a launch's
-        return false;
-    }
-    return at.type == hipMemoryTypeDevice;
 }
 
 }  // namespace
@@ -318,8 +303,8 @@ int toc3d_box_segments(const float* boxes, int64_t box_stride, const float* scor
     TOC3D_REQUIRE(H <= MAX_SIDE && W <= MAX_SIDE, "toc3d_box_segments: bad dims (H and W at most %d)", MAX_SIDE);
     TOC3D_REQUIRE(V <= 65535 && n <= 0x7fffffffll && V * n <= 0x7fffffffll / EC,"toc3d_box_segments: bad dims (V at most 65535, V * n * 12 below 2^31: one launch's grid)");
     if (n == 0) return TOC3D_OK;
-    TOC3D_REQUIRE(device_memory(boxes) && device_memory(scores) && device_memory(labels) && device_memory(proj) && device_memory(segf) && device_memory(segi) &&
-                      device_memory(cidx),
+    TOC3D_REQUIRE(toc3d_device_memory(boxes) && toc3d_device_memory(scores) && toc3d_device_memory(labels) && toc3d_device_memory(proj) && toc3d_device_memory(segf) && toc3d_device_memory(segi) &&
+                      toc3d_device_memory(cidx),
                   "toc3d_box_segments: host pointer (every buffer must be device memory)");
     const int64_t threads = V * n;
     toc3d_launch(box_segments_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, as_stream(stream), boxes, box_stride, scores, labels, (int)n, score_thr,
@@ -336,7 +321,7 @@ int toc3d_box_segments_bev(const float* boxes, int64_t box_stride, const float* 
     TOC3D_REQUIRE(range_m > 0.f && range_m <= 3.0e38f, "toc3d_box_segments_bev: bad range_m (a positive finite number of metres)");
     TOC3D_REQUIRE(n <= 0x7fffffffll / EB, "toc3d_box_segments_bev: bad dims (n * 5 below 2^31: one launch's grid)");
     if (n == 0) return TOC3D_OK;
-    TOC3D_REQUIRE(device_memory(boxes) && device_memory(scores) && device_memory(labels) && device_memory(segf) && device_memory(segi) && device_memory(cidx),
+    TOC3D_REQUIRE(toc3d_device_memory(boxes) && toc3d_device_memory(scores) && toc3d_device_memory(labels) && toc3d_device_memory(segf) && toc3d_device_memory(segi) && toc3d_device_memory(cidx),
                   "toc3d_box_segments_bev: host pointer (every buffer must be device memory)");
     const float half = 0.5f * (float)S, scale = (float)S / (2.f * range_m);
     toc3d_launch(box_segments_bev_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), boxes, box_stride, scores, labels, (int)n, score_thr,
@@ -362,7 +347,7 @@ int toc3d_segments_render(const void* src, int src_kind, int64_t src_stride, int
     TOC3D_REQUIRE(((uintptr_t)segi & 3) == 0, "toc3d_segments_render: bad alignment (segi starts on a 4-byte boundary)");
     TOC3D_REQUIRE(num_colors >= 1 && num_colors <= 254, "toc3d_segments_render: bad num_colors (1 <= num_colors <= 254: 255 marks a segment that is not drawn)");
     TOC3D_REQUIRE(bg_r >= 0 && bg_r <= 255 && bg_g >= 0 && bg_g <= 255 && bg_b >= 0 && bg_b <= 255, "toc3d_segments_render: bad background (three bytes, 0..255)");
-    TOC3D_REQUIRE(device_memory(out) && device_memory(palette) && (src_kind == 2 || device_memory(src)) && (nseg == 0 || (device_memory(segi) && device_memory(cidx))),
+    TOC3D_REQUIRE(toc3d_device_memory(out) && toc3d_device_memory(palette) && (src_kind == 2 || toc3d_device_memory(src)) && (nseg == 0 || (toc3d_device_memory(segi) && toc3d_device_memory(cidx))),
                   "toc3d_segments_render: host pointer (every buffer must be device memory)");
     RenderArgs a;
     a.src = src; a.segi = segi; a.cidx = cidx; a.palette = palette; a.out = out; a.src_stride = src_stride;

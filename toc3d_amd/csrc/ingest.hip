@@ -163,15 +163,6 @@ __global__ __launch_bounds__(256) void resize_crop_kernel(IngestArgs a) {
     }
 }
 
-bool device_memory(const void* p) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-        (void)hipGetLastError();                                         // an unknown pointer leaves an error behind: not a launch's
-        return false;
-    }
-    return at.type == hipMemoryTypeDevice;
-}
-
 }  // namespace
 
 extern "C" {
@@ -190,7 +181,7 @@ int toc3d_resize_crop_u8(const uint8_t* src, int64_t src_stride, int64_t V, int6
     TOC3D_REQUIRE(ksize_h >= 1 && ksize_h <= KMAX && ksize_v >= 1 && ksize_v <= KMAX,
                   "toc3d_resize_crop_u8: bad ksize (1 <= ksize_h, ksize_v <= %d: the coefficients of a tile must fit the kernel's LDS budget)", KMAX);
     TOC3D_REQUIRE(max_span >= 1 && max_span <= ROWS, "toc3d_resize_crop_u8: bad max_span (1 <= max_span <= %d rows of the intermediate fit the kernel's LDS budget)", ROWS);
-    TOC3D_REQUIRE(device_memory(src) && device_memory(dst) && device_memory(coef_h) && device_memory(bounds_h) && device_memory(coef_v) && device_memory(bounds_v),
+    TOC3D_REQUIRE(toc3d_device_memory(src) && toc3d_device_memory(dst) && toc3d_device_memory(coef_h) && toc3d_device_memory(bounds_h) && toc3d_device_memory(coef_v) && toc3d_device_memory(bounds_v),
                   "toc3d_resize_crop_u8: host pointer (every buffer must be device memory)");
     IngestArgs a;
     a.src = src; a.dst = dst; a.coef_h = coef_h; a.bounds_h = bounds_h; a.coef_v = coef_v; a.bounds_v = bounds_v;

@@ -5,7 +5,7 @@
 #include "../../include/toc3d_vis.h"
 #include "capi.h"
 #include "common.h"
-#include "vis_pixel.h"                                   // sat_u8, mul_then_add, denorm_byte: the image byte, shared with box_vis.hip
+#include "vis_pixel.h"                                   // sat_u8, mul_then_add, denorm_byte: the image byte; group_byte, store_group: four pixels in three dwords -- shared with box_vis.hip
 
 namespace {
 
@@ -83,8 +83,7 @@ __global__ __launch_bounds__(256) void vis_render_wide_kernel(VisArgs a) {
                 for (int q = 0; q < 4; ++q) {
 #pragma unroll
                     for (int c = 0; c < 3; ++c) {
-                        const int lo = 3 * q + c, hi = 3 * q + 2 - c;
-                        const uint32_t plain = (d[lo >> 2] >> (8 * (lo & 3))) & 255u, swapped = (d[hi >> 2] >> (8 * (hi & 3))) & 255u;
+                        const uint32_t plain = group_byte(d, 3 * q + c), swapped = group_byte(d, 3 * q + 2 - c);
                         b[q][c] = a.to_rgb ? swapped : plain;
                     }
                 }
@@ -106,10 +105,7 @@ __global__ __launch_bounds__(256) void vis_render_wide_kernel(VisArgs a) {
         for (int q = 0; q < 4; ++q) pixel_bytes<U8>(a, v, y, x + q, b[q]);
     }
     const int64_t pix = ((int64_t)v * a.H + y) * a.W + x;
-    uint32_t* o = reinterpret_cast<uint32_t*>(a.ori + pix * 3);          // 12 bytes at a multiple of 12 behind a dword boundary
-    o[0] = b[0][0] | b[0][1] << 8 | b[0][2] << 16 | b[1][0] << 24;
-    o[1] = b[1][1] | b[1][2] << 8 | b[2][0] << 16 | b[2][1] << 24;
-    o[2] = b[2][2] | b[3][0] << 8 | b[3][1] << 16 | b[3][2] << 24;
+    store_group(a.ori + pix * 3, b);
     uint32_t rgb[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) rgb[q] = b[q][0] | b[q][1] << 8 | b[q][2] << 16;
@@ -156,15 +152,6 @@ __global__ __launch_bounds__(256) void vis_render_narrow_kernel(VisArgs a) {
     }
 }
 
-bool device_memory(const void* p) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-        (void)hipGetLastError();                                         // an unknown pointer leaves an error behind: not a launch's
-        return false;
-    }
-    return at.type == hipMemoryTypeDevice;
-}
-
 }  // namespace
 
 extern "C" {
@@ -182,7 +169,7 @@ int toc3d_token_alpha(const float* mask, const int64_t* keep, int64_t keep_strid
     TOC3D_REQUIRE(!with_keep || keep || K == 0, "toc3d_token_alpha: null buffer (keep, with alpha_keep given and K > 0)");
     TOC3D_REQUIRE(Kk == 0 || keep_stride >= K, "toc3d_token_alpha: bad strides (keep_stride >= K elements: a stride smaller than a row)");
     TOC3D_REQUIRE(Kk <= 0x7fffffffll, "toc3d_token_alpha: bad dims (K must fit 31 bits)");
-    TOC3D_REQUIRE(device_memory(mask) && device_memory(alpha_mask) && (!with_keep || device_memory(alpha_keep)) && (Kk == 0 || device_memory(keep)),
+    TOC3D_REQUIRE(toc3d_device_memory(mask) && toc3d_device_memory(alpha_mask) && (!with_keep || toc3d_device_memory(alpha_keep)) && (Kk == 0 || toc3d_device_memory(keep)),
                   "toc3d_token_alpha: host pointer (every buffer must be device memory)");
     toc3d_launch(token_alpha_kernel, dim3((unsigned)V), dim3(256), 0, as_stream(stream), mask, Kk ? keep : nullptr, keep_stride, (int)Kk, (int)T, (float)min_alpha,
                  (float)(max_alpha - min_alpha), alpha_mask, alpha_keep);
@@ -204,7 +191,7 @@ int toc3d_token_vis_render(const void* src, int src_u8, int64_t src_stride, int6
     TOC3D_REQUIRE(T <= MAXT, "toc3d_token_vis_render: bad dims ((H/patch)*(W/patch) <= %d = TOC3D_VIS_MAX_TOKENS)", MAXT);
     TOC3D_REQUIRE(!src_u8 || src_stride >= 3 * W0, "toc3d_token_vis_render: bad strides (src_stride >= 3*W0 bytes: a stride smaller than a row)");
     TOC3D_REQUIRE(src_u8 || ((uintptr_t)src & 3) == 0, "toc3d_token_vis_render: bad alignment (an f32 source starts on a 4-byte boundary)");
-    TOC3D_REQUIRE(device_memory(src) && device_memory(alpha) && device_memory(ori) && device_memory(rgba),
+    TOC3D_REQUIRE(toc3d_device_memory(src) && toc3d_device_memory(alpha) && toc3d_device_memory(ori) && toc3d_device_memory(rgba),
                   "toc3d_token_vis_render: host pointer (every buffer must be device memory)");
     VisArgs a;
     a.src = src; a.alpha = alpha; a.ori = ori; a.rgba = rgba; a.src_stride = src_stride;

@@ -14,3 +14,13 @@ TOC3D_DEV float mul_then_add(float x, float s, float m) {
     return p + m;
 }
 TOC3D_DEV uint32_t denorm_byte(float x, float sd, float mu) { return sat_u8(mul_then_add(x, sd, mu)); }
+
+// Four 3-byte pixels as three dwords, the wide form of both kernels.  Byte `at` (0 .. 11) of a group read as d[0 .. 2] ...
+TOC3D_DEV uint32_t group_byte(const uint32_t d[3], int at) { return (d[at >> 2] >> (8 * (at & 3))) & 255u; }
+// ... and the bytes b[pixel][channel] of a group stored: 12 bytes at a multiple of 12 behind a dword boundary.
+TOC3D_DEV void store_group(uint8_t* o, const uint32_t b[4][3]) {
+    uint32_t* ow = reinterpret_cast<uint32_t*>(o);
+    ow[0] = b[0][0] | b[0][1] << 8 | b[0][2] << 16 | b[1][0] << 24;
+    ow[1] = b[1][1] | b[1][2] << 8 | b[2][0] << 16 | b[2][1] << 24;
+    ow[2] = b[2][2] | b[3][0] << 8 | b[3][1] << 16 | b[3][2] << 24;
+}

@@ -151,7 +151,8 @@ STREAMS_ABI = 1                 # == TOC3D_STREAMS_ABI
 _STREAMS_SIGS = {
     "toc3d_score_head_frames": "ipllppppllpppp",
 }
-# include/toc3d_focal.h (the 2-D auxiliary head, toc3d_amd.FocalHead): a side header as toc3d_streams.h is, for the same reason, bound the same way
+# include/toc3d_focal.h (the 2-D auxiliary head, toc3d_amd.FocalHead): a side header as toc3d_streams.h is, for the same reason, bound the same way -- every side
+# header is its path, its ABI number, its constants and its table here, and one row of SIDES below; nothing else is written per header
 FOCAL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "toc3d_focal.h")
 FOCAL_ABI = 1                   # == TOC3D_FOCAL_ABI
 _FOCAL_SIGS = {
@@ -204,6 +205,20 @@ RESULTS_MAX_BOXES, RESULTS_MAX_CLASSES, RESULTS_REC = 2048, 64, 12      # == TOC
 _RESULTS_SIGS = {
     "toc3d_boxes_to_global": "pll" + "ppp" + "ll" + "i" + "p" + "ppp" + "l" + "d" + "pppppp" + "p",
 }
+
+# The side headers, one row each: key -> (header, the symbol that reports its ABI, the ABI this package binds, its signature table).  _bind_side() and call() read
+# nothing else, so A NEW SIDE HEADER IS ONE NEW ROW HERE plus its constants above (tests/test_cpu_abi.py holds every row against its header).
+SIDES = {
+    "streams": (STREAMS_HEADER_PATH, "toc3d_streams_abi", STREAMS_ABI, _STREAMS_SIGS),
+    "focal": (FOCAL_HEADER_PATH, "toc3d_focal_abi", FOCAL_ABI, _FOCAL_SIGS),
+    "sampled": (SAMPLED_HEADER_PATH, "toc3d_sampled_abi", SAMPLED_ABI, _SAMPLED_SIGS),
+    "select": (SELECT_HEADER_PATH, "toc3d_select_abi", SELECT_ABI, _SELECT_SIGS),
+    "ingest": (INGEST_HEADER_PATH, "toc3d_ingest_abi", INGEST_ABI, _INGEST_SIGS),
+    "vis": (VIS_HEADER_PATH, "toc3d_vis_abi", VIS_ABI, _VIS_SIGS),
+    "boxes": (BOXES_HEADER_PATH, "toc3d_boxes_abi", BOXES_ABI, _BOXES_SIGS),
+    "results": (RESULTS_HEADER_PATH, "toc3d_results_abi", RESULTS_ABI, _RESULTS_SIGS),
+}
+_SIDE_OF = {name: key for key, row in SIDES.items() for name in row[3]}       # entry point -> its side: call()'s one lookup
 
 _lib = None
 
@@ -273,161 +288,31 @@ def _conv(a):
     return a
 
 
-def _bind_streams(lib):
-    """The entry points of include/toc3d_streams.h, bound when the first of them is called."""
+def _bind_side(lib, key):
+    """The entry points of one side header (a row of SIDES), bound when the first of them is called.  The mark is left on the library object: another object in its
+    place (an older build) is asked for its own toc3d_<key>_abi."""
+    path, abi_fn, want, sigs = SIDES[key]
     try:
-        lib.toc3d_streams_abi.restype = _I
-        abi = lib.toc3d_streams_abi()
-        fns = {name: getattr(lib, name) for name in _STREAMS_SIGS}
+        getattr(lib, abi_fn).restype = _I
+        abi = getattr(lib, abi_fn)()
+        fns = {name: getattr(lib, name) for name in sigs}
     except AttributeError:
         abi, fns = None, {}
-    if abi != STREAMS_ABI:
-        raise RuntimeError(f"{LIB_PATH} reports streams ABI {abi}, this package binds {STREAMS_ABI} (include/toc3d_streams.h): "
+    if abi != want:
+        raise RuntimeError(f"{LIB_PATH} reports {key} ABI {abi}, this package binds {want} (include/{os.path.basename(path)}): "
                            "rebuild the library (`make -C toc3d_amd/csrc`)")
     for name, fn in fns.items():
         fn.restype = _I
-        fn.argtypes = [_CT[c] for c in _STREAMS_SIGS[name]]
-    lib._toc3d_streams_bound = True
-
-
-def _bind_focal(lib):
-    """The entry points of include/toc3d_focal.h, bound when the first of them is called."""
-    try:
-        lib.toc3d_focal_abi.restype = _I
-        abi = lib.toc3d_focal_abi()
-        fns = {name: getattr(lib, name) for name in _FOCAL_SIGS}
-    except AttributeError:
-        abi, fns = None, {}
-    if abi != FOCAL_ABI:
-        raise RuntimeError(f"{LIB_PATH} reports focal ABI {abi}, this package binds {FOCAL_ABI} (include/toc3d_focal.h): "
-                           "rebuild the library (`make -C toc3d_amd/csrc`)")
-    for name, fn in fns.items():
-        fn.restype = _I
-        fn.argtypes = [_CT[c] for c in _FOCAL_SIGS[name]]
-    lib._toc3d_focal_bound = True
-
-
-def _bind_sampled(lib):
-    """The entry points of include/toc3d_sampled.h, bound when the first of them is called."""
-    try:
-        lib.toc3d_sampled_abi.restype = _I
-        abi = lib.toc3d_sampled_abi()
-        fns = {name: getattr(lib, name) for name in _SAMPLED_SIGS}
-    except AttributeError:
-        abi, fns = None, {}
-    if abi != SAMPLED_ABI:
-        raise RuntimeError(f"{LIB_PATH} reports sampled ABI {abi}, this package binds {SAMPLED_ABI} (include/toc3d_sampled.h): "
-                           "rebuild the library (`make -C toc3d_amd/csrc`)")
-    for name, fn in fns.items():
-        fn.restype = _I
-        fn.argtypes = [_CT[c] for c in _SAMPLED_SIGS[name]]
-    lib._toc3d_sampled_bound = True
-
-
-def _bind_select(lib):
-    """The entry point of include/toc3d_select.h, bound when it is first called."""
-    try:
-        lib.toc3d_select_abi.restype = _I
-        abi = lib.toc3d_select_abi()
-        fns = {name: getattr(lib, name) for name in _SELECT_SIGS}
-    except AttributeError:
-        abi, fns = None, {}
-    if abi != SELECT_ABI:
-        raise RuntimeError(f"{LIB_PATH} reports select ABI {abi}, this package binds {SELECT_ABI} (include/toc3d_select.h): "
-                           "rebuild the library (`make -C toc3d_amd/csrc`)")
-    for name, fn in fns.items():
-        fn.restype = _I
-        fn.argtypes = [_CT[c] for c in _SELECT_SIGS[name]]
-    lib._toc3d_select_bound = True
-
-
-def _bind_ingest(lib):
-    """The entry point of include/toc3d_ingest.h, bound when it is first called."""
-    try:
-        lib.toc3d_ingest_abi.restype = _I
-        abi = lib.toc3d_ingest_abi()
-        fns = {name: getattr(lib, name) for name in _INGEST_SIGS}
-    except AttributeError:
-        abi, fns = None, {}
-    if abi != INGEST_ABI:
-        raise RuntimeError(f"{LIB_PATH} reports ingest ABI {abi}, this package binds {INGEST_ABI} (include/toc3d_ingest.h): "
-                           "rebuild the library (`make -C toc3d_amd/csrc`)")
-    for name, fn in fns.items():
-        fn.restype = _I
-        fn.argtypes = [_CT[c] for c in _INGEST_SIGS[name]]
-    lib._toc3d_ingest_bound = True
-
-
-def _bind_vis(lib):
-    """The entry points of include/toc3d_vis.h, bound when the first of them is called."""
-    try:
-        lib.toc3d_vis_abi.restype = _I
-        abi = lib.toc3d_vis_abi()
-        fns = {name: getattr(lib, name) for name in _VIS_SIGS}
-    except AttributeError:
-        abi, fns = None, {}
-    if abi != VIS_ABI:
-        raise RuntimeError(f"{LIB_PATH} reports vis ABI {abi}, this package binds {VIS_ABI} (include/toc3d_vis.h): "
-                           "rebuild the library (`make -C toc3d_amd/csrc`)")
-    for name, fn in fns.items():
-        fn.restype = _I
-        fn.argtypes = [_CT[c] for c in _VIS_SIGS[name]]
-    lib._toc3d_vis_bound = True
-
-
-def _bind_boxes(lib):
-    """The entry points of include/toc3d_boxes.h, bound when the first of them is called."""
-    try:
-        lib.toc3d_boxes_abi.restype = _I
-        abi = lib.toc3d_boxes_abi()
-        fns = {name: getattr(lib, name) for name in _BOXES_SIGS}
-    except AttributeError:
-        abi, fns = None, {}
-    if abi != BOXES_ABI:
-        raise RuntimeError(f"{LIB_PATH} reports boxes ABI {abi}, this package binds {BOXES_ABI} (include/toc3d_boxes.h): "
-                           "rebuild the library (`make -C toc3d_amd/csrc`)")
-    for name, fn in fns.items():
-        fn.restype = _I
-        fn.argtypes = [_CT[c] for c in _BOXES_SIGS[name]]
-    lib._toc3d_boxes_bound = True
-
-
-def _bind_results(lib):
-    """The entry point of include/toc3d_results.h, bound when it is first called."""
-    try:
-        lib.toc3d_results_abi.restype = _I
-        abi = lib.toc3d_results_abi()
-        fns = {name: getattr(lib, name) for name in _RESULTS_SIGS}
-    except AttributeError:
-        abi, fns = None, {}
-    if abi != RESULTS_ABI:
-        raise RuntimeError(f"{LIB_PATH} reports results ABI {abi}, this package binds {RESULTS_ABI} (include/toc3d_results.h): "
-                           "rebuild the library (`make -C toc3d_amd/csrc`)")
-    for name, fn in fns.items():
-        fn.restype = _I
-        fn.argtypes = [_CT[c] for c in _RESULTS_SIGS[name]]
-    lib._toc3d_results_bound = True
+        fn.argtypes = [_CT[c] for c in sigs[name]]
+    setattr(lib, f"_toc3d_{key}_bound", True)
 
 
 def call(name: str, *args):
     """Invoke a C-ABI entry point; tensors are passed as device pointers; raises on a non-zero return."""
     lib = load()
-    if name in _STREAMS_SIGS and not getattr(lib, "_toc3d_streams_bound", False):
-        _bind_streams(lib)
-    if name in _FOCAL_SIGS and not getattr(lib, "_toc3d_focal_bound", False):
-        _bind_focal(lib)
-    if name in _SAMPLED_SIGS and not getattr(lib, "_toc3d_sampled_bound", False):
-        _bind_sampled(lib)
-    if name in _SELECT_SIGS and not getattr(lib, "_toc3d_select_bound", False):
-        _bind_select(lib)
-    if name in _INGEST_SIGS and not getattr(lib, "_toc3d_ingest_bound", False):
-        _bind_ingest(lib)
-    if name in _VIS_SIGS and not getattr(lib, "_toc3d_vis_bound", False):
-        _bind_vis(lib)
-    if name in _BOXES_SIGS and not getattr(lib, "_toc3d_boxes_bound", False):
-        _bind_boxes(lib)
-    if name in _RESULTS_SIGS and not getattr(lib, "_toc3d_results_bound", False):
-        _bind_results(lib)
+    key = _SIDE_OF.get(name)
+    if key is not None and not getattr(lib, f"_toc3d_{key}_bound", False):
+        _bind_side(lib, key)
     rc = getattr(lib, name)(*[_conv(a) for a in args])
     if rc != 0:
         raise RuntimeError(f"{name} failed ({rc}): {lib.toc3d_last_error().decode()}")

@@ -58,14 +58,44 @@ def write_png(path: str, arr: np.ndarray, blue_first: bool = True):
         f.write(encode_png(arr))
 
 
-def _three(v, what):
+def _three(v, what, name):
     """mean / std of an img_norm_cfg -- a list, a numpy array or a tensor -- as three Python floats (the entry point takes them as float32)."""
     if isinstance(v, torch.Tensor):
         v = v.detach().cpu().numpy()
     v = np.asarray(v, dtype=np.float64).reshape(-1)
     if v.size != 3:
-        raise ValueError(f"{_NAME}: img_norm_cfg['{what}'] must have 3 entries, got {v.size}")
+        raise ValueError(f"{name}: img_norm_cfg['{what}'] must have 3 entries, got {v.size}")
     return [float(x) for x in v]
+
+
+def _image_arg(imgs, img_norm_cfg, name):
+    """The image argument of ``TokenVis.render`` and ``BoxVis.render`` (``name``: the caller, for the messages): f32 NCHW images or uint8 HWC frames on the
+    device, leading dimensions flattened.  -> ``(img, u8, V, H0, W0, stride, mean, std, to_rgb)``: the tensor the entry point reads (f32 contiguous; uint8 as it
+    came where its rows are dense pixels at one stride, else contiguous), the source size, the row stride in bytes (0 for f32) and what ``img_norm_cfg`` says
+    (None: the image's own values, channels as they are)."""
+    if not isinstance(imgs, torch.Tensor) or not imgs.is_cuda:
+        raise RuntimeError(f"{name}: images must be CUDA/HIP tensors -- the HIP extension is the only compute path")
+    u8 = imgs.dtype == torch.uint8
+    img = imgs.reshape(-1, *imgs.shape[-3:]) if imgs.dim() != 4 else imgs
+    if u8:
+        if img_norm_cfg is None:
+            raise ValueError(f"{name}: uint8 frames need img_norm_cfg=dict(mean=..., std=..., to_rgb=...)")
+        if img.shape[3] != 3:
+            raise ValueError(f"{name}: expected uint8 HWC frames (V, H, W, 3), got {tuple(imgs.shape)}")
+        V, H0, W0 = img.shape[:3]
+        if not (img.stride(3) == 1 and img.stride(2) == 3 and img.stride(1) >= 3 * W0 and img.stride(0) == H0 * img.stride(1)):
+            img = img.contiguous()
+        stride = img.stride(1)
+    else:
+        if img.dim() != 4 or img.shape[1] != 3:
+            raise ValueError(f"{name}: expected f32 NCHW images (V, 3, H, W), got {tuple(imgs.shape)}")
+        img = img.float().contiguous()
+        V, H0, W0 = img.shape[0], img.shape[2], img.shape[3]
+        stride = 0
+    cfg = img_norm_cfg if img_norm_cfg is not None else dict(mean=[0.0, 0.0, 0.0], std=[1.0, 1.0, 1.0], to_rgb=False)
+    mean, std = _three(cfg["mean"], "mean", name), _three(cfg["std"], "std", name)
+    to_rgb = bool(cfg.get("to_rgb", True)) if img_norm_cfg is not None else False
+    return img, u8, V, H0, W0, stride, mean, std, to_rgb
 
 
 class TokenVis:
@@ -89,8 +119,7 @@ class TokenVis:
         ``drop_idxes``: its lists of ``(V, K_s)`` int64 indices (``drop_idxes`` is only asked whether it is there, as in the reference).
         -> ``dict(ori (V, H, W, 3), masks (L, V, H, W, 4), keepidx (L, V, H, W, 4) or None, to_rgb)``: device uint8 tensors in a per-shape workspace of this
         object, valid until the next call; channel order as the reference's arrays (what ``imdenormalize(to_bgr=False)`` leaves).  ``L + 1`` launches."""
-        if not isinstance(input_imgs, torch.Tensor) or not input_imgs.is_cuda:
-            raise RuntimeError(f"{_NAME}: images must be CUDA/HIP tensors -- the HIP extension is the only compute path")
+        img, u8, V, H0, W0, stride, mean, std, to_rgb = _image_arg(input_imgs, img_norm_cfg, _NAME)
         masks = list(masks)
         L, p = len(masks), self.patch_size
         if L == 0:
@@ -99,24 +128,6 @@ class TokenVis:
         keeps = list(keep_idxes) if with_keep else []
         if with_keep and len(keeps) != L:
             raise ValueError(f"{_NAME}: {len(keeps)} keep lists for {L} masks")
-        u8 = input_imgs.dtype == torch.uint8
-        if u8:
-            if img_norm_cfg is None:
-                raise ValueError(f"{_NAME}: uint8 frames need img_norm_cfg=dict(mean=..., std=..., to_rgb=...)")
-            img = input_imgs.reshape(-1, *input_imgs.shape[-3:]) if input_imgs.dim() != 4 else input_imgs
-            if img.shape[3] != 3:
-                raise ValueError(f"{_NAME}: expected uint8 HWC frames (V, H0, W0, 3), got {tuple(input_imgs.shape)}")
-            V, H0, W0 = img.shape[:3]
-            if not (img.stride(3) == 1 and img.stride(2) == 3 and img.stride(1) >= 3 * W0 and img.stride(0) == H0 * img.stride(1)):
-                img = img.contiguous()
-            stride = img.stride(1)
-        else:
-            img = input_imgs.reshape(-1, *input_imgs.shape[-3:]) if input_imgs.dim() != 4 else input_imgs
-            if img.shape[1] != 3:
-                raise ValueError(f"{_NAME}: expected f32 NCHW images (V, 3, H, W), got {tuple(input_imgs.shape)}")
-            img = img.float().contiguous()
-            V, H0, W0 = img.shape[0], img.shape[2], img.shape[3]
-            stride = 0
         m0 = masks[0]
         if m0.dim() != 4 or m0.shape[0] != V or m0.shape[3] != 1:
             raise ValueError(f"{_NAME}: expected masks (V={V}, hp, wp, 1), got {tuple(m0.shape)}")
@@ -128,9 +139,6 @@ class TokenVis:
             raise ValueError(f"{_NAME}: images {H0} x {W0} are not the {hp} x {wp} token grid at patch {p}")
         if T > lib.VIS_MAX_TOKENS:
             raise ValueError(f"{_NAME}: {T} tokens a view > {lib.VIS_MAX_TOKENS} (TOC3D_VIS_MAX_TOKENS)")
-        cfg = img_norm_cfg if img_norm_cfg is not None else dict(mean=[0.0, 0.0, 0.0], std=[1.0, 1.0, 1.0], to_rgb=False)
-        mean, std = _three(cfg["mean"], "mean"), _three(cfg["std"], "std")
-        to_rgb = bool(cfg.get("to_rgb", True)) if img_norm_cfg is not None else False
         A, dev = (2 * L if with_keep else L), img.device
         key = (V, H, W, A, str(dev))
         if key not in self._ws:
