@@ -202,15 +202,18 @@ int toc3d_pack_weight_lnfold(int dtype, const float* w3, const float* gamma, con
  * dst == src converts in place (equal leading dims). */
 int toc3d_x3_planes(const float* src, int64_t ld_src, float* dst, int64_t ld_dst, int64_t rows, int64_t K, toc3d_stream_t stream);
 
-/* f32 [N, K] state-dict weight -> act [Np, Kp], zero padded (Np multiple of 128, Kp multiple of 64). */
+/* f32 [N, K] state-dict weight -> act [Np, Kp], zero padded (Np multiple of 128, Kp multiple of 64).  Refused: Np or Kp above 2^31 - 1 (and with them
+ * N and K). */
 int toc3d_pack_weight(int dtype, const float* w, int64_t N, int64_t K, void* out, int64_t Np, int64_t Kp, toc3d_stream_t stream);
 /* mlp.w1 / mlp.w2 (eva_vit.py:35-36) -> interleaved [2*Hp, Kp] + bias [2*Hp]; packed row 32b+i = w1 row 16b+i,
- * row 32b+16+i = w2 row 16b+i. */
+ * row 32b+16+i = w2 row 16b+i; units from Hd on and columns from K on are zero, in the weights and in the bias.  Refused: Hd <= 0 or K <= 0;
+ * 2 * Hp or Kp above 2^31 - 1 (and with them Hd and K). */
 int toc3d_pack_swiglu(int dtype, const float* w1, const float* w2, const float* b1, const float* b2, int64_t Hd, int64_t K,
                       void* out_w, float* out_b, int64_t Hp, int64_t Kp, toc3d_stream_t stream);
 
 /* PatchEmbed input side (backbones/eva_utils.py:283-287): img f32 NCHW [V, Cin, H, W] -> rows
- * [V*(H/p)*(W/p), ldo] act with column order (ch, py, px) == flattened Conv2d weight. */
+ * [V*(H/p)*(W/p), ldo] act with column order (ch, py, px) == flattened Conv2d weight; columns [Cin*p*p, ldo) are not written.  Refused: V, Cin, H
+ * or W <= 0 (there is no empty call); V, H, W or Cin*p*p above 2^31 - 1, or an image of more than 2^63 - 1 bytes. */
 int toc3d_im2col_patches(int dtype, const float* img, void* out, int64_t ldo, int64_t V, int64_t Cin, int64_t H, int64_t W,
                          int64_t patch, toc3d_stream_t stream);
 
@@ -220,7 +223,9 @@ int toc3d_im2col_patches(int dtype, const float* img, void* out, int64_t ldo, in
  *   channel flip if to_rgb, then fl32(fl32(x - mean) * fl32(1/std))) + PadMultiViewImage (transform_3d.py:38-50: zeros bottom /
  *   right up to [Hp, Wp]) + the HWC->CHW transpose of DefaultFormatBundle (mmdet3d/datasets/pipelines/formating.py:42-47)
  *   -> out f32 NCHW [V, 3, Hp, Wp], i.e. the tensor ToC3DEVAViT.forward receives.
- * toc3d_im2col_patches_u8 = the same fused into toc3d_im2col_patches: rows [V*(Hp/p)*(Wp/p), ldo], identical values. */
+ * toc3d_im2col_patches_u8 = the same fused into toc3d_im2col_patches: rows [V*(Hp/p)*(Wp/p), ldo], identical values.
+ * Both refuse V, Hp or Wp above 2^31 - 1 (and with them H, W and the patch) and a padded image of more than 2^63 - 1 bytes; toc3d_normalize_images
+ * stores four pixels at once and refuses an `out` that is not 16-byte aligned. */
 int toc3d_normalize_images(const uint8_t* img, int64_t V, int64_t H, int64_t W, const float* mean3, const float* std3, int to_rgb,
                            float* out, int64_t Hp, int64_t Wp, toc3d_stream_t stream);
 int toc3d_im2col_patches_u8(int dtype, const uint8_t* img, int64_t V, int64_t H, int64_t W, const float* mean3, const float* std3,
@@ -450,16 +455,18 @@ int toc3d_score_head(int dtype, const void* f, int64_t ld, int64_t kdim, const f
 /* ---------------------------------------------------------------------------------------------------
  * Layout helpers at the module boundary.
  * toc3d_nhwc_to_nchw: x f32 [V, T, C] -> out f32 [V, C, T] (materialises the reference's permute(0,3,1,2),
- *   toc3d_eva_vit.py:294, for consumers that need contiguous NCHW).
+ *   toc3d_eva_vit.py:294, for consumers that need contiguous NCHW).  Refused: V above 65535 or C above 65535 * 32 (V and ceil(C / 32) are grid
+ *   axes), T above 2^31 - 32 (tokens are counted in 32 bits, in whole tiles of 32).
  * toc3d_im2col_3x3: CPFPN's 3x3 conv (necks/cp_fpn.py:124-133) as a GEMM: x f32 [V, h, w, C] (NHWC) ->
- *   rows [V*h*w, 9*C] act with column order (ky, kx, c); the weight is packed to match by the host.
+ *   rows [V*h*w, 9*C] act with column order (ky, kx, c); the weight is packed to match by the host; columns [9*C, ldo) are not written.  V, h or
+ *   w == 0 is an empty call (TOC3D_OK, no launch).  Refused: a negative V, h or w; C <= 0 or 9*C above 2^31 - 1; V*h*w above 2^31 - 1.
  */
 int toc3d_nhwc_to_nchw(const float* x, float* out, int64_t V, int64_t T, int64_t C, toc3d_stream_t stream);
 /* CPFPN's 3x3 conv (pad 1, necks/cp_fpn.py:124-133) as an IMPLICIT GEMM: x act [V, h, w, C] (NHWC, C a multiple of 64), W act packed
  * [ceil128(Cout), 9*C] in (ky, kx, c) column order (the layout toc3d_im2col_3x3 produces rows for), bias f32 [Cout] or NULL ->
  * out f32 [V*h*w, ldo].  The GEMM's operand loader gathers the nine neighbours of every pixel itself (out-of-image taps read `zeros`, a
  * device buffer of >= 16 zero bytes), so the [V*h*w, 9*C] im2col matrix is never written or read; same K order as toc3d_im2col_3x3 +
- * toc3d_linear, hence the same bits.  `variant` as toc3d_linear_ex (phased variants excluded). */
+ * toc3d_linear, hence the same bits.  `variant` as toc3d_linear_ex (phased variants excluded).  Refused: V*h*w above 2^31 - 1. */
 int toc3d_conv3x3_nhwc(int dtype, int variant, const void* x, int64_t C, const void* W, int64_t ldw, const float* bias, float* out, int64_t ldo,
                        int64_t V, int64_t h, int64_t w, int64_t Cout, const void* zeros, toc3d_stream_t stream);
 int toc3d_im2col_3x3(int dtype, const float* x, void* out, int64_t ldo, int64_t V, int64_t h, int64_t w, int64_t C,

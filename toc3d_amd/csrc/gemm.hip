@@ -28,6 +28,8 @@ thread_local bool g_bad_variant = false;               // variant cannot serve t
 
 namespace {
 
+constexpr int64_t I32_MAX = 0x7fffffffLL;              // the layout kernels below decode their dimensions in 32 bits
+
 int launch_gemm(int is_bf16, int epi, int variant, const GemmArgs& a, hipStream_t s) {
     switch (epi) {
         case TOC3D_EPI_BIAS: case TOC3D_EPI_GELU: case TOC3D_EPI_BIAS_RELU: case TOC3D_EPI_CONV3X3: return toc3d_gemm_launch_plain(is_bf16, epi, variant, a, s);
@@ -220,6 +222,9 @@ int toc3d_normalize_images(const uint8_t* img, int64_t V, int64_t H, int64_t W, 
                            float* out, int64_t Hp, int64_t Wp, toc3d_stream_t stream) {
     TOC3D_REQUIRE(img && out && mean3 && std3, "toc3d_normalize_images: null buffer");
     TOC3D_REQUIRE(V > 0 && H > 0 && W > 0 && Hp >= H && Wp >= W && Wp % 4 == 0, "toc3d_normalize_images: bad dims (Wp must be a multiple of 4)");
+    TOC3D_REQUIRE(V <= I32_MAX && Hp <= I32_MAX && Wp <= I32_MAX && V * Hp <= INT64_MAX / (12 * Wp),
+                  "toc3d_normalize_images: dimension too large (the kernel decodes V, H, W, Hp, Wp in 32 bits; the output's bytes in 64)");
+    TOC3D_REQUIRE(((uintptr_t)out % 16) == 0, "toc3d_normalize_images: out must be 16-byte aligned (four pixels leave in one store)");
     TOC3D_REQUIRE(std3[0] != 0.f && std3[1] != 0.f && std3[2] != 0.f, "toc3d_normalize_images: zero std");
     const int64_t total = V * Hp * (Wp / 4);
     const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
@@ -234,6 +239,8 @@ int toc3d_im2col_patches_u8(int dtype, const uint8_t* img, int64_t V, int64_t H,
     TOC3D_REQUIRE(img && out && mean3 && std3, "toc3d_im2col_patches_u8: null buffer");
     TOC3D_REQUIRE(V > 0 && H > 0 && W > 0 && patch > 0 && patch % 4 == 0 && Hp >= H && Wp >= W && Hp % patch == 0 && Wp % patch == 0,
                   "toc3d_im2col_patches_u8: bad dims (padded size must be a multiple of the patch, patch a multiple of 4)");
+    TOC3D_REQUIRE(V <= I32_MAX && Hp <= I32_MAX && Wp <= I32_MAX && V * Hp <= INT64_MAX / (12 * Wp),
+                  "toc3d_im2col_patches_u8: dimension too large (the kernel decodes V, H, W, Hp, Wp, patch in 32 bits; the image's bytes in 64)");
     TOC3D_REQUIRE(ldo >= 3 * patch * patch, "toc3d_im2col_patches_u8: ldo < 3*patch*patch");
     TOC3D_REQUIRE(std3[0] != 0.f && std3[1] != 0.f && std3[2] != 0.f, "toc3d_im2col_patches_u8: zero std");
     const int64_t total = V * (Hp / patch) * (Wp / patch) * patch * (patch / 4);
@@ -399,6 +406,7 @@ int toc3d_conv3x3_nhwc(int dtype, int variant, const void* x, int64_t C, const v
                        int64_t V, int64_t h, int64_t w, int64_t Cout, const void* zeros, toc3d_stream_t stream) {
     TOC3D_REQUIRE(x && W && out && zeros && V > 0 && h > 0 && w > 0 && h < 32768 && w < 65536, "toc3d_conv3x3_nhwc: bad arguments");
     TOC3D_REQUIRE(C % 64 == 0, "toc3d_conv3x3_nhwc: the channel count must be a multiple of 64 (one K-tile never straddles two taps)");
+    TOC3D_REQUIRE(V <= I32_MAX / (h * w), "toc3d_conv3x3_nhwc: too many rows (V * h * w is counted in 32 bits)");
     return toc3d_linear_fused(dtype, TOC3D_EPI_CONV3X3, variant, x, C, W, ldw, bias, out, ldo, nullptr, 0, 0, nullptr, nullptr, V * h * w, Cout, 9 * C, 0,
                               nullptr, 0, nullptr, 0, nullptr, 0, 0.f, const_cast<void*>(zeros), (h << 32) | w, nullptr, stream);
 }
@@ -461,6 +469,7 @@ int toc3d_x3_planes(const float* src, int64_t ld_src, float* dst, int64_t ld_dst
 
 int toc3d_pack_weight(int dtype, const float* w, int64_t N, int64_t K, void* out, int64_t Np, int64_t Kp, toc3d_stream_t stream) {
     TOC3D_REQUIRE(w && out && Np >= N && Kp >= K && N > 0 && K > 0, "toc3d_pack_weight: bad arguments");
+    TOC3D_REQUIRE(Np <= I32_MAX && Kp <= I32_MAX, "toc3d_pack_weight: dimension too large (the kernel decodes N, K, Np, Kp in 32 bits)");
     const int blocks = (int)((Np * Kp + 255) / 256 < 4096 ? (Np * Kp + 255) / 256 : 4096);
     if (dtype == TOC3D_BF16)
         toc3d_launch(pack_weight_kernel<bf16_t>, dim3(blocks), dim3(256), 0, as_stream(stream), w, (int)N, (int)K, (bf16_t*)out, (int)Np, (int)Kp);
@@ -499,7 +508,9 @@ int toc3d_pack_swiglu_lnfold(int dtype, const float* w1, const float* w2, const 
 int toc3d_pack_swiglu(int dtype, const float* w1, const float* w2, const float* b1, const float* b2, int64_t Hd, int64_t K,
                       void* out_w, float* out_b, int64_t Hp, int64_t Kp, toc3d_stream_t stream) {
     TOC3D_REQUIRE(w1 && w2 && b1 && b2 && out_w && out_b, "toc3d_pack_swiglu: null buffer");
+    TOC3D_REQUIRE(Hd > 0 && K > 0, "toc3d_pack_swiglu: Hd and K must be positive");
     TOC3D_REQUIRE(Hp >= Hd && Hp % 64 == 0 && Kp >= K, "toc3d_pack_swiglu: Hp must be >= Hd and a multiple of 64");
+    TOC3D_REQUIRE(Hp <= I32_MAX / 2 && Kp <= I32_MAX, "toc3d_pack_swiglu: dimension too large (the kernel decodes Hd, K, 2 * Hp, Kp in 32 bits)");
     const int64_t total = 2 * Hp * Kp;
     const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
     if (dtype == TOC3D_BF16)
@@ -514,11 +525,13 @@ int toc3d_pack_swiglu(int dtype, const float* w1, const float* w2, const float* 
 int toc3d_im2col_patches(int dtype, const float* img, void* out, int64_t ldo, int64_t V, int64_t Cin, int64_t H, int64_t W,
                          int64_t patch, toc3d_stream_t stream) {
     TOC3D_REQUIRE(img && out, "toc3d_im2col_patches: null buffer");
+    TOC3D_REQUIRE(V > 0 && Cin > 0 && H > 0 && W > 0, "toc3d_im2col_patches: V, Cin, H and W must be positive");
     TOC3D_REQUIRE(patch > 0 && patch % 4 == 0 && H % patch == 0 && W % patch == 0, "toc3d_im2col_patches: H, W must be multiples of patch (patch %% 4 == 0)");
+    TOC3D_REQUIRE(V <= I32_MAX && H <= I32_MAX && W <= I32_MAX && Cin <= I32_MAX / (patch * patch) && V * Cin <= INT64_MAX / (4 * H) / W,
+                  "toc3d_im2col_patches: dimension too large (the kernel decodes V, H, W and Cin * patch * patch in 32 bits; the image's bytes in 64)");
     TOC3D_REQUIRE(ldo >= Cin * patch * patch, "toc3d_im2col_patches: ldo too small");
     TOC3D_REQUIRE(((uintptr_t)img % 16) == 0, "toc3d_im2col_patches: img must be 16-byte aligned");
     const int64_t total = V * (H / patch) * (W / patch) * Cin * patch * patch / 4;
-    if (total == 0) return TOC3D_OK;
     const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
     if (dtype == TOC3D_BF16)
         toc3d_launch(im2col_kernel<bf16_t>, dim3(blocks), dim3(256), 0, as_stream(stream), img, (bf16_t*)out, ldo, (int)V, (int)Cin, (int)H, (int)W, (int)patch);

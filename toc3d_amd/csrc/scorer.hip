@@ -681,9 +681,12 @@ int toc3d_abs_pos_bicubic(const float* pos, int64_t S, int64_t C, float* out, in
 
 int toc3d_im2col_3x3(int dtype, const float* x, void* out, int64_t ldo, int64_t V, int64_t h, int64_t w, int64_t C,
                      toc3d_stream_t stream) {
+    TOC3D_REQUIRE(V >= 0 && h >= 0 && w >= 0, "toc3d_im2col_3x3: negative dimension");
+    TOC3D_REQUIRE(C > 0 && C <= 0x7fffffffLL / 9, "toc3d_im2col_3x3: the channel count must be positive (and 9 * C fit 32 bits)");
     TOC3D_REQUIRE(x && out && ldo >= 9 * C, "toc3d_im2col_3x3: bad arguments");
+    if (V == 0 || h == 0 || w == 0) return TOC3D_OK;
+    TOC3D_REQUIRE(V <= 0x7fffffffLL && h <= 0x7fffffffLL / V && w <= 0x7fffffffLL / (V * h), "toc3d_im2col_3x3: too many rows (V * h * w: one workgroup per row, counted in 32 bits)");
     const int64_t M = V * h * w;
-    if (M <= 0) return TOC3D_OK;
     if (int rc = toc3d_dispatch_act<ACT_BF16 | ACT_F32>("toc3d_im2col_3x3", dtype, [&](auto tag) {
             using T = typename decltype(tag)::type;
             toc3d_launch(im2col_3x3_kernel<T>, dim3((unsigned)M), dim3(256), 0, as_stream(stream), x, (T*)out, ldo, (int)V, (int)h, (int)w, (int)C);

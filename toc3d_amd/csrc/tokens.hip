@@ -946,6 +946,8 @@ int toc3d_copy_segments(int64_t n, void* const* dst, const void* const* src, con
 
 int toc3d_nhwc_to_nchw(const float* x, float* out, int64_t V, int64_t T, int64_t C, toc3d_stream_t stream) {
     TOC3D_REQUIRE(x && out && V > 0 && T > 0 && C > 0, "toc3d_nhwc_to_nchw: bad arguments");
+    TOC3D_REQUIRE(T <= 0x7fffffffLL - 31, "toc3d_nhwc_to_nchw: too many tokens (the kernel counts them, rounded up to whole 32-token tiles, in 32 bits)");
+    TOC3D_REQUIRE(V <= 65535 && C <= 65535 * 32, "toc3d_nhwc_to_nchw: grid too large (V and ceil(C / 32) ride on grid axes of at most 65535)");
     dim3 grid((unsigned)((T + 31) / 32), (unsigned)((C + 31) / 32), (unsigned)V);
     toc3d_launch(nhwc_to_nchw_kernel, grid, dim3(256), 0, as_stream(stream), x, out, (int)T, (int)C);
     TOC3D_LAUNCH_CHECK("toc3d_nhwc_to_nchw");
