@@ -38,6 +38,9 @@ Derived state (packed weights, workspaces, plans, the bank) belongs to the parts
 """
 from __future__ import annotations
 
+import json
+import os
+
 import torch
 import torch.nn as nn
 
@@ -50,6 +53,7 @@ from .neck import CPFPN
 from .token_vis import TokenVis
 from .box_vis import BoxVis
 from .nusc_results import POSE_KEYS, NuScenesResults
+from .tracking import TRACKING_META, PubTracker
 
 _NAME = "toc3d_amd.Petr3D"
 _ABSENT = ("pts_voxel_layer", "pts_voxel_encoder", "pts_middle_encoder", "pts_fusion_layer", "pts_backbone", "pts_neck", "img_rpn_head")
@@ -123,6 +127,7 @@ class Petr3D(_plan.DerivedState, nn.Module):
         self.box_vis, self.box_vis_num_sample, self.box_vis_start_id, self.box_vis_out_path, self.box_vis_cur_id = False, 0, 0, "./box_vis", 0
         self._box_vis = None                                                # a BoxVis, made by enable_box_vis()
         self.format_nusc_results, self.nusc_results = False, None           # a NuScenesResults, made by enable_nusc_results()
+        self.track_results, self.tracker, self.tracking_score_threshold, self.tracking_results = False, None, 0.25, {}     # a PubTracker, made by enable_tracking()
         self._drop_derived()
         self.eval()
 
@@ -249,9 +254,62 @@ class Petr3D(_plan.DerivedState, nn.Module):
         self.format_nusc_results = False
         return self
 
-    def _nusc_results_step(self, img_metas, bbox_list):
-        """In :meth:`_pts_results`: from the device tensors ``get_bboxes`` returned, before ``bbox3d2result`` moves them to the host; one launch for all samples."""
+    # ---- tracking ids (the reference tracks after the run, on the host, from results_nusc.json: nusc_tracking/pub_test.py:77-153) ------------------------------
+    def enable_tracking(self, max_age=3, score_threshold=0.25, **tracker_kwargs):
+        """From the next frame on the submission records of every sample are tracked on the device (:class:`toc3d_amd.PubTracker`, to which ``max_age`` --
+        ``pub_test.py``'s default is 3 -- and ``tracker_kwargs`` go), one tracker per camera stream, and the frame's tracking records (``pub_test.py:115-128``) are
+        kept in ``self.tracking_results`` under ``img_metas[b]['sample_idx']``; :meth:`dump_tracking` writes the file.  Needs :meth:`enable_nusc_results`, whose
+        records it steps on.  A stream's tracker starts afresh where the scene-token comparison of :meth:`simple_test` / :meth:`simple_test_streams` starts a
+        scene.  THE TIMESTAMP is ``data['timestamp']``, the float64 ``(B,)`` tensor the frame carries: the frame's own time, where ``pub_test.py`` uses the sample's
+        ``timestamp * 1e-6`` from the devkit (:54) -- the two differ where a dataset pipeline rebases or replaces the frame time, and then so do the time lags
+        and with them the predicted positions; :meth:`PubTracker.track_file` on the dumped records is the route that is exact to the reference's script.  Every
+        detection result, the records of ``nusc_results`` and every piece of derived state keep their bits."""
+        if not self.format_nusc_results or self.nusc_results is None:
+            raise ValueError(f"{_NAME}: enable_tracking needs the submission records it tracks: call enable_nusc_results() first")
+        self._tracker_kwargs = dict(tracker_kwargs, max_age=max_age, class_names=self.nusc_results.class_names)
+        self.tracker = PubTracker(**self._tracker_kwargs)
+        self.track_results, self.tracking_score_threshold = True, float(score_threshold)
+        return self
+
+    def disable_tracking(self):
+        """Stops the tracking; ``self.tracking_results`` keeps what it has gathered."""
+        self.track_results = False
+        return self
+
+    def dump_tracking(self, jsonfile_prefix):
+        """``{jsonfile_prefix}/tracking_result.json`` (created with its directory) as ``pub_test.py:89-152`` writes it -> the path."""
+        os.makedirs(jsonfile_prefix, exist_ok=True)
+        path = os.path.join(jsonfile_prefix, "tracking_result.json")
+        with open(path, "w") as fh:
+            json.dump(dict(results=self.tracking_results, meta=dict(TRACKING_META)), fh)
+        return path
+
+    def _tracking_step(self, tokens, fixed, data, first):
+        """The trackers' step on the records still on the device: one launch for all streams."""
+        B = len(tokens)
+        if fixed is None or B == 0:
+            return
         if not self.format_nusc_results:
+            raise ValueError(f"{_NAME}: tracking is enabled but the submission records are not (disable_tracking() before disable_nusc_results())")
+        ts = data.get("timestamp")
+        if not isinstance(ts, torch.Tensor) or ts.numel() != B:
+            raise ValueError(f"{_NAME}: tracking is enabled but the frame carries no timestamp (data['timestamp'], float64 ({B},))")
+        if self.tracker.num_streams != B:                                   # another number of streams: every stream starts afresh, as the head's bank does
+            self.tracker = PubTracker(**dict(self._tracker_kwargs, num_streams=B))
+        dev = fixed["rec"].device
+        out = self.tracker.step_fixed(fixed["rec"], fixed["score"], fixed["name"], fixed["kept"], ts.to(device=dev, dtype=torch.float64).reshape(B),
+                                      [True] * B if first is None else first, self.tracking_score_threshold)
+        host = {k: v.cpu().numpy() for k, v in dict(out, rec=fixed["rec"], score=fixed["score"], name=fixed["name"]).items()}
+        annos = self.tracker.records_to_annos(host["rec"], host["score"], host["name"], host["track_id"], host["order"], host["num_out"], tokens)
+        for token, a in zip(tokens, annos):
+            self.tracking_results[token] = a
+
+    def _nusc_results_step(self, img_metas, bbox_list, data=None, first=None):
+        """In :meth:`_pts_results`: from the device tensors ``get_bboxes`` returned, before ``bbox3d2result`` moves them to the host; one launch for all samples
+        (and one more for the trackers, after :meth:`enable_tracking`; ``first``: per sample, whether it starts a scene)."""
+        if not self.format_nusc_results:
+            if self.track_results:
+                raise ValueError(f"{_NAME}: tracking is enabled but the submission records are not (disable_tracking() before disable_nusc_results())")
             return
         for b, meta in enumerate(img_metas[:len(bbox_list)]):
             for key in POSE_KEYS + ("sample_idx",):
@@ -259,8 +317,14 @@ class Petr3D(_plan.DerivedState, nn.Module):
                     raise ValueError(f"{_NAME}: nuScenes results are enabled but img_metas[{b}] has no {key!r} (needed: sample_idx, {', '.join(POSE_KEYS)})")
         metas = img_metas[:len(bbox_list)]
         tokens = [m["sample_idx"] for m in metas]
-        for token, annos in zip(tokens, self.nusc_results.format(bbox_list, metas, tokens)):
+        if self.track_results:                                              # the device half as well: the trackers step on it
+            fixed, formatted = self.nusc_results.format_device(bbox_list, metas, tokens)
+        else:
+            fixed, formatted = None, self.nusc_results.format(bbox_list, metas, tokens)
+        for token, annos in zip(tokens, formatted):
             self.nusc_results.add(token, annos)
+        if self.track_results:
+            self._tracking_step(tokens, fixed, data or {}, first)
 
     # ---- the reference's methods -------------------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -389,11 +453,13 @@ class Petr3D(_plan.DerivedState, nn.Module):
             self.prev_scene_token = img_metas[0]["scene_token"]
             data["prev_exists"] = data["img"].new_zeros(1)
             self.pts_bbox_head.reset_memory()
+            first = [True]
         else:
             data["prev_exists"] = data["img"].new_ones(1)
-        return self._pts_results(img_metas, location, topk_indexes, data)
+            first = [False]
+        return self._pts_results(img_metas, location, topk_indexes, data, first=first)
 
-    def _pts_results(self, img_metas, location, topk_indexes, data, streams=None):
+    def _pts_results(self, img_metas, location, topk_indexes, data, streams=None, first=None):
         """The head on ``data`` (``prev_exists`` decided by the caller) and the decoded lists, one per sample; after :meth:`enable_box_vis` the lists are drawn
         while they are still on the device (``streams``: B, for a step of several camera streams)."""
         fanned = self._is_fanned(data["img_feats"])
@@ -401,7 +467,7 @@ class Petr3D(_plan.DerivedState, nn.Module):
         outs = self.pts_bbox_head(location, img_metas, topk_indexes, img_feats_rows=fanned, **data)
         bbox_list = self.pts_bbox_head.get_bboxes(outs, img_metas)
         self._box_vis_step(img_metas, data, bbox_list, streams)
-        self._nusc_results_step(img_metas, bbox_list)
+        self._nusc_results_step(img_metas, bbox_list, data, first)
         return [bbox3d2result(bboxes, scores, labels) for bboxes, scores, labels in bbox_list]
 
     @torch.no_grad()
@@ -451,7 +517,7 @@ class Petr3D(_plan.DerivedState, nn.Module):
         self._vis_step(img_metas, data["img"], token_masks, keep_idxes, drop_idxes, streams=B)
         data["prev_exists"] = torch.tensor([1.0 if p else 0.0 for p in prev], dtype=torch.float32, device=data["img"].device)
         location, topk_indexes = self._select_tokens(img_metas, data)
-        return [dict(pts_bbox=r) for r in self._pts_results(img_metas, location, topk_indexes, data, streams=B)]
+        return [dict(pts_bbox=r) for r in self._pts_results(img_metas, location, topk_indexes, data, streams=B, first=[not p for p in prev])]
 
     def reset_streams(self, indices=None):
         """Forget the scene tokens of the streams ``indices`` (default: all): their next step starts a scene whatever token it carries."""

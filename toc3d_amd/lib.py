@@ -205,6 +205,15 @@ RESULTS_MAX_BOXES, RESULTS_MAX_CLASSES, RESULTS_REC = 2048, 64, 12      # == TOC
 _RESULTS_SIGS = {
     "toc3d_boxes_to_global": "pll" + "ppp" + "ll" + "i" + "p" + "ppp" + "l" + "d" + "pppppp" + "p",
 }
+# include/toc3d_tracks.h (greedy centre-distance tracking of the submission records, toc3d_amd.PubTracker): a side header likewise
+TRACKS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "toc3d_tracks.h")
+TRACKS_ABI = 1                  # == TOC3D_TRACKS_ABI
+TRACKS_MAX_TRACKS, TRACKS_MAX_BOXES, TRACKS_MAX_CLASSES, TRACKS_REC = 8192, 2048, 64, 12        # == TOC3D_TRACKS_MAX_TRACKS, _MAX_BOXES, _MAX_CLASSES, _REC
+TRACKS_HEADER_BYTES, TRACKS_ROW_BYTES = 32, 48                                                   # == TOC3D_TRACKS_HEADER_BYTES, _ROW_BYTES
+_TRACKS_SIGS = {
+    "toc3d_tracks_state_bytes": "lp",
+    "toc3d_tracks_step": "pppp" + "ll" + "pl" + "pl" + "d" + "l" + "pp" + "ppl" + "pppp" + "p",
+}
 
 # The side headers, one row each: key -> (header, the symbol that reports its ABI, the ABI this package binds, its signature table).  _bind_side() and call() read
 # nothing else, so A NEW SIDE HEADER IS ONE NEW ROW HERE plus its constants above (tests/test_cpu_abi.py holds every row against its header).
@@ -217,6 +226,7 @@ SIDES = {
     "vis": (VIS_HEADER_PATH, "toc3d_vis_abi", VIS_ABI, _VIS_SIGS),
     "boxes": (BOXES_HEADER_PATH, "toc3d_boxes_abi", BOXES_ABI, _BOXES_SIGS),
     "results": (RESULTS_HEADER_PATH, "toc3d_results_abi", RESULTS_ABI, _RESULTS_SIGS),
+    "tracks": (TRACKS_HEADER_PATH, "toc3d_tracks_abi", TRACKS_ABI, _TRACKS_SIGS),
 }
 _SIDE_OF = {name: key for key, row in SIDES.items() for name in row[3]}       # entry point -> its side: call()'s one lookup
 

@@ -180,12 +180,17 @@ class NuScenesResults:
         ``.tensor``); ``poses``: a pose record per sample.  Packs the lists, formats them in one launch, copies the records to the host once and returns, per
         sample, the list of dicts the reference appends (:348-356): ``sample_token`` (when ``sample_tokens`` is given), ``translation``, ``size``, ``rotation``,
         ``velocity``, ``detection_name``, ``detection_score``, ``attribute_name``; numbers are Python floats."""
+        return self.format_device(bbox_list, poses, sample_tokens)[1]
+
+    def format_device(self, bbox_list, poses, sample_tokens=None):
+        """What :meth:`format` is built on -> ``(fixed, annos)``: the :meth:`format_fixed` dict of the packed lists, still on the device (``None`` for no samples;
+        what :class:`toc3d_amd.PubTracker` steps on), and what :meth:`format` returns."""
         B = len(bbox_list)
         if len(poses) != B or (sample_tokens is not None and len(sample_tokens) != B):
             raise ValueError(f"{_NAME}: {B} samples need {B} pose records{'' if sample_tokens is None else ' and sample tokens'}")
         pose = pose_array(poses)                                            # the refusals come before any device work
         if B == 0:
-            return []
+            return None, []
         width = 9 if self.with_velocity else 7
         tensors = [getattr(bb, "tensor", bb) for bb, _, _ in bbox_list]
         for t in tensors:
@@ -205,7 +210,7 @@ class NuScenesResults:
         counts = torch.tensor(ns, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
         out = self.format_fixed(boxes, scores, labels, counts, pose)
         host = {k: out[k].cpu().numpy() for k in ("rec", "score", "name", "attr", "kept")}
-        return self.records_to_annos(host["rec"], host["score"], host["name"], host["attr"], host["kept"], sample_tokens)
+        return out, self.records_to_annos(host["rec"], host["score"], host["name"], host["attr"], host["kept"], sample_tokens)
 
     # ---- the host half -----------------------------------------------------------------------------------------------------------------------------------
     def records_to_annos(self, rec, score, name, attr, kept, tokens=None):
