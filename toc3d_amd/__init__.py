@@ -17,7 +17,7 @@ from .detector import Petr3D, build_vis_detector
 from .token_vis import TokenVis, token_selection_vis
 from .box_vis import BoxVis
 from .nusc_results import NuScenesResults
-from .tracking import PubTracker
+from .tracking import HungarianPubTracker, PubTracker, build_tracker
 from .registry import (BACKBONES, BBOX_CODERS, DETECTORS, HEADS, NECKS, TRANSFORMER, build_backbone, build_bbox_coder, build_detector, build_head, build_neck,
                        build_transformer, register_all)
 
@@ -26,4 +26,4 @@ register_all()
 __all__ = ["ToC3DEVAViT", "EVA_ViT", "CPFPN", "ToC3DViTReturnType", "BACKBONES", "NECKS", "build_backbone", "build_neck", "prepare_images", "ResizeCropFlipRotImage", "resample_tables", "TemporalMemory", "HeadTokenEmbedding",
            "PETRTemporalTransformer", "TRANSFORMER", "build_transformer", "HeadOutputs", "HeadQueries", "NMSFreeCoder", "BBOX_CODERS", "build_bbox_coder",
            "StreamPETRHead", "FocalHead", "HEADS", "build_head", "Petr3D", "DETECTORS", "build_detector", "build_vis_detector",
-           "TokenVis", "token_selection_vis", "BoxVis", "NuScenesResults", "PubTracker"]
+           "TokenVis", "token_selection_vis", "BoxVis", "NuScenesResults", "PubTracker", "HungarianPubTracker", "build_tracker"]

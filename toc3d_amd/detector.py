@@ -53,7 +53,7 @@ from .neck import CPFPN
 from .token_vis import TokenVis
 from .box_vis import BoxVis
 from .nusc_results import POSE_KEYS, NuScenesResults
-from .tracking import TRACKING_META, PubTracker
+from .tracking import TRACKING_META, HungarianPubTracker, PubTracker, build_tracker
 
 _NAME = "toc3d_amd.Petr3D"
 _ABSENT = ("pts_voxel_layer", "pts_voxel_encoder", "pts_middle_encoder", "pts_fusion_layer", "pts_backbone", "pts_neck", "img_rpn_head")
@@ -255,9 +255,10 @@ class Petr3D(_plan.DerivedState, nn.Module):
         return self
 
     # ---- tracking ids (the reference tracks after the run, on the host, from results_nusc.json: nusc_tracking/pub_test.py:77-153) ------------------------------
-    def enable_tracking(self, max_age=3, score_threshold=0.25, **tracker_kwargs):
-        """From the next frame on the submission records of every sample are tracked on the device (:class:`toc3d_amd.PubTracker`, to which ``max_age`` --
-        ``pub_test.py``'s default is 3 -- and ``tracker_kwargs`` go), one tracker per camera stream, and the frame's tracking records (``pub_test.py:115-128``) are
+    def enable_tracking(self, max_age=3, score_threshold=0.25, hungarian=False, **tracker_kwargs):
+        """From the next frame on the submission records of every sample are tracked on the device (:func:`toc3d_amd.build_tracker`, to which ``hungarian`` and
+        ``max_age`` -- ``pub_test.py``'s defaults are False and 3 -- and ``tracker_kwargs`` go: a :class:`toc3d_amd.PubTracker`, or with ``hungarian=True`` a
+        :class:`toc3d_amd.HungarianPubTracker`, at most 512 records a sample), one tracker per camera stream, and the frame's tracking records (``pub_test.py:115-128``) are
         kept in ``self.tracking_results`` under ``img_metas[b]['sample_idx']``; :meth:`dump_tracking` writes the file.  Needs :meth:`enable_nusc_results`, whose
         records it steps on.  A stream's tracker starts afresh where the scene-token comparison of :meth:`simple_test` / :meth:`simple_test_streams` starts a
         scene.  THE TIMESTAMP is ``data['timestamp']``, the float64 ``(B,)`` tensor the frame carries: the frame's own time, where ``pub_test.py`` uses the sample's
@@ -267,9 +268,13 @@ class Petr3D(_plan.DerivedState, nn.Module):
         if not self.format_nusc_results or self.nusc_results is None:
             raise ValueError(f"{_NAME}: enable_tracking needs the submission records it tracks: call enable_nusc_results() first")
         self._tracker_kwargs = dict(tracker_kwargs, max_age=max_age, class_names=self.nusc_results.class_names)
-        self.tracker = PubTracker(**self._tracker_kwargs)
+        self._tracker_hungarian = bool(hungarian)
+        self.tracker = self._build_tracker()
         self.track_results, self.tracking_score_threshold = True, float(score_threshold)
         return self
+
+    def _build_tracker(self, **more):
+        return build_tracker(hungarian=self._tracker_hungarian, classes=(PubTracker, HungarianPubTracker), **dict(self._tracker_kwargs, **more))
 
     def disable_tracking(self):
         """Stops the tracking; ``self.tracking_results`` keeps what it has gathered."""
@@ -295,7 +300,7 @@ class Petr3D(_plan.DerivedState, nn.Module):
         if not isinstance(ts, torch.Tensor) or ts.numel() != B:
             raise ValueError(f"{_NAME}: tracking is enabled but the frame carries no timestamp (data['timestamp'], float64 ({B},))")
         if self.tracker.num_streams != B:                                   # another number of streams: every stream starts afresh, as the head's bank does
-            self.tracker = PubTracker(**dict(self._tracker_kwargs, num_streams=B))
+            self.tracker = self._build_tracker(num_streams=B)
         dev = fixed["rec"].device
         out = self.tracker.step_fixed(fixed["rec"], fixed["score"], fixed["name"], fixed["kept"], ts.to(device=dev, dtype=torch.float64).reshape(B),
                                       [True] * B if first is None else first, self.tracking_score_threshold)

@@ -214,6 +214,13 @@ _TRACKS_SIGS = {
     "toc3d_tracks_state_bytes": "lp",
     "toc3d_tracks_step": "pppp" + "ll" + "pl" + "pl" + "d" + "l" + "pp" + "ppl" + "pppp" + "p",
 }
+# include/toc3d_assign.h (the tracking step with the reference's hungarian=True: scipy's solver replayed, toc3d_amd.HungarianPubTracker): a side header likewise
+ASSIGN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "toc3d_assign.h")
+ASSIGN_ABI = 1                  # == TOC3D_ASSIGN_ABI
+ASSIGN_MAX_BOXES, ASSIGN_MAX_TRACKS = 512, 2048                                                  # == TOC3D_ASSIGN_MAX_BOXES, _MAX_TRACKS
+_ASSIGN_SIGS = {
+    "toc3d_tracks_step_hungarian": "pppp" + "ll" + "pl" + "pl" + "d" + "l" + "pp" + "ppl" + "pppp" + "p" + "p",
+}
 
 # The side headers, one row each: key -> (header, the symbol that reports its ABI, the ABI this package binds, its signature table).  _bind_side() and call() read
 # nothing else, so A NEW SIDE HEADER IS ONE NEW ROW HERE plus its constants above (tests/test_cpu_abi.py holds every row against its header).
@@ -227,6 +234,7 @@ SIDES = {
     "boxes": (BOXES_HEADER_PATH, "toc3d_boxes_abi", BOXES_ABI, _BOXES_SIGS),
     "results": (RESULTS_HEADER_PATH, "toc3d_results_abi", RESULTS_ABI, _RESULTS_SIGS),
     "tracks": (TRACKS_HEADER_PATH, "toc3d_tracks_abi", TRACKS_ABI, _TRACKS_SIGS),
+    "assign": (ASSIGN_HEADER_PATH, "toc3d_assign_abi", ASSIGN_ABI, _ASSIGN_SIGS),
 }
 _SIDE_OF = {name: key for key, row in SIDES.items() for name in row[3]}       # entry point -> its side: call()'s one lookup
 

@@ -1,4 +1,5 @@
-"""Greedy centre-distance tracking of the submission records, on the device (``toc3d_tracks_step``, include/toc3d_tracks.h).
+"""Centre-distance tracking of the submission records, on the device: greedy assignment (``toc3d_tracks_step``, include/toc3d_tracks.h) and the reference's
+``hungarian=True`` (``toc3d_tracks_step_hungarian``, include/toc3d_assign.h).
 
 The reference tracks after the run, on the host: ``nusc_tracking/pub_tracker.py:26-186`` (``PubTracker.step_centertrack``) with ``track_utils.py:3-12``
 (``greedy_assignment``), driven by ``nusc_tracking/pub_test.py:77-153``, which reads ``results_nusc.json`` and writes ``tracking_result.json`` -- per frame an
@@ -10,8 +11,14 @@ takes the reference's lists of dicts, :meth:`PubTracker.track_file` restates ``p
 The reference's quirks are reproduced, not mended (include/toc3d_tracks.h states the arithmetic): a frame none of whose detections survives the filter leaves
 every track in place, the old ones (``age >= max_age``) untouched and able to match later; the positions are compared in float32, each operation rounded once; the
 lowest track index wins a tie, the earlier detection takes first.  Differences, by design: a distance that is not a number is no match; the unmatched tracks the
-reference returns in its list with ``active == 0`` (``pub_test.py:116`` skips them) are state here, not output; Hungarian assignment is not built.
-No CPU path for the matching.
+reference returns in its list with ``active == 0`` (``pub_test.py:116`` skips them) are state here, not output.  No CPU path for the matching.
+
+HUNGARIAN ASSIGNMENT (``pub_tracker.py:27`` ``hungarian=False``, ``pub_test.py:28,81`` ``--hungarian``) is reached through :func:`build_tracker`, which takes the
+reference's keywords: ``build_tracker(hungarian=True, max_age=3)`` returns a :class:`HungarianPubTracker`, whose step replays scipy's
+``linear_sum_assignment`` operation for operation on the reference's matrix (1e18 for an invalid pair), tie-breaking included, and so reproduces what the
+reference does there and an exact optimum would not: a track parked in an invalid match is dropped at once whatever its age, and the detections parked on tracks
+get their new ids after the unmatched ones (include/toc3d_assign.h).  It holds up to 512 rows a stream and 2048 tracks.  ``PubTracker(hungarian=True)`` itself
+keeps refusing.
 """
 from __future__ import annotations
 
@@ -26,7 +33,7 @@ import torch
 from . import lib
 from .nusc_results import CLASS_NAMES
 
-__all__ = ["PubTracker", "NUSCENES_TRACKING_NAMES", "NUSCENE_CLS_VELOCITY_ERROR", "TRACK_ANNO_KEYS", "TRACKING_META"]
+__all__ = ["PubTracker", "HungarianPubTracker", "build_tracker", "NUSCENES_TRACKING_NAMES", "NUSCENE_CLS_VELOCITY_ERROR", "TRACK_ANNO_KEYS", "TRACKING_META"]
 _NAME = "toc3d_amd.PubTracker"
 
 NUSCENES_TRACKING_NAMES = ("car", "truck", "bus", "trailer", "motorcycle", "bicycle", "pedestrian")       # pub_tracker.py:9-12: the index is the tracking label
@@ -65,6 +72,9 @@ class PubTracker:
     >>> out = trk.step_fixed(fixed["rec"], fixed["score"], fixed["name"], fixed["kept"], timestamps, first)      # on the device, one launch
     >>> toc3d_amd.PubTracker(max_age=3).track_file("results_nusc.json", frames, "./work_dir")                    # pub_test.py:main
     """
+
+    _ENTRY, _MAX_BOXES, _MAX_TRACKS, _CAPS = "toc3d_tracks_step", lib.TRACKS_MAX_BOXES, lib.TRACKS_MAX_TRACKS, ("TOC3D_TRACKS_MAX_BOXES", "TOC3D_TRACKS_MAX_TRACKS")
+    _EXTRA_OUT = ()                                                         # outputs of the entry point behind num_out: (key, dtype), one value a stream
 
     def __init__(self, hungarian=False, max_age=0, class_names=CLASS_NAMES, tracking_names=NUSCENES_TRACKING_NAMES, cls_velocity_error=None, num_streams=1):
         if hungarian:
@@ -119,8 +129,8 @@ class PubTracker:
     def _ensure_state(self, K, dev):
         """The two state buffers on ``dev`` with room for a step of K rows; grown (the tracks copied field by field, on the device) when K asks for more."""
         need = capacity_for(K, self.max_age)
-        if need > lib.TRACKS_MAX_TRACKS:
-            raise ValueError(f"{_NAME}: {K} rows a stream with max_age {self.max_age} need {need} tracks, more than {lib.TRACKS_MAX_TRACKS} (TOC3D_TRACKS_MAX_TRACKS)")
+        if need > self._MAX_TRACKS:
+            raise ValueError(f"{_NAME}: {K} rows a stream with max_age {self.max_age} need {need} tracks, more than {self._MAX_TRACKS} ({self._CAPS[1]})")
         if self._state is not None and self._state[0].device == dev and need <= self.capacity:
             return
         cap = max(need, self.capacity if self._state is not None and self._state[0].device == dev else 0)
@@ -153,7 +163,7 @@ class PubTracker:
         returns, on the device, B = ``num_streams``.  ``timestamps``: a device float64 ``(B,)`` tensor, or B host numbers (seconds; finite, else ``ValueError``).
         ``first``: a device int32 ``(B,)`` tensor, B bools, or ``None``; a stream is started when its flag is set, on its first step and after :meth:`reset`.
         -> ``dict(track_id, active (B, K) int32 per input row, order (B, K) int32: the rows in the reference's output order, -1 from num_out on, num_out (B,) int64)``
-        on the device.  One launch, no host synchronisation."""
+        on the device (a :class:`HungarianPubTracker` adds ``rounds (B,) int32``).  One launch, no host synchronisation."""
         for t, what in ((rec, "rec"), (score, "score"), (name, "name"), (kept, "kept")):
             if not isinstance(t, torch.Tensor) or not t.is_cuda:
                 raise RuntimeError(f"{_NAME}: {what} must be a CUDA/HIP tensor -- the HIP extension is the only compute path")
@@ -164,8 +174,8 @@ class PubTracker:
         if (tuple(score.shape), tuple(name.shape), tuple(kept.shape)) != ((B, K), (B, K), (B,)) or score.dtype != torch.float32 or name.dtype != torch.int32 or kept.dtype != torch.int64:
             raise ValueError(f"{_NAME}: float32 score ({B}, {K}), int32 name ({B}, {K}) and int64 kept ({B},) expected, got {score.dtype} {tuple(score.shape)}, "
                              f"{name.dtype} {tuple(name.shape)}, {kept.dtype} {tuple(kept.shape)}")
-        if K > lib.TRACKS_MAX_BOXES:
-            raise ValueError(f"{_NAME}: {K} rows a stream exceed {lib.TRACKS_MAX_BOXES} (TOC3D_TRACKS_MAX_BOXES)")
+        if K > self._MAX_BOXES:
+            raise ValueError(f"{_NAME}: {K} rows a stream exceed {self._MAX_BOXES} ({self._CAPS[0]})")
         thr = float(score_threshold)
         if not math.isfinite(thr):
             raise ValueError(f"{_NAME}: score_threshold must be finite, got {score_threshold!r}")
@@ -198,8 +208,10 @@ class PubTracker:
             lab, gate = self._tables_on(dev)
             out = dict(track_id=torch.empty(B, K, dtype=torch.int32, device=dev), active=torch.empty(B, K, dtype=torch.int32, device=dev),
                        order=torch.empty(B, K, dtype=torch.int32, device=dev), num_out=torch.empty(B, dtype=torch.int64, device=dev))
-            lib.call("toc3d_tracks_step", rec, score, name, kept, B, K, lab, len(self.class_names), gate, len(self.tracking_names), thr, self.max_age, ts, flags,
-                     self._state[0], self._state[1], self.capacity, out["track_id"], out["active"], out["order"], out["num_out"], lib.stream_ptr())
+            out.update({key: torch.empty(B, dtype=dtype, device=dev) for key, dtype in self._EXTRA_OUT})
+            lib.call(self._ENTRY, rec, score, name, kept, B, K, lab, len(self.class_names), gate, len(self.tracking_names), thr, self.max_age, ts, flags,
+                     self._state[0], self._state[1], self.capacity, out["track_id"], out["active"], out["order"], out["num_out"], *[out[key] for key, _ in self._EXTRA_OUT],
+                     lib.stream_ptr())
             self._state.reverse()                                           # what was written is read next
         return out
 
@@ -292,6 +304,25 @@ class PubTracker:
         with open(path, "w") as fh:
             json.dump(dict(results=results, meta=dict(TRACKING_META)), fh)
         return path
+
+
+class HungarianPubTracker(PubTracker):
+    """:class:`PubTracker` with the reference's ``hungarian=True``: ``toc3d_tracks_step_hungarian`` (include/toc3d_assign.h) in place of the greedy step.  Made by
+    :func:`build_tracker`.  :meth:`step_fixed` returns ``rounds (B,) int32`` -- the scan rounds the solver made per stream -- beside the other outputs; ``step``,
+    ``records_to_annos``, ``track_file``, ``reset``, the growth of the state and the streams are inherited.  At most 512 rows a stream (TOC3D_ASSIGN_MAX_BOXES)
+    and 2048 tracks (TOC3D_ASSIGN_MAX_TRACKS): more is a ``ValueError``."""
+    _ENTRY, _MAX_BOXES, _MAX_TRACKS, _CAPS = "toc3d_tracks_step_hungarian", lib.ASSIGN_MAX_BOXES, lib.ASSIGN_MAX_TRACKS, ("TOC3D_ASSIGN_MAX_BOXES", "TOC3D_ASSIGN_MAX_TRACKS")
+    _EXTRA_OUT = (("rounds", torch.int32),)
+
+    def __init__(self, max_age=0, **kwargs):
+        super().__init__(hungarian=False, max_age=max_age, **kwargs)
+        self.hungarian = True
+
+
+def build_tracker(hungarian=False, max_age=0, classes=(PubTracker, HungarianPubTracker), **kwargs):
+    """The reference's ``PubTracker(hungarian=False, max_age=0)`` (``pub_tracker.py:27``; ``pub_test.py --hungarian --max_age``): a :class:`PubTracker`, or with
+    ``hungarian=True`` a :class:`HungarianPubTracker`; ``kwargs`` go to the class.  ``classes``: the (greedy, Hungarian) pair to build from."""
+    return classes[1 if hungarian else 0](max_age=max_age, **kwargs)
 
 
 def library_state_bytes(capacity: int) -> int:
