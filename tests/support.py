@@ -297,7 +297,23 @@ def same_bits(a, b):
     return torch.equal(bits(a.cpu()), bits(b.cpu()))
 
 
-CAN32, CAN16 = 0x41104110, 0x4110            # the canary: bf16 9.0 in every 16-bit half, so a planes buffer decodes to hi = lo = 9.0 (as f32: 9.016...)
+GUARD_BYTES, FILL = 256, 0xA5                 # the byte guard: a window of a byte buffer with GUARD_BYTES of FILL on either side of it
+
+
+def guarded(nbytes, off=0, device=DEV):
+    """-> (the whole buffer, its window of ``nbytes`` bytes): GUARD_BYTES + ``off`` bytes before the window (``off`` puts it at an odd address) and GUARD_BYTES
+    behind it, all FILL."""
+    buf = torch.full((GUARD_BYTES + off + nbytes + GUARD_BYTES,), FILL, dtype=torch.uint8, device=device)
+    return buf, buf[GUARD_BYTES + off:GUARD_BYTES + off + nbytes]
+
+
+def touched(buf, nbytes, off=0):
+    """How many bytes of ``guarded(nbytes, off)``'s buffer outside the window are no longer FILL."""
+    host = buf.cpu().numpy()
+    return int((host[:GUARD_BYTES + off] != FILL).sum() + (host[GUARD_BYTES + off + nbytes:] != FILL).sum())
+
+
+CAN32, CAN16 = 0x41104110, 0x4110           # the canary: bf16 9.0 in every 16-bit half, so a planes buffer decodes to hi = lo = 9.0 (as f32: 9.016...)
 
 
 def canary(rows, ld, tdt):

@@ -12,12 +12,12 @@ import re
 import numpy as np
 import pytest
 import torch
-import torch.nn as nn
 
 import nusc_results_cases as NC
 import toc3d_amd
-from support import A, ERR_ARG, FakeNeck, OldLibrary, header_sigs, raw_call
-from toc3d_amd import lib, synth
+from detector_cases import fake_detector, frame
+from support import A, ERR_ARG, OldLibrary, header_sigs, raw_call
+from toc3d_amd import lib
 from toc3d_amd import nusc_results as NR
 
 ENTRY = "toc3d_boxes_to_global"
@@ -326,32 +326,6 @@ def test_records_to_annos_and_dump_round_trip(tmp_path):
 
 
 # ---- the detector hook --------------------------------------------------------------------------------------------------------------------------------------------------
-class FakeBackbone(nn.Module):
-    pruning_loc, pruning_num_queries, patch_size, img_norm_cfg = [3, 6, 9], 64, 16, None
-
-    def forward(self, x, **kw):
-        return toc3d_amd.ToC3DViTReturnType({"last_feat": torch.zeros(x.shape[0], 8, 2, 5)}, ["m0", "m1", "m2"], None, ["k0", "k1", "k2"], ["d0", "d1", "d2"])
-
-
-class FakeHead(nn.Module):
-    embed_dims = 256
-
-    def backbone_queries(self, n, prev_exists, batch_size=1):
-        return dict(temp_queries=torch.zeros(batch_size, n, 256), temp_ref_points=None, temp_timestamp=None, temp_ego_pose=None, temp_vel=None, prev_exists=False)
-
-    def img_feats_rows_buffer(self, B, N, h, w, device=None):
-        return "rows", 64, lib.F32X3P
-
-    def reset_memory(self):
-        pass
-
-    def forward(self, memory_center, img_metas, topk_indexes=None, img_feats_rows=False, **data):
-        return dict(all_cls_scores="cls", all_bbox_preds="box", dn_mask_dict=None)
-
-    def get_bboxes(self, outs, img_metas, rescale=False):
-        return [[torch.full((3, 9), float(i)), torch.arange(3.0) + i, torch.arange(3) + i] for i, _ in enumerate(img_metas)]
-
-
 class FakeResults:
     """Records what the detector hands to NuScenesResults."""
     def __init__(self):
@@ -365,21 +339,8 @@ class FakeResults:
         self.results[token] = annos
 
 
-def fake_detector():
-    det = toc3d_amd.build_detector(synth.detector_cfg(synth.DETECTOR_TINY))
-    det.img_backbone, det.img_neck, det.pts_bbox_head = FakeBackbone(), FakeNeck([]), FakeHead()
-    return det
-
-
 def meta(token, scene="a", **over):
     return dict(pose(**over), scene_token=scene, pad_shape=[(32, 80, 3)], sample_idx=token)
-
-
-def frame(det, metas):
-    B = len(metas)
-    data = dict(img=torch.zeros(B, 6, 3, 32, 80), intrinsics=torch.zeros(B, 6, 4, 4), lidar2img=torch.zeros(B, 6, 4, 4), timestamp=torch.zeros(B, dtype=torch.float64),
-                ego_pose=torch.eye(4)[None].repeat(B, 1, 1), ego_pose_inv=torch.eye(4)[None].repeat(B, 1, 1))
-    return det.simple_test(metas, **data) if B == 1 else det.simple_test_streams(metas, **data)
 
 
 def test_detector_hook_reads_the_poses_and_names_a_missing_key():

@@ -51,6 +51,25 @@ def test_sentinel_buffers_and_is_sent():
     assert not support.same_bits(a, b) and support.bits(a).dtype == torch.int16 and support.bits(a.float()).dtype == torch.int32
 
 
+def test_byte_guard_counts_writes_around_the_window_and_not_inside():
+    for off in (0, 2, 5):
+        buf, win = support.guarded(24, off, device="cpu")
+        assert buf.dtype == torch.uint8 and buf.numel() == 2 * support.GUARD_BYTES + off + 24 and win.numel() == 24 and bool((buf == support.FILL).all())
+        assert win.data_ptr() - buf.data_ptr() == support.GUARD_BYTES + off and support.touched(buf, 24, off) == 0
+        win[:] = 0                                                           # every byte of the window, its first and last included: not counted
+        assert support.touched(buf, 24, off) == 0
+        buf[support.GUARD_BYTES + off - 1] = 0                               # the byte before the window
+        assert support.touched(buf, 24, off) == 1
+        buf[support.GUARD_BYTES + off + 24] = 0                              # the byte behind it
+        assert support.touched(buf, 24, off) == 2
+        buf[0], buf[-1] = 1, 2                                               # the far ends of both guards
+        assert support.touched(buf, 24, off) == 4
+        if off:
+            buf[support.GUARD_BYTES] = 0                                     # the first byte of the gap ``off`` opens between the leading guard and the window
+            assert support.touched(buf, 24, off) == 5
+    assert (support.GUARD_BYTES, support.FILL) == (256, 0xA5)
+
+
 def test_worst_report_prints_the_present_line_format(capsys):
     note, fixture = support.worst_report("token kernels", 58)
     for ratio in (0.1, torch.tensor(0.1234), 0.05):

@@ -9,12 +9,13 @@ import re
 import numpy as np
 import pytest
 import torch
-import torch.nn as nn
 
+import detector_cases as DC
 import tracking_cases as TC
 import toc3d_amd
-from support import A, ERR_ARG, FakeNeck, header_sigs, raw_call
-from toc3d_amd import lib, synth, tracking
+from support import A, ERR_ARG, header_sigs, raw_call
+from toc3d_amd import lib, tracking
+from tracking_cases import case_annos, restated
 
 ENTRY = "toc3d_tracks_step"
 
@@ -29,6 +30,7 @@ def test_tracks_header_constants_exports_and_makefile():
     assert (define("TOC3D_TRACKS_MAX_TRACKS"), define("TOC3D_TRACKS_MAX_BOXES"), define("TOC3D_TRACKS_MAX_CLASSES"), define("TOC3D_TRACKS_REC")) == (8192, 2048, 64, 12)
     assert (lib.TRACKS_MAX_TRACKS, lib.TRACKS_MAX_BOXES, lib.TRACKS_MAX_CLASSES, lib.TRACKS_REC) == (8192, 2048, 64, 12)
     assert (define("TOC3D_TRACKS_HEADER_BYTES"), define("TOC3D_TRACKS_ROW_BYTES")) == (lib.TRACKS_HEADER_BYTES, lib.TRACKS_ROW_BYTES) == (32, 48)
+    assert (TC.HEADER_BYTES, TC.state_bytes(1) - TC.HEADER_BYTES) == (lib.TRACKS_HEADER_BYTES, lib.TRACKS_ROW_BYTES), "the state's bytes as tests/tracking_cases.py lays them out"
     assert (lib.TRACKS_MAX_BOXES, lib.TRACKS_MAX_CLASSES, lib.TRACKS_REC) == (lib.RESULTS_MAX_BOXES, lib.RESULTS_MAX_CLASSES, lib.RESULTS_REC), "the records' own limits"
     for cited in ("pub_tracker.py:26-186", "track_utils.py:3-12", "pub_test.py:77-153", "pub_test.py:101-105", "pub_test.py:107-108", ":62-72", ":103-116", ":119-124",
                   "track_utils.py:7-11", ":155-160", ":162-168", ":172-183", ":42-59", ":81-98", "EMPTY-FRAME QUIRK", "No atomics", "no inline assembly"):
@@ -230,28 +232,6 @@ def test_capacity_arithmetic_and_device_refusals():
     assert held["age"].tolist() == [4, 5, 6] and held["id_count"] == 9 and held["ct"].tolist() == [[8.0, 9.0], [10.0, 11.0], [12.0, 13.0]]
 
 
-def restated(tracker):
-    """The seam: PubTracker._step_host, the one place where the host half meets the device, replaced by the restatement."""
-    streams = [TC.Tracker(tracker.max_age, tracker.track_label, [tracker.NUSCENE_CLS_VELOCITY_ERROR[n] for n in tracker.tracking_names]) for _ in range(tracker.num_streams)]
-    started = [False] * tracker.num_streams
-
-    def step_host(rec, score, name, kept, timestamps, first, thr):
-        outs, first = [], [False] * len(streams) if first is None else first
-        for b, s in enumerate(streams):
-            outs.append(s.step(rec[b], score[b], name[b], kept[b], timestamps[b], bool(first[b]) or not started[b], thr))
-            started[b] = True
-        return {k: np.stack([o[k] for o in outs]) for k in TC.OUT_KEYS}
-    tracker._step_host = step_host
-    return tracker
-
-
-def case_annos(c, f, b):
-    fr = c["frames"][f]
-    return [dict(sample_token=f"s{f}", translation=fr["rec"][b, i, 0:3].tolist(), size=fr["rec"][b, i, 3:6].tolist(), rotation=fr["rec"][b, i, 6:10].tolist(),
-                 velocity=fr["rec"][b, i, 10:12].tolist(), detection_name=TC.CLASS_NAMES[int(fr["name"][b, i])], detection_score=float(fr["score"][b, i]),
-                 attribute_name="") for i in range(int(fr["kept"][b]))]
-
-
 def test_step_records_and_track_file_on_the_restatement(tmp_path):
     name = "reset_midway"
     c, e = TC.build_case(name), TC.expected(name)
@@ -268,8 +248,7 @@ def test_step_records_and_track_file_on_the_restatement(tmp_path):
         assert all(list(x)[-2:] == ["tracking_id", "active"] and {k: v for k, v in x.items() if k not in ("tracking_id", "active")} == annos[r] for x, r in zip(items, rows))
         results[f"s{f}"] = annos
         frames.append(dict(token=f"s{f}", timestamp=float(fr["timestamp"][0]), first=bool(fr["first"][0])))
-        want[f"s{f}"] = [dict(sample_token=f"s{f}", translation=annos[r]["translation"], size=annos[r]["size"], rotation=annos[r]["rotation"], velocity=annos[r]["velocity"],
-                              tracking_id=str(int(e["track_id"][f, 0, r])), tracking_name=annos[r]["detection_name"], tracking_score=annos[r]["detection_score"]) for r in rows]
+        want[f"s{f}"] = TC.want_annos(annos, e, f, rows)
         # the numpy route of the detector's hook: the same dicts
         got = trk.records_to_annos(fr["rec"], fr["score"], fr["name"], e["track_id"][f], e["order"][f], e["num_out"][f], [f"s{f}"])
         assert got == [want[f"s{f}"]] and all(list(a) == list(tracking.TRACK_ANNO_KEYS) and isinstance(a["tracking_id"], str) for a in got[0])
@@ -293,32 +272,6 @@ def test_step_records_and_track_file_on_the_restatement(tmp_path):
 
 
 # ---- the detector's hook -------------------------------------------------------------------------------------------------------------------------------------------------
-class FakeBackbone(nn.Module):
-    pruning_loc, pruning_num_queries, patch_size, img_norm_cfg = [3, 6, 9], 64, 16, None
-
-    def forward(self, x, **kw):
-        return toc3d_amd.ToC3DViTReturnType({"last_feat": torch.zeros(x.shape[0], 8, 2, 5)}, ["m0", "m1", "m2"], None, ["k0", "k1", "k2"], ["d0", "d1", "d2"])
-
-
-class FakeHead(nn.Module):
-    embed_dims = 256
-
-    def backbone_queries(self, n, prev_exists, batch_size=1):
-        return dict(temp_queries=torch.zeros(batch_size, n, 256), temp_ref_points=None, temp_timestamp=None, temp_ego_pose=None, temp_vel=None, prev_exists=False)
-
-    def img_feats_rows_buffer(self, B, N, h, w, device=None):
-        return "rows", 64, lib.F32X3P
-
-    def reset_memory(self):
-        pass
-
-    def forward(self, memory_center, img_metas, topk_indexes=None, img_feats_rows=False, **data):
-        return dict(all_cls_scores="cls", all_bbox_preds="box", dn_mask_dict=None)
-
-    def get_bboxes(self, outs, img_metas, rescale=False):
-        return [[torch.full((3, 9), float(i)), torch.arange(3.0) + i, torch.arange(3) + i] for i, _ in enumerate(img_metas)]
-
-
 class FakeResults:
     class_names = TC.CLASS_NAMES
 
@@ -354,23 +307,12 @@ class FakeTracker:
         return self.inner.records_to_annos(*a)
 
 
-def fake_detector():
-    det = toc3d_amd.build_detector(synth.detector_cfg(synth.DETECTOR_TINY))
-    det.img_backbone, det.img_neck, det.pts_bbox_head = FakeBackbone(), FakeNeck([]), FakeHead()
-    return det
-
-
 def frame(det, tokens, scenes, t):
-    B = len(tokens)
-    metas = [dict(scene_token=s, pad_shape=[(32, 80, 3)], sample_idx=tok, lidar2ego_rotation=[1.0, 0, 0, 0], lidar2ego_translation=[0.0, 0, 0],
-                  ego2global_rotation=[1.0, 0, 0, 0], ego2global_translation=[0.0, 0, 0]) for tok, s in zip(tokens, scenes)]
-    data = dict(img=torch.zeros(B, 6, 3, 32, 80), intrinsics=torch.zeros(B, 6, 4, 4), lidar2img=torch.zeros(B, 6, 4, 4),
-                timestamp=torch.tensor([t + 7.0 * b for b in range(B)], dtype=torch.float64), ego_pose=torch.eye(4)[None].repeat(B, 1, 1), ego_pose_inv=torch.eye(4)[None].repeat(B, 1, 1))
-    return det.simple_test(metas, **data) if B == 1 else det.simple_test_streams(metas, **data)
+    return DC.frame(det, [DC.posed_meta(tok, s) for tok, s in zip(tokens, scenes)], t)
 
 
 def test_detector_hook_hands_over_timestamps_and_scene_starts(monkeypatch, tmp_path):
-    det = fake_detector()
+    det = DC.fake_detector()
     assert det.track_results is False and det.tracker is None and det.tracking_results == {}
     with pytest.raises(ValueError, match="enable_tracking needs the submission records it tracks: call enable_nusc_results\\(\\) first"):
         det.enable_tracking()

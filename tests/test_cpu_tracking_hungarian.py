@@ -9,13 +9,13 @@ import re
 import numpy as np
 import pytest
 import torch
-import torch.nn as nn
 
+import detector_cases as DC
 import tracking_cases as TC
 import tracking_hungarian_cases as HC
 import toc3d_amd
-from support import A, ERR_ARG, FakeNeck, header_sigs, raw_call
-from toc3d_amd import lib, synth, tracking
+from support import A, ERR_ARG, header_sigs, raw_call
+from toc3d_amd import lib, tracking
 
 ENTRY = "toc3d_tracks_step_hungarian"
 
@@ -203,18 +203,7 @@ def test_build_tracker_and_the_caps():
 
 
 def restated(tracker):
-    """The seam: PubTracker._step_host, the one place where the host half meets the device, replaced by the Hungarian restatement."""
-    streams = [HC.Tracker(tracker.max_age, tracker.track_label, [tracker.NUSCENE_CLS_VELOCITY_ERROR[n] for n in tracker.tracking_names]) for _ in range(tracker.num_streams)]
-    started = [False] * tracker.num_streams
-
-    def step_host(rec, score, name, kept, timestamps, first, thr):
-        outs, first = [], [False] * len(streams) if first is None else first
-        for b, s in enumerate(streams):
-            outs.append(s.step(rec[b], score[b], name[b], kept[b], timestamps[b], bool(first[b]) or not started[b], thr))
-            started[b] = True
-        return {k: np.stack([o[k] for o in outs]) for k in HC.OUT_KEYS}
-    tracker._step_host = step_host
-    return tracker
+    return TC.restated(tracker, HC.Tracker)
 
 
 def test_step_on_the_restatement():
@@ -230,32 +219,6 @@ def test_step_on_the_restatement():
 
 
 # ---- the detector's keyword ------------------------------------------------------------------------------------------------------------------------------------------
-class FakeBackbone(nn.Module):
-    pruning_loc, pruning_num_queries, patch_size, img_norm_cfg = [3, 6, 9], 64, 16, None
-
-    def forward(self, x, **kw):
-        return toc3d_amd.ToC3DViTReturnType({"last_feat": torch.zeros(x.shape[0], 8, 2, 5)}, ["m0", "m1", "m2"], None, ["k0", "k1", "k2"], ["d0", "d1", "d2"])
-
-
-class FakeHead(nn.Module):
-    embed_dims = 256
-
-    def backbone_queries(self, n, prev_exists, batch_size=1):
-        return dict(temp_queries=torch.zeros(batch_size, n, 256), temp_ref_points=None, temp_timestamp=None, temp_ego_pose=None, temp_vel=None, prev_exists=False)
-
-    def img_feats_rows_buffer(self, B, N, h, w, device=None):
-        return "rows", 64, lib.F32X3P
-
-    def reset_memory(self):
-        pass
-
-    def forward(self, memory_center, img_metas, topk_indexes=None, img_feats_rows=False, **data):
-        return dict(all_cls_scores="cls", all_bbox_preds="box", dn_mask_dict=None)
-
-    def get_bboxes(self, outs, img_metas, rescale=False):
-        return [[torch.full((3, 9), float(i)), torch.arange(3.0) + i, torch.arange(3) + i] for i, _ in enumerate(img_metas)]
-
-
 class FakeResults:
     """Three trucks a frame: the first moves a metre, the other two are far from every track in the second frame."""
     class_names = TC.CLASS_NAMES
@@ -296,8 +259,7 @@ class FakeHungarian:
 
 def test_enable_tracking_hungarian_builds_through_build_tracker(monkeypatch):
     from toc3d_amd import detector as D
-    det = toc3d_amd.build_detector(synth.detector_cfg(synth.DETECTOR_TINY))
-    det.img_backbone, det.img_neck, det.pts_bbox_head = FakeBackbone(), FakeNeck([]), FakeHead()
+    det = DC.fake_detector()
     det.enable_nusc_results()
     assert type(det.enable_tracking().tracker) is toc3d_amd.PubTracker and det.tracker.max_age == 3
     assert type(det.enable_tracking(hungarian=True, max_age=2).tracker) is toc3d_amd.HungarianPubTracker and det.tracker.max_age == 2
@@ -305,15 +267,10 @@ def test_enable_tracking_hungarian_builds_through_build_tracker(monkeypatch):
     assert det.enable_tracking(max_age=0, score_threshold=0.3, hungarian=True) is det
     assert isinstance(det.tracker, FakeHungarian) and det.tracker.kw == dict(max_age=0, class_names=TC.CLASS_NAMES), "hungarian chooses the class and is not handed on"
     det.nusc_results = FakeResults()
-    meta = lambda tok: dict(scene_token="a", pad_shape=[(32, 80, 3)], sample_idx=tok, lidar2ego_rotation=[1.0, 0, 0, 0], lidar2ego_translation=[0.0, 0, 0],
-                            ego2global_rotation=[1.0, 0, 0, 0], ego2global_translation=[0.0, 0, 0])
-    data = lambda B, t: dict(img=torch.zeros(B, 6, 3, 32, 80), intrinsics=torch.zeros(B, 6, 4, 4), lidar2img=torch.zeros(B, 6, 4, 4),
-                             timestamp=torch.tensor([t + 7.0 * b for b in range(B)], dtype=torch.float64), ego_pose=torch.eye(4)[None].repeat(B, 1, 1),
-                             ego_pose_inv=torch.eye(4)[None].repeat(B, 1, 1))
-    det.simple_test([meta("t0")], **data(1, 100.0))
-    det.simple_test([meta("t1")], **data(1, 100.5))
+    DC.frame(det, [DC.posed_meta("t0")], 100.0)
+    DC.frame(det, [DC.posed_meta("t1")], 100.5)
     assert det.tracker.calls == [([100.0], [True], 0.3), ([100.5], [False], 0.3)]
     assert [a["tracking_id"] for a in det.tracking_results["t1"]] == ["1", "4", "5"], "the first truck continued; those at 20 and 30 m are parked on the other two tracks and numbered anew"
     # another number of streams: the second place the detector builds a tracker, through build_tracker again
-    det.simple_test_streams([meta("u0"), meta("v0")], **data(2, 200.0))
+    DC.frame(det, [DC.posed_meta("u0"), DC.posed_meta("v0")], 200.0)
     assert isinstance(det.tracker, FakeHungarian) and det.tracker.num_streams == 2 and det.tracker.kw == dict(max_age=0, class_names=TC.CLASS_NAMES)

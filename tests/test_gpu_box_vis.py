@@ -10,26 +10,15 @@ import pytest
 import torch
 
 import box_vis_cases as BC
+import detector_cases as DC
 import toc3d_amd
 import token_vis_cases as TC
-from support import DEV, S, to_dev
+from support import DEV, S, guarded, to_dev, touched
 from toc3d_amd import lib, synth
 
 pytestmark = pytest.mark.gpu
-GUARD_BYTES, FILL = 256, 0xA5
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 THIN = 1.0                                   # a decision whose margin is below its own error bound may go the other way in float32
 dv = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def guarded(nbytes, off=0):
-    buf = torch.full((GUARD_BYTES + off + nbytes + GUARD_BYTES,), FILL, dtype=torch.uint8, device=DEV)
-    return buf, buf[GUARD_BYTES + off:GUARD_BYTES + off + nbytes]
-
-
-def touched(buf, nbytes, off=0):
-    host = buf.cpu().numpy()
-    return int((host[:GUARD_BYTES + off] != FILL).sum() + (host[GUARD_BYTES + off + nbytes:] != FILL).sum())
 
 
 # ---- the render, exact -----------------------------------------------------------------------------------------------------------------------------------------------
@@ -286,57 +275,11 @@ def test_six_views_at_the_shipped_size_and_the_same_call_twice():
 
 # ---- the detector ------------------------------------------------------------------------------------------------------------------------------------------------
 TINY = synth.DETECTOR_TINY
-BANK = ("memory_embedding", "memory_reference_point", "memory_timestamp", "memory_egopose", "memory_velo")
-_SD = {}
+run, assert_same_bits = DC.run, DC.assert_same_bits
 
 
 def build_detector(precision, norm=None):
-    cfg = synth.detector_cfg(TINY)
-    if norm is not None:
-        cfg["img_backbone"] = dict(cfg["img_backbone"], img_norm_cfg=norm)
-    det = toc3d_amd.build_detector(cfg, precision=precision)
-    if "sd" not in _SD:
-        _SD["sd"] = synth.detector_state_dict(TINY)
-    det.load_state_dict(_SD["sd"], strict=True)
-    det = det.to(DEV)
-    det.img_backbone.autotune = det.img_neck.autotune = False
-    tuned = os.path.join(ROOT, "toc3d_amd", "tuned", f"{TINY['backbone']}_320x800_{precision}.json")
-    if os.path.exists(tuned):
-        det.img_backbone.load_tuning(tuned)
-        det.img_neck._tuned.update(det.img_backbone._tuned)
-    return det
-
-
-def snapshot(det, outs, results, B):
-    last, N = det.last_frame, det.last_frame["img_feats"].shape[1]
-    res = []
-    for b in range(B):
-        res.append(dict(keep=[k[b * N:(b + 1) * N].clone() for k in last["keep_idxes"]], masks=[m[b * N:(b + 1) * N].clone() for m in last["token_masks"]],
-                        img_feats=last["img_feats"][b].clone(), out={k: outs[k][:, b].clone() for k in ("all_cls_scores", "all_bbox_preds")},
-                        bank={k: getattr(det.pts_bbox_head, k)[b].clone() for k in BANK}, dec=results[b]["pts_bbox"]))
-    return res
-
-
-def run(det, frames, streams=False):
-    seen, res = [], []
-    hook = det.pts_bbox_head.register_forward_hook(lambda m, a, out: seen.append(out))
-    try:
-        for fr in frames:
-            step = det.simple_test_streams if streams else det.simple_test
-            results = step(fr["img_metas"], gumbel_noise=fr["gumbel"], **fr["dev"])
-            res.append(snapshot(det, seen[-1], results, len(fr["img_metas"])))
-    finally:
-        hook.remove()
-    return res
-
-
-def assert_same_bits(a, b):
-    for f, (xs, ys) in enumerate(zip(a, b)):
-        for x, y in zip(xs, ys):
-            assert all(torch.equal(p, q) for p, q in zip(x["keep"], y["keep"])) and all(torch.equal(p, q) for p, q in zip(x["masks"], y["masks"])), f"frame {f}: kept sets"
-            assert torch.equal(x["img_feats"], y["img_feats"]), f"frame {f}: img_feats"
-            assert all(torch.equal(x["out"][k], y["out"][k]) for k in x["out"]) and all(torch.equal(x["bank"][k], y["bank"][k]) for k in BANK), f"frame {f}: head outputs, bank"
-            assert all(torch.equal(torch.as_tensor(x["dec"][k]), torch.as_tensor(y["dec"][k])) for k in ("boxes_3d", "scores_3d", "labels_3d")), f"frame {f}: decoded lists"
+    return DC.build_detector(TINY, precision, norm=norm)
 
 
 def check_files(folder, img, dec, l2i, norm, V=6):

@@ -13,18 +13,16 @@ and in f64, and on none of the seeds 0 .. 63 does the stream, or frame 0 alone, 
 misses its condition is not committed (the generator's docstring has the figures).  The parts are held to the reference by their own fixtures; (b) and (d) hold the
 detector to the parts.
 Every test prints the figures it asserts on (run with -s)."""
-import os
-
 import pytest
 import torch
 
+import detector_cases as DC
 import toc3d_amd
+from detector_cases import BANK, schedule, weights
 from support import DEV, to_dev
 from toc3d_amd import lib, synth
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BANK = ("memory_embedding", "memory_reference_point", "memory_timestamp", "memory_egopose", "memory_velo")
 TINY = synth.DETECTOR_TINY
 S = lambda: torch.cuda.current_stream().cuda_stream
 SENTINEL = -7.0
@@ -74,36 +72,8 @@ def test_a_fanout_kernel_bit_for_bit(name, shape):
 
 
 # ---- the detector and the chain ------------------------------------------------------------------------------------------------------------------------------
-_SD = {}
-
-
-def weights(sizes):
-    key = id(sizes)
-    if key not in _SD:
-        _SD[key] = synth.detector_state_dict(sizes)
-    return _SD[key]
-
-
-def tuning(sizes, precision):
-    return os.path.join(ROOT, "toc3d_amd", "tuned", f"{sizes['backbone']}_320x800_{precision}.json")
-
-
 def build_detector(sizes, precision, launch_mode="plan"):
-    cfg = synth.detector_cfg(sizes)
-    cfg["pts_bbox_head"]["launch_mode"] = launch_mode
-    det = toc3d_amd.build_detector(cfg, precision=precision)
-    det.load_state_dict(weights(sizes), strict=True)
-    det = det.to(DEV)
-    schedule(det.img_backbone, det.img_neck, sizes, precision, launch_mode)
-    return det
-
-
-def schedule(backbone, neck, sizes, precision, launch_mode):
-    backbone.launch_mode = neck.launch_mode = launch_mode
-    backbone.autotune = neck.autotune = False           # every tile variant accumulates in the same order; the shipped table where there is one
-    if os.path.exists(tuning(sizes, precision)):
-        backbone.load_tuning(tuning(sizes, precision))
-        neck._tuned.update(backbone._tuned)
+    return DC.build_detector(sizes, precision, launch_mode)
 
 
 def build_chain(sizes, precision, launch_mode="plan"):

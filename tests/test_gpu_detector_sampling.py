@@ -13,52 +13,27 @@ the scene change at frame 3, in "fp32x3" and "bf16", recorded and eager:
 There is no fixture of the reference's own ``Petr3D`` (tests/test_gpu_detector.py's docstring and DESIGN.md 4f: no seed meets the near-tie condition); the parts
 are held to the reference by their own fixtures (focal_head_*.npz, head_sampled_*.npz, tiny_toc3d_*.npz, tiny_neck.npz), these tests hold the detector to the parts.
 Every test prints the figures it asserts on (run with -s)."""
-import os
-
 import pytest
 import torch
 
+import detector_cases as DC
 import toc3d_amd
+from detector_cases import BANK, schedule, weights
 from support import DEV, same_bits, to_dev
 from toc3d_amd import synth
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BANK = ("memory_embedding", "memory_reference_point", "memory_timestamp", "memory_egopose", "memory_velo")
 TINY = synth.DETECTOR_TINY_ROI
 FULL = dict(synth.DETECTOR_FULL, roi=dict(infer_ratio=0.5))
 ROI_KEYS = ("enc_cls_scores", "enc_bbox_preds", "pred_centers2d", "centerness", "topk_indexes", "sample_weight")
-_SD = {}
-
-
-def weights(sizes):
-    key = id(sizes)
-    if key not in _SD:
-        _SD[key] = synth.detector_state_dict(sizes)
-    return _SD[key]
-
-
 def config(sizes, launch_mode):
     cfg = dict(synth.detector_cfg(sizes), aux_2d_only=False)
     cfg["pts_bbox_head"]["launch_mode"] = cfg["img_roi_head"]["launch_mode"] = launch_mode
     return cfg
 
 
-def schedule(backbone, neck, sizes, precision, launch_mode):
-    backbone.launch_mode = neck.launch_mode = launch_mode
-    backbone.autotune = neck.autotune = False           # every tile variant accumulates in the same order; the shipped table where there is one
-    path = os.path.join(ROOT, "toc3d_amd", "tuned", f"{sizes['backbone']}_320x800_{precision}.json")
-    if os.path.exists(path):
-        backbone.load_tuning(path)
-        neck._tuned.update(backbone._tuned)
-
-
 def build_detector(sizes, precision, launch_mode="plan"):
-    det = toc3d_amd.build_detector(config(sizes, launch_mode), precision=precision)
-    det.load_state_dict(weights(sizes), strict=True)
-    det = det.to(DEV)
-    schedule(det.img_backbone, det.img_neck, sizes, precision, launch_mode)
-    return det
+    return DC.build_detector(sizes, precision, launch_mode, cfg=config(sizes, launch_mode))
 
 
 def build_chain(sizes, precision, launch_mode="plan"):
@@ -87,44 +62,17 @@ def location_of(metas, feats):
     return torch.stack((xx.reshape(-1), yy.reshape(-1)), dim=1).reshape(h, w, 2)[None].repeat(bs * n, 1, 1, 1)
 
 
-def watch(det):
-    """Forward hook on the head -> the list of (topk_indexes, outputs) of every call."""
-    seen = []
-    hook = det.pts_bbox_head.register_forward_hook(lambda m, a, k, out: seen.append((a[2] if len(a) > 2 else k.get("topk_indexes"), out)), with_kwargs=True)
-    return seen, hook
-
-
-def snapshot(det, seen, results, B):
-    last, N = det.last_frame, det.last_frame["img_feats"].shape[1]
-    topk, outs = seen[-1]
-    return [dict(keep=[k[b * N:(b + 1) * N].clone() for k in last["keep_idxes"]], img_feats=last["img_feats"][b].clone(), topk=topk[b].clone(),
-                 out={k: outs[k][:, b].clone() for k in ("all_cls_scores", "all_bbox_preds")},
-                 bank={k: getattr(det.pts_bbox_head, k)[b].clone() for k in BANK}, dec=results[b]["pts_bbox"]) for b in range(B)]
+def check_result(f, det, data, result):
+    assert isinstance(result, list) and len(result) == 1 and set(result[0]) == {"pts_bbox"} and set(result[0]["pts_bbox"]) == {"boxes_3d", "scores_3d", "labels_3d"}
 
 
 def run_detector(det, frames):
-    seen, hook = watch(det)
-    res = []
-    try:
-        for fr in frames:
-            result = det.simple_test(fr["img_metas"], gumbel_noise=fr["gumbel"], **to_dev(fr))
-            assert isinstance(result, list) and len(result) == 1 and set(result[0]) == {"pts_bbox"} and set(result[0]["pts_bbox"]) == {"boxes_3d", "scores_3d", "labels_3d"}
-            res.append(snapshot(det, seen, result, 1)[0])
-    finally:
-        hook.remove()
-    return res
+    """-> per frame the snapshot of its one sample, ``topk`` (the head's topk_indexes) included."""
+    return [r[0] for r in DC.run(det, frames, on_frame=check_result)]
 
 
 def run_streams(det, steps):
-    seen, hook = watch(det)
-    res = []
-    try:
-        for st in steps:
-            results = det.simple_test_streams(st["img_metas"], gumbel_noise=st["gumbel"], **to_dev(st))
-            res.append(snapshot(det, seen, results, len(st["img_metas"])))
-    finally:
-        hook.remove()
-    return res
+    return DC.run(det, steps, streams=True)
 
 
 def run_chain(parts, frames):

@@ -178,7 +178,7 @@ def test_memory_scores(rows, classes):
 GUARD64 = 0x7FF8_7FC1_7FC1_7FC1                          # an f64 NaN pattern for the timestamps' guard slots
 
 
-def guarded(bank, L):
+def guarded_bank(bank, L):
     """The host bank on the device with the sentinel in every slot >= L -> (device bank, the bits it starts with)."""
     out = {}
     for k, t in bank.items():
@@ -213,7 +213,7 @@ def test_memory_pre_update(L):
         data = HC.frame_data(B, seed=L + npg)
         host = HC.memory_bank(B, cap, L, D, seed=L + 7 * npg + D, zero=bool(fresh))
         pseudo = torch.rand(max(npg, 1), 3, generator=torch.Generator().manual_seed(L + D))
-        bank, before = guarded(host, L)
+        bank, before = guarded_bank(host, L)
         x, ts, inv, pc = dev(data["prev"]), dev(data["ts"]), dev(data["ego_inv"]), dev(data["pc"])
         ps = dev(pseudo) if npg else None                 # num_propagated = 0: a null pointer
         lib.call("toc3d_memory_pre_update", bank["emb"], bank["ref"], bank["ts"], bank["pose"], bank["vel"], x, ts, inv, ps, pc, B, cap, L, npg, D, fresh, S())
@@ -235,7 +235,7 @@ def test_memory_post_update(topk):
         data = HC.frame_data(B, seed=Q + ld_bbox)
         host = HC.memory_bank(B, cap, L, D, seed=Q + L + D)
         dec = HC.post_update_inputs(B, Q, D, ld_bbox, seed=Q + topk + ld_bbox)
-        src, before = guarded(host, L)                     # slots >= memory_len of the in bank hold NaNs: nothing may read them into a result
+        src, before = guarded_bank(host, L)                     # slots >= memory_len of the in bank hold NaNs: nothing may read them into a result
         rows = B * cap
         out = dict(emb=sent(rows + G, D), ref=sent(rows + G, 3), pose=sent(rows + G, 16), vel=sent(rows + G, 2),
                    ts=torch.full((rows + G,), GUARD64, dtype=torch.int64, device=DEV).view(torch.float64))

@@ -3,6 +3,7 @@ inputs and the float64 restatement's outputs) -- kept, src, name, attr and the s
 bound derived in that module, at 0, 1, 63 / 64 / 65, 256 / 257 and 2048 boxes a sample with every keep pattern; row and sample strides; guard bytes around every
 output; the same call twice; the class on top of it; and the detector with the records switched on against one without, bit for bit, in both precisions and for a
 step of two streams.  Every test prints the figures it asserts on (run with -s)."""
+import functools
 import math
 import os
 
@@ -10,28 +11,17 @@ import numpy as np
 import pytest
 import torch
 
+import detector_cases as DC
 import nusc_results_cases as NC
 import toc3d_amd
-from support import DEV, S, to_dev, worst_report
+from support import DEV, S, guarded, to_dev, touched, worst_report
 from toc3d_amd import lib, synth
 
 pytestmark = pytest.mark.gpu
-GUARD_BYTES, FILL = 256, 0xA5
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY = "toc3d_boxes_to_global"
 OUT_DTYPES = dict(rec=np.float64, score=np.float32, name=np.int32, attr=np.int32, src=np.int32, kept=np.int64)
 note, _report = worst_report("nuScenes records", 44)
 dv = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def guarded(nbytes):
-    buf = torch.full((GUARD_BYTES + nbytes + GUARD_BYTES,), FILL, dtype=torch.uint8, device=DEV)
-    return buf, buf[GUARD_BYTES:GUARD_BYTES + nbytes]
-
-
-def touched(buf, nbytes):
-    host = buf.cpu().numpy()
-    return int((host[:GUARD_BYTES] != FILL).sum() + (host[GUARD_BYTES + nbytes:] != FILL).sum())
 
 
 def launch(c, box_stride=9, sample_pad=0, with_velocity=None, poses=None):
@@ -191,60 +181,8 @@ def test_format_fixed_and_format():
 
 # ---- the detector ------------------------------------------------------------------------------------------------------------------------------------------------
 TINY = synth.DETECTOR_TINY
-BANK = ("memory_embedding", "memory_reference_point", "memory_timestamp", "memory_egopose", "memory_velo")
-_SD = {}
-
-
-def build_detector(precision):
-    det = toc3d_amd.build_detector(synth.detector_cfg(TINY), precision=precision)
-    if "sd" not in _SD:
-        _SD["sd"] = synth.detector_state_dict(TINY)
-    det.load_state_dict(_SD["sd"], strict=True)
-    det = det.to(DEV)
-    det.img_backbone.autotune = det.img_neck.autotune = False
-    tuned = os.path.join(ROOT, "toc3d_amd", "tuned", f"{TINY['backbone']}_320x800_{precision}.json")
-    if os.path.exists(tuned):
-        det.img_backbone.load_tuning(tuned)
-        det.img_neck._tuned.update(det.img_backbone._tuned)
-    return det
-
-
-def snapshot(det, outs, results, B):
-    last, N = det.last_frame, det.last_frame["img_feats"].shape[1]
-    res = []
-    for b in range(B):
-        res.append(dict(keep=[k[b * N:(b + 1) * N].clone() for k in last["keep_idxes"]], masks=[m[b * N:(b + 1) * N].clone() for m in last["token_masks"]],
-                        img_feats=last["img_feats"][b].clone(), out={k: outs[k][:, b].clone() for k in ("all_cls_scores", "all_bbox_preds")},
-                        bank={k: getattr(det.pts_bbox_head, k)[b].clone() for k in BANK}, dec=results[b]["pts_bbox"]))
-    return res
-
-
-def run(det, frames, streams=False):
-    seen, res = [], []
-    hook = det.pts_bbox_head.register_forward_hook(lambda m, a, out: seen.append(out))
-    try:
-        for fr in frames:
-            step = det.simple_test_streams if streams else det.simple_test
-            results = step(fr["img_metas"], gumbel_noise=fr["gumbel"], **fr["dev"])
-            res.append(snapshot(det, seen[-1], results, len(fr["img_metas"])))
-    finally:
-        hook.remove()
-    return res
-
-
-def assert_same_bits(a, b):
-    for f, (xs, ys) in enumerate(zip(a, b)):
-        for x, y in zip(xs, ys):
-            assert all(torch.equal(p, q) for p, q in zip(x["keep"], y["keep"])) and all(torch.equal(p, q) for p, q in zip(x["masks"], y["masks"])), f"frame {f}: kept sets"
-            assert torch.equal(x["img_feats"], y["img_feats"]), f"frame {f}: img_feats"
-            assert all(torch.equal(x["out"][k], y["out"][k]) for k in x["out"]) and all(torch.equal(x["bank"][k], y["bank"][k]) for k in BANK), f"frame {f}: head outputs, bank"
-            assert all(torch.equal(torch.as_tensor(x["dec"][k]), torch.as_tensor(y["dec"][k])) for k in ("boxes_3d", "scores_3d", "labels_3d")), f"frame {f}: decoded lists"
-
-
-def with_pose(meta, token, seed):
-    """A frame's meta with the four keys of a nuScenes info record (any rotations; the vehicle a few hundred metres from the map's origin) and its sample token."""
-    p = NC.random_poses(np.random.default_rng(seed), 1)
-    return dict(meta, sample_idx=token, **NC.pose_records(p)[0])
+build_detector = functools.partial(DC.build_detector, TINY)
+run, assert_same_bits, with_pose = DC.run, DC.assert_same_bits, DC.with_pose
 
 
 def independent(dec, meta, token):

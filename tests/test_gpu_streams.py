@@ -16,19 +16,17 @@
     sample's bank after every step and the decoded lists, bit for bit, in fp32x3 and bf16, plan and eager; the same streams run twice give the same bits, and
     ``reset_streams([1])`` makes stream 1's next step a first frame.
 Every test prints the figures it asserts on (run with -s)."""
-import os
-
 import pytest
 import torch
 
+import detector_cases as DC
 import scorer_cases as SC
 import toc3d_amd
 from oracle import toc3d_oracle as O
-from support import DEV, iou, rel_max, to_dev
+from support import DEV, iou, rel_max
 from toc3d_amd import configs, lib, synth
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 S = lambda: torch.cuda.current_stream().cuda_stream
 SENTINEL = 0x7FC0BEEF                         # a NaN no kernel produces: the buffers are compared as bits
 
@@ -177,68 +175,24 @@ def test_b_uniform_lists_are_the_single_bool(precision, launch_mode):
 
 # ---- (c) the detector --------------------------------------------------------------------------------------------------------------------------------------------
 TINY = synth.DETECTOR_TINY
-BANK = ("memory_embedding", "memory_reference_point", "memory_timestamp", "memory_egopose", "memory_velo")
-_SD = {}
-
-
-def weights():
-    if "sd" not in _SD:
-        _SD["sd"] = synth.detector_state_dict(TINY)
-    return _SD["sd"]
+BANK = DC.BANK
 
 
 def build_detector(precision, launch_mode="plan"):
-    cfg = synth.detector_cfg(TINY)
-    cfg["pts_bbox_head"]["launch_mode"] = launch_mode
-    det = toc3d_amd.build_detector(cfg, precision=precision)
-    det.load_state_dict(weights(), strict=True)
-    det = det.to(DEV)
-    for part in (det.img_backbone, det.img_neck):
-        part.launch_mode, part.autotune = launch_mode, False          # every tile variant accumulates in the same order
-    path = os.path.join(ROOT, "toc3d_amd", "tuned", f"{TINY['backbone']}_320x800_{precision}.json")
-    if os.path.exists(path):                                          # the shipped table where there is one, as tests/test_gpu_detector.py
-        det.img_backbone.load_tuning(path)
-        det.img_neck._tuned.update(det.img_backbone._tuned)
-    return det
+    return DC.build_detector(TINY, precision, launch_mode)
 
 
-def snapshot(det, outs, results, B):
-    """Per sample: (kept sets, img_feats, head outputs, bank, decoded lists) of the step the detector just ran."""
-    last, N = det.last_frame, det.last_frame["img_feats"].shape[1]
-    res = []
-    for b in range(B):
-        res.append(dict(keep=[k[b * N:(b + 1) * N].clone() for k in last["keep_idxes"]], img_feats=last["img_feats"][b].clone(),
-                        out={k: outs[k][:, b].clone() for k in ("all_cls_scores", "all_bbox_preds")},
-                        bank={k: getattr(det.pts_bbox_head, k)[b].clone() for k in BANK}, dec=results[b]["pts_bbox"]))
-    return res
+def check_results(f, det, data, results):
+    B = data["img"].shape[0]
+    assert isinstance(results, list) and len(results) == B and all(set(r) == {"pts_bbox"} for r in results)
 
 
 def run_streams(det, steps):
-    seen = []
-    hook = det.pts_bbox_head.register_forward_hook(lambda m, a, out: seen.append(out))
-    res = []
-    try:
-        for st in steps:
-            B = len(st["img_metas"])
-            results = det.simple_test_streams(st["img_metas"], gumbel_noise=st["gumbel"], **to_dev(st))
-            assert isinstance(results, list) and len(results) == B and all(set(r) == {"pts_bbox"} for r in results)
-            res.append(snapshot(det, seen[-1], results, B))
-    finally:
-        hook.remove()
-    return res
+    return DC.run(det, steps, streams=True, on_frame=check_results)
 
 
 def run_single(det, frames):
-    seen = []
-    hook = det.pts_bbox_head.register_forward_hook(lambda m, a, out: seen.append(out))
-    res = []
-    try:
-        for fr in frames:
-            results = det.simple_test(fr["img_metas"], gumbel_noise=fr["gumbel"], **to_dev(fr))
-            res.append(snapshot(det, seen[-1], results, 1)[0])
-    finally:
-        hook.remove()
-    return res
+    return [r[0] for r in DC.run(det, frames)]
 
 
 def assert_same(tag, x, y):

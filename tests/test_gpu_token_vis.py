@@ -11,28 +11,17 @@ import numpy as np
 import pytest
 import torch
 
+import detector_cases as DC
 import toc3d_amd
 import token_vis_cases as TC
-from support import DEV, S, to_dev
+from support import DEV, S, guarded, to_dev, touched
 from toc3d_amd import lib, synth
 
 pytestmark = pytest.mark.gpu
-GUARD, FILL = 256, 0xA5
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # (source offset, source row padding, destination offset) in bytes.  Contiguous; source rows padded by 4 (dwords still) and by 5 (bytes); a source base off by 1
 # byte (an f32 source: off by 4, which leaves the 16-byte form); a destination base off by 4 (one pixel a thread, a dword per RGBA pixel); everything odd (bytes)
 LAYOUTS = ((0, 0, 0), (0, 4, 0), (0, 5, 0), (1, 0, 0), (0, 0, 4), (1, 5, 1))
-
-
-def guarded(nbytes, off=0):
-    buf = torch.full((GUARD + off + nbytes + GUARD,), FILL, dtype=torch.uint8, device=DEV)
-    return buf, buf[GUARD + off:GUARD + off + nbytes]
-
-
-def touched(buf, nbytes, off=0):
-    host = buf.cpu().numpy()
-    return int((host[:GUARD + off] != FILL).sum() + (host[GUARD + off + nbytes:] != FILL).sum())
 
 
 def pipeline(inp, c, form, layout=(0, 0, 0), with_keep=True):
@@ -238,53 +227,22 @@ def test_the_same_call_twice_gives_the_same_bytes(big):
 
 # ---- the detector ------------------------------------------------------------------------------------------------------------------------------------------------
 TINY = synth.DETECTOR_TINY
-BANK = ("memory_embedding", "memory_reference_point", "memory_timestamp", "memory_egopose", "memory_velo")
-_SD = {}
+assert_same_bits = DC.assert_same_bits
 
 
 def build_detector(precision, norm=None):
-    cfg = synth.detector_cfg(TINY)
-    if norm is not None:
-        cfg["img_backbone"] = dict(cfg["img_backbone"], img_norm_cfg=norm)
-    det = toc3d_amd.build_vis_detector(cfg, precision=precision)
-    if "sd" not in _SD:
-        _SD["sd"] = synth.detector_state_dict(TINY)
-    det.load_state_dict(_SD["sd"], strict=True)
-    det = det.to(DEV)
-    det.img_backbone.autotune = det.img_neck.autotune = False
-    tuned = os.path.join(ROOT, "toc3d_amd", "tuned", f"{TINY['backbone']}_320x800_{precision}.json")
-    if os.path.exists(tuned):
-        det.img_backbone.load_tuning(tuned)
-        det.img_neck._tuned.update(det.img_backbone._tuned)
-    return det
+    return DC.build_detector(TINY, precision, norm=norm, builder=toc3d_amd.build_vis_detector)
 
 
 def run(det, frames, at=None):
     """simple_test over the frames -> per frame what must keep its bits; ``at``: the frame whose last_frame tensors and image are brought to the host."""
-    seen, res, kept = [], [], None
-    hook = det.pts_bbox_head.register_forward_hook(lambda m, a, out: seen.append(out))
-    try:
-        for f, fr in enumerate(frames):
-            data = fr["dev"]
-            result = det.simple_test(fr["img_metas"], gumbel_noise=fr["gumbel"], **data)
-            last = det.last_frame
-            res.append(dict(keep=[k.clone() for k in last["keep_idxes"]], masks=[m.clone() for m in last["token_masks"]], img_feats=last["img_feats"].clone(),
-                            out={k: seen[-1][k].clone() for k in ("all_cls_scores", "all_bbox_preds")}, bank={k: getattr(det.pts_bbox_head, k).clone() for k in BANK},
-                            dec=result[0]["pts_bbox"]))
-            if f == at:
-                cpu = lambda ts: [t.cpu().numpy() for t in ts]
-                kept = dict(img=data["img"].cpu().numpy(), masks=cpu(last["token_masks"]), keeps=cpu(last["keep_idxes"]), drops=cpu(last["drop_idxes"]))
-    finally:
-        hook.remove()
-    return res, kept
+    kept = {}
 
-
-def assert_same_bits(a, b):
-    for f, (x, y) in enumerate(zip(a, b)):
-        assert all(torch.equal(p, q) for p, q in zip(x["keep"], y["keep"])) and all(torch.equal(p, q) for p, q in zip(x["masks"], y["masks"])), f"frame {f}: kept sets"
-        assert torch.equal(x["img_feats"], y["img_feats"]), f"frame {f}: img_feats"
-        assert all(torch.equal(x["out"][k], y["out"][k]) for k in x["out"]) and all(torch.equal(x["bank"][k], y["bank"][k]) for k in BANK), f"frame {f}: head outputs, bank"
-        assert all(torch.equal(torch.as_tensor(x["dec"][k]), torch.as_tensor(y["dec"][k])) for k in ("boxes_3d", "scores_3d", "labels_3d")), f"frame {f}: decoded lists"
+    def on_frame(f, det, data, results):
+        if f == at:
+            last, cpu = det.last_frame, lambda ts: [t.cpu().numpy() for t in ts]
+            kept.update(img=data["img"].cpu().numpy(), masks=cpu(last["token_masks"]), keeps=cpu(last["keep_idxes"]), drops=cpu(last["drop_idxes"]))
+    return DC.run(det, frames, on_frame=on_frame), kept or None
 
 
 def check_files(tmp_path, files, V, L):

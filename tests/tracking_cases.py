@@ -1,5 +1,6 @@
 """The cases of the tracking tests and a numpy restatement of the step (include/toc3d_tracks.h, points 0-6), shared by tests/test_cpu_tracking.py,
-tests/test_gpu_tracking.py, tools/gen_golden_tracking.py and tools/tracking_time.py.
+tests/test_gpu_tracking.py, tools/gen_golden_tracking.py and tools/tracking_time.py, and the base of tests/tracking_hungarian_cases.py, which replaces the
+assignment alone.  Beside them: the bytes of a state (``state_to_bytes``, ``bytes_to_state``), the records of a case and the seam the host class is tested through.
 
 The fixture (tests/golden/tracking_cases.npz, written by tools/gen_golden_tracking.py where the reference tree exists) holds what the REFERENCE's PubTracker
 returned and held on these cases: per frame and stream the rows in output order with their ids and active counts, and the tracks after the frame.  The inputs are
@@ -22,7 +23,9 @@ TRACKING_NAMES = ("car", "truck", "bus", "trailer", "motorcycle", "bicycle", "pe
 MAX_DIFF = 2.5
 REC = 12
 OUT_KEYS = ("track_id", "active", "order", "num_out")
-STATE_KEYS = ("ct", "tracking", "label", "tracking_id", "age", "active")
+HEADER_BYTES = 32                        # TOC3D_TRACKS_HEADER_BYTES
+STATE_FIELDS = (("ct", 16), ("tracking", 16), ("label", 4), ("tracking_id", 4), ("age", 4), ("active", 4))      # a state's fields in its byte order, bytes per track
+STATE_KEYS = tuple(k for k, _ in STATE_FIELDS)
 STATE_DTYPES = dict(ct=np.float64, tracking=np.float64, label=np.int32, tracking_id=np.int32, age=np.int32, active=np.int32)
 FULL_STATE_ROWS = 600                    # a case whose frames hold at most this many tracks in all has them stored in full
 CAR, TRUCK, CONSTRUCTION, BUS, TRAILER, BARRIER, MOTORCYCLE, BICYCLE, PEDESTRIAN, CONE = range(10)
@@ -54,6 +57,7 @@ def state_digest(state):
 class Tracker:
     """One stream's tracker, restated: one vector operation over the tracks per detection.  The float32 distance is made of numpy float32 array operations, each
     rounded once (numpy fuses nothing)."""
+    EXTRA_OUT = {}                           # outputs beyond OUT_KEYS, with the values an empty frame leaves them at
 
     def __init__(self, max_age, track_label=None, max_diff=None):
         self.max_age = int(max_age)
@@ -67,6 +71,19 @@ class Tracker:
         self.last = float(last)
 
     def step(self, rec, score, name, kept, timestamp, first, score_thr):
+        """The step in the three parts csrc/tracks_steps.h has: the filter, the assignment, the state write."""
+        self.seen = None                                                    # what an assignment that records its view of the frame leaves behind
+        out, found = self._filter(rec, score, name, kept, timestamp, first, score_thr)
+        if found is None:
+            return out
+        match, taken, late, extras = self._assign(found["p"], found["q"], found["dl"], self.state)
+        out.update(extras)
+        self._write(out, found, match, taken, late)
+        return out
+
+    def _filter(self, rec, score, name, kept, timestamp, first, score_thr):
+        """Points 0-2: the scene start, the time lag, the rows that survive -> (blank outputs, None on an empty frame, else the surviving rows ``rows``, their
+        centres ``ct``, displacements ``tracking`` and labels ``dl``, and the float32 positions the distance is taken between: ``p`` predicted, ``q`` held)."""
         K = len(score)
         if first:
             self.state, self.last = empty_state(), float(timestamp)
@@ -82,19 +99,23 @@ class Tracker:
         keep = lab >= 0
         keep[:n] &= ~(np.asarray(score[:n], dtype=np.float32).astype(np.float64) < np.float64(score_thr))
         rows = np.nonzero(keep)[0]
-        N, M = len(rows), len(s["label"])
-        out = dict(track_id=np.zeros(K, np.int32), active=np.zeros(K, np.int32), order=np.full(K, -1, np.int32), num_out=np.int64(N))
+        N = len(rows)
+        out = dict(track_id=np.zeros(K, np.int32), active=np.zeros(K, np.int32), order=np.full(K, -1, np.int32), num_out=np.int64(N), **self.EXTRA_OUT)
         if N == 0:                                                          # the empty-frame quirk: nothing is dropped, the old tracks are left as they are
             young = s["age"] < self.max_age
             s["ct"][young] = s["ct"][young] + s["tracking"][young] * -1.0
             s["age"][young] += 1
             s["active"][young] = 0
-            return out
+            return out, None
         ct = np.asarray(rec, dtype=np.float64)[rows, 0:2]
         tracking = (np.asarray(rec, dtype=np.float64)[rows, 10:12] * -1.0) * lag
         p = (ct + tracking.astype(np.float32).astype(np.float64)).astype(np.float32)
-        q = s["ct"].astype(np.float32)
-        dl = lab[rows].astype(np.int32)
+        return out, dict(rows=rows, ct=ct, tracking=tracking, p=p, q=s["ct"].astype(np.float32), dl=lab[rows].astype(np.int32))
+
+    def _assign(self, p, q, dl, state):
+        """Points 3-4, greedy: a detection takes the nearest free track of its label within the gate -> (the track of each detection or -1, the tracks taken, the
+        unmatched detections that are numbered last -- none here --, further outputs)."""
+        N, M = len(p), len(state["label"])
         match = np.full(N, -1, dtype=np.int64)
         taken = np.zeros(M, dtype=bool)
         if M:
@@ -103,39 +124,111 @@ class Tracker:
                     dx, dy = q[:, 0] - p[i, 0], q[:, 1] - p[i, 1]
                     d = np.sqrt(dx * dx + dy * dy)
                     assert d.dtype == np.float32
-                    idx = np.nonzero((s["label"] == dl[i]) & (d <= self.max_diff[dl[i]]) & ~taken)[0]
+                    idx = np.nonzero((state["label"] == dl[i]) & (d <= self.max_diff[dl[i]]) & ~taken)[0]
                     if len(idx):
                         j = idx[np.argmin(d[idx])]                          # the first of the smallest: the lowest track index
                         match[i], taken[j] = j, True
+        return match, taken, np.zeros(N, dtype=bool), {}
+
+    def _write(self, out, found, match, taken, late):
+        """Points 5-6: the new state -- matches in detection order, then the unmatched detections, those in ``late`` behind the others, then the old tracks that
+        stay -- and the outputs."""
+        s, rows, ct, tracking, dl = self.state, found["rows"], found["ct"], found["tracking"], found["dl"]
+        N = len(rows)
         hit = match >= 0
-        seq = np.concatenate([np.nonzero(hit)[0], np.nonzero(~hit)[0]])    # matches in detection order, then the unmatched detections
-        nu = int((~hit).sum())
-        ids = np.empty(N, np.int32)
-        act = np.empty(N, np.int32)
+        seq = np.concatenate([np.nonzero(hit)[0], np.nonzero(~hit & ~late)[0], np.nonzero(late)[0]])
+        nu = N - int(hit.sum())
+        ids, act = np.empty(N, np.int32), np.empty(N, np.int32)
         ids[hit], act[hit] = s["tracking_id"][match[hit]], s["active"][match[hit]] + 1
-        ids[~hit], act[~hit] = s["id_count"] + 1 + np.arange(nu, dtype=np.int32), 1
+        ids[seq[N - nu:]], act[~hit] = s["id_count"] + 1 + np.arange(nu, dtype=np.int32), 1
         stay = ~taken & (s["age"] < self.max_age)
         self.state = dict(ct=np.concatenate([ct[seq], s["ct"][stay] + s["tracking"][stay] * -1.0]), tracking=np.concatenate([tracking[seq], s["tracking"][stay]]),
                           label=np.concatenate([dl[seq], s["label"][stay]]), tracking_id=np.concatenate([ids[seq], s["tracking_id"][stay]]),
                           age=np.concatenate([np.ones(N, np.int32), s["age"][stay] + 1]), active=np.concatenate([act[seq], np.zeros(int(stay.sum()), np.int32)]),
                           id_count=int(s["id_count"]) + nu)
         out["track_id"][rows], out["active"][rows], out["order"][:N] = ids, act, rows[seq]
-        return out
 
 
-def run_case(c, streams=None):
-    """The restatement over a case -> (outputs [frame][stream], states after [frame][stream])."""
+def run_case(c, streams=None, on_step=None, tracker=Tracker):
+    """The restatement ``tracker`` over a case -> (outputs [frame][stream], states after [frame][stream]).  ``on_step(f, b, tracker)`` sees a stream's tracker
+    after each step."""
     B = c["B"]
     streams = range(B) if streams is None else streams
-    trackers = {b: Tracker(c["max_age"]) for b in streams}
+    trackers = {b: tracker(c["max_age"]) for b in streams}
     if c.get("init") is not None:
         for b in streams:
             trackers[b].set_state(c["init"][b], c["init_last"][b])
     outs, states = [], []
-    for fr in c["frames"]:
+    for f, fr in enumerate(c["frames"]):
         outs.append([trackers[b].step(fr["rec"][b], fr["score"][b], fr["name"][b], fr["kept"][b], fr["timestamp"][b], fr["first"][b], c["thr"]) for b in streams])
         states.append([{k: (v.copy() if hasattr(v, "copy") else v) for k, v in trackers[b].state.items()} for b in streams])
+        if on_step is not None:
+            for b in streams:
+                on_step(f, b, trackers[b])
     return outs, states
+
+
+def restated(tracker, restatement=Tracker):
+    """The seam: PubTracker._step_host, the one place where the host half of ``tracker`` meets the device, replaced by the restatement."""
+    streams = [restatement(tracker.max_age, tracker.track_label, [tracker.NUSCENE_CLS_VELOCITY_ERROR[n] for n in tracker.tracking_names]) for _ in range(tracker.num_streams)]
+    started = [False] * tracker.num_streams
+
+    def step_host(rec, score, name, kept, timestamps, first, thr):
+        outs, first = [], [False] * len(streams) if first is None else first
+        for b, s in enumerate(streams):
+            outs.append(s.step(rec[b], score[b], name[b], kept[b], timestamps[b], bool(first[b]) or not started[b], thr))
+            started[b] = True
+        return {k: np.stack([o[k] for o in outs]) for k in OUT_KEYS + tuple(restatement.EXTRA_OUT)}
+    tracker._step_host = step_host
+    return tracker
+
+
+# ---- the state's bytes (include/toc3d_tracks.h) ---------------------------------------------------------------------------------------------------------------------------
+def state_bytes(cap):
+    return HEADER_BYTES + sum(size for _, size in STATE_FIELDS) * cap
+
+
+def state_to_bytes(state, last, cap):
+    """A state dict -> the bytes of include/toc3d_tracks.h."""
+    n = len(state["label"])
+    raw = np.zeros(state_bytes(cap), dtype=np.uint8)
+    raw[0:8].view(np.int32)[:] = [n, state["id_count"]]
+    raw[8:16].view(np.float64)[0] = last
+    at = HEADER_BYTES
+    for k, size in STATE_FIELDS:
+        raw[at:at + size * n] = np.ascontiguousarray(state[k], dtype=STATE_DTYPES[k]).reshape(-1).view(np.uint8)
+        at += size * cap
+    return raw
+
+
+def bytes_to_state(raw, cap):
+    """-> (state dict of the live rows, last_timestamp, bytes that should be zero and are not: the header's padding and every row at or beyond count)."""
+    n, id_count = raw[0:8].view(np.int32).tolist()
+    assert 0 <= n <= cap
+    dirty = int((raw[16:32] != 0).sum())
+    state, at = dict(id_count=id_count), HEADER_BYTES
+    for k, size in STATE_FIELDS:
+        field = raw[at:at + size * cap]
+        live = field[:size * n].view(STATE_DTYPES[k])
+        state[k] = live.reshape(-1, 2).copy() if size == 16 else live.copy()
+        dirty += int((field[size * n:] != 0).sum())
+        at += size * cap
+    return state, float(raw[8:16].view(np.float64)[0]), dirty
+
+
+# ---- records ----------------------------------------------------------------------------------------------------------------------------------------------------------------
+def case_annos(c, f, b):
+    """The submission records of a case's frame f, stream b: the rows below ``kept``."""
+    fr = c["frames"][f]
+    return [dict(sample_token=f"s{f}", translation=fr["rec"][b, i, 0:3].tolist(), size=fr["rec"][b, i, 3:6].tolist(), rotation=fr["rec"][b, i, 6:10].tolist(),
+                 velocity=fr["rec"][b, i, 10:12].tolist(), detection_name=CLASS_NAMES[int(fr["name"][b, i])], detection_score=float(fr["score"][b, i]),
+                 attribute_name="") for i in range(int(fr["kept"][b]))]
+
+
+def want_annos(annos, e, f, rows):
+    """The tracking records the reference makes of frame f's records ``annos`` (stream 0), in its output order ``rows``."""
+    return [dict(sample_token=f"s{f}", translation=annos[r]["translation"], size=annos[r]["size"], rotation=annos[r]["rotation"], velocity=annos[r]["velocity"],
+                 tracking_id=str(int(e["track_id"][f, 0, r])), tracking_name=annos[r]["detection_name"], tracking_score=annos[r]["detection_score"]) for r in rows]
 
 
 # ---- the cases ---------------------------------------------------------------------------------------------------------------------------------------------------------
@@ -391,11 +484,12 @@ def pack_expected(prefix, outs, states, arrays):
 _EXPECTED = {}
 
 
-def expected(name):
-    """What the reference returned and held -> dict(track_id, active, order [F, B, K], num_out, count, id_count [F, B], digest [F, B, 32], states [f][b] or None)."""
-    if name not in _EXPECTED:
-        z = np.load(FIXTURE)
-        e = {k: z[f"{name}/{k}"] for k in ("track_id", "active", "order", "num_out", "count", "id_count", "digest")}
+def expected(name, fixture=FIXTURE, extra=()):
+    """What the reference returned and held -> dict(track_id, active, order [F, B, K], num_out, count, id_count [F, B], digest [F, B, 32], states [f][b] or None),
+    and the arrays ``extra`` names, as the fixture has them."""
+    if (fixture, name) not in _EXPECTED:
+        z = np.load(fixture)
+        e = {k: z[f"{name}/{k}"] for k in ("track_id", "active", "order", "num_out", "count", "id_count", "digest") + tuple(extra)}
         e["states"] = None
         if f"{name}/state_ct" in z.files:
             F, B = e["count"].shape
@@ -407,8 +501,8 @@ def expected(name):
                     m = int(e["count"][f, b])
                     e["states"][f].append(dict({k: flat[k][at:at + m] for k in STATE_KEYS}, id_count=int(e["id_count"][f, b])))
                     at += m
-        _EXPECTED[name] = e
-    return _EXPECTED[name]
+        _EXPECTED[(fixture, name)] = e
+    return _EXPECTED[(fixture, name)]
 
 
 def compare_state(tag, got, e, f, b):

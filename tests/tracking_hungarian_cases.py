@@ -1,6 +1,6 @@
 """The cases of the Hungarian tracking tests and a numpy restatement of the step (include/toc3d_assign.h: points 0-3 and 6 of include/toc3d_tracks.h, points 4h
 and 5h), shared by tests/test_cpu_tracking_hungarian.py, tests/test_gpu_tracking_hungarian.py, tools/gen_golden_tracking_hungarian.py and
-tools/tracking_hungarian_time.py.  Built on tests/tracking_cases.py, which is imported and left as it is.
+tools/tracking_hungarian_time.py.  Built on tests/tracking_cases.py: its Tracker with another ``_assign``, its ``run_case`` and its fixture reader.
 
 The fixture (tests/golden/tracking_hungarian_cases.npz, written by tools/gen_golden_tracking_hungarian.py where the reference tree and scipy exist) holds what the
 REFERENCE's PubTracker(hungarian=True) returned and held on these cases, per frame and stream, laid out as the greedy fixture is, and beside it the scan rounds of
@@ -116,85 +116,33 @@ def has_ties(cost, valid):
 
 
 class Tracker(TC.Tracker):
-    """One stream's tracker with ``hungarian=True``, restated.  ``seen``: what the last step saw where it had both detections and tracks (the matrix, the
-    matches), for the generator's flags; ``None`` otherwise."""
+    """One stream's tracker with ``hungarian=True``, restated: the greedy step with another assignment.  ``seen``: what the last step saw where it had both
+    detections and tracks (the matrix, the matches), for the generator's flags; ``None`` otherwise."""
+    EXTRA_OUT = dict(rounds=np.int32(0))
 
-    def step(self, rec, score, name, kept, timestamp, first, score_thr):
-        K = len(score)
-        if first:
-            self.state, self.last = TC.empty_state(), float(timestamp)
-        lag = np.float64(timestamp) - np.float64(self.last)
-        self.last = float(timestamp)
-        self.seen = None
-        s = self.state
-        n = int(min(max(int(kept), 0), K))
-        lab = np.full(K, -1, dtype=np.int64)
-        nm = np.asarray(name[:n], dtype=np.int64)
-        ok = (nm >= 0) & (nm < len(self.track_label))
-        lab[:n][ok] = self.track_label[nm[ok]]
-        lab[(lab < 0) | (lab >= len(self.max_diff))] = -1
-        keep = lab >= 0
-        keep[:n] &= ~(np.asarray(score[:n], dtype=np.float32).astype(np.float64) < np.float64(score_thr))
-        rows = np.nonzero(keep)[0]
-        N, M = len(rows), len(s["label"])
-        out = dict(track_id=np.zeros(K, np.int32), active=np.zeros(K, np.int32), order=np.full(K, -1, np.int32), num_out=np.int64(N), rounds=np.int32(0))
-        if N == 0:                                                          # the empty-frame quirk, as in the greedy step
-            young = s["age"] < self.max_age
-            s["ct"][young] = s["ct"][young] + s["tracking"][young] * -1.0
-            s["age"][young] += 1
-            s["active"][young] = 0
-            return out
-        ct = np.asarray(rec, dtype=np.float64)[rows, 0:2]
-        tracking = (np.asarray(rec, dtype=np.float64)[rows, 10:12] * -1.0) * lag
-        p = (ct + tracking.astype(np.float32).astype(np.float64)).astype(np.float32)
-        q = s["ct"].astype(np.float32)
-        dl = lab[rows].astype(np.int32)
+    def _assign(self, p, q, dl, state):
+        """Points 4h-5h: the solver on the reference's matrix; a detection in a match that costs more than 1e16 is parked -- unmatched and numbered last (quirk B)
+        -- and its track is gone (quirk A)."""
+        N, M = len(p), len(state["label"])
         match = np.full(N, -1, dtype=np.int64)                              # the track of a detection's valid match
         parked = np.zeros(N, dtype=bool)                                    # the detection is in a match that costs more than 1e16
         taken = np.zeros(M, dtype=bool)                                     # the track is in a match, valid or not
-        if M:
-            cost, valid = cost_matrix(p, q, dl, s["label"], self.max_diff)
-            di, tj, rounds = solve(cost)
-            out["rounds"] = np.int32(rounds)
-            taken[tj] = True
-            good = cost[di, tj] <= SHOWN_BELOW
-            match[di[good]], parked[di[~good]] = tj[good], True
-            lost = taken.copy()
-            lost[tj[good]] = False                                          # quirk A: the tracks in an invalid match are gone, the young ones too
-            self.seen = dict(cost=cost, valid=valid, pairs={(int(a), int(b)) for a, b in zip(di[good], tj[good])}, N=N, M=M, parked=parked.copy(),
-                             dropped_young=bool((lost & (s["age"] < self.max_age)).any()))
-        hit = match >= 0
-        free = ~hit & ~parked
-        seq = np.concatenate([np.nonzero(hit)[0], np.nonzero(free)[0], np.nonzero(parked)[0]])
-        nu = N - int(hit.sum())
-        ids, act = np.empty(N, np.int32), np.empty(N, np.int32)
-        ids[hit], act[hit] = s["tracking_id"][match[hit]], s["active"][match[hit]] + 1
-        ids[seq[N - nu:]], act[~hit] = s["id_count"] + 1 + np.arange(nu, dtype=np.int32), 1
-        stay = ~taken & (s["age"] < self.max_age)
-        self.state = dict(ct=np.concatenate([ct[seq], s["ct"][stay] + s["tracking"][stay] * -1.0]), tracking=np.concatenate([tracking[seq], s["tracking"][stay]]),
-                          label=np.concatenate([dl[seq], s["label"][stay]]), tracking_id=np.concatenate([ids[seq], s["tracking_id"][stay]]),
-                          age=np.concatenate([np.ones(N, np.int32), s["age"][stay] + 1]), active=np.concatenate([act[seq], np.zeros(int(stay.sum()), np.int32)]),
-                          id_count=int(s["id_count"]) + nu)
-        out["track_id"][rows], out["active"][rows], out["order"][:N] = ids, act, rows[seq]
-        return out
+        if not M:
+            return match, taken, parked, {}
+        cost, valid = cost_matrix(p, q, dl, state["label"], self.max_diff)
+        di, tj, rounds = solve(cost)
+        taken[tj] = True
+        good = cost[di, tj] <= SHOWN_BELOW
+        match[di[good]], parked[di[~good]] = tj[good], True
+        lost = taken.copy()
+        lost[tj[good]] = False                                              # quirk A: the tracks in an invalid match are gone, the young ones too
+        self.seen = dict(cost=cost, valid=valid, pairs={(int(a), int(b)) for a, b in zip(di[good], tj[good])}, N=N, M=M, parked=parked.copy(),
+                         dropped_young=bool((lost & (state["age"] < self.max_age)).any()))
+        return match, taken, parked, dict(rounds=np.int32(rounds))
 
 
 def run_case(c, streams=None, on_step=None):
-    """The restatement over a case -> (outputs [frame][stream], states after [frame][stream]).  ``on_step(f, b, tracker)`` sees the tracker after each step."""
-    B = c["B"]
-    streams = range(B) if streams is None else streams
-    trackers = {b: Tracker(c["max_age"]) for b in streams}
-    if c.get("init") is not None:
-        for b in streams:
-            trackers[b].set_state(c["init"][b], c["init_last"][b])
-    outs, states = [], []
-    for f, fr in enumerate(c["frames"]):
-        outs.append([trackers[b].step(fr["rec"][b], fr["score"][b], fr["name"][b], fr["kept"][b], fr["timestamp"][b], fr["first"][b], c["thr"]) for b in streams])
-        states.append([{k: (v.copy() if hasattr(v, "copy") else v) for k, v in trackers[b].state.items()} for b in streams])
-        if on_step is not None:
-            for b in streams:
-                on_step(f, b, trackers[b])
-    return outs, states
+    return TC.run_case(c, streams, on_step, Tracker)
 
 
 def frame_flags(seen, clean_pairs):
@@ -290,27 +238,9 @@ def pack_expected(prefix, outs, states, rounds, flags, arrays):
     arrays[f"{prefix}/flags"] = np.asarray(flags, dtype=bool)
 
 
-_EXPECTED = {}
-
-
 def expected(name):
     """-> what tracking_cases.expected returns, read from this fixture, with ``rounds`` [F, B] int32 and ``flags`` [F, B, len(FLAGS)] bool."""
-    if name not in _EXPECTED:
-        z = np.load(FIXTURE)
-        e = {k: z[f"{name}/{k}"] for k in ("track_id", "active", "order", "num_out", "count", "id_count", "digest", "rounds", "flags")}
-        e["states"] = None
-        if f"{name}/state_ct" in z.files:
-            F, B = e["count"].shape
-            flat = {k: z[f"{name}/state_{k}"] for k in TC.STATE_KEYS}
-            at, e["states"] = 0, []
-            for f in range(F):
-                e["states"].append([])
-                for b in range(B):
-                    m = int(e["count"][f, b])
-                    e["states"][f].append(dict({k: flat[k][at:at + m] for k in TC.STATE_KEYS}, id_count=int(e["id_count"][f, b])))
-                    at += m
-        _EXPECTED[name] = e
-    return _EXPECTED[name]
+    return TC.expected(name, FIXTURE, ("rounds", "flags"))
 
 
 compare_state = TC.compare_state

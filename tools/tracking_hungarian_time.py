@@ -26,22 +26,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import tracking_cases as TC              # noqa: E402
 import tracking_hungarian_cases as HC    # noqa: E402
-from tools.tracking_time import spread   # noqa: E402
+from tools.tracking_time import K, MAX_AGE, THR, spread, steady   # noqa: E402
 
 DEV = "cuda:0"
-K, MAX_AGE, THR, WARM_FRAMES = 300, 3, 0.25, 5
-FIELDS = (("ct", 16), ("tracking", 16), ("label", 4), ("tracking_id", 4), ("age", 4), ("active", 4))
-
-
-def steady(B, classes, spacing, seed=31):
-    """-> (the Hungarian restatement's trackers after WARM_FRAMES frames, the next frame)."""
-    c = TC.scene_case(seed, K, WARM_FRAMES + 1, 330, MAX_AGE, thr=THR, classes=classes, spacing=spacing, B=B)
-    trackers = [HC.Tracker(MAX_AGE) for _ in range(B)]
-    for fr in c["frames"][:WARM_FRAMES]:
-        for b, t in enumerate(trackers):
-            t.step(fr["rec"][b], fr["score"][b], fr["name"][b], fr["kept"][b], fr["timestamp"][b], fr["first"][b], THR)
-    return trackers, dict(c["frames"][WARM_FRAMES], thr=THR)
-
 
 def main():
     ap = argparse.ArgumentParser()
@@ -74,21 +61,10 @@ def main():
             ts.append(e0.elapsed_time(e1))
         return spread(ts)
 
-    def state_bytes_of(state, last, cap):
-        raw = np.zeros(tracking.state_bytes(cap), dtype=np.uint8)
-        n = len(state["label"])
-        raw[0:8].view(np.int32)[:] = [n, state["id_count"]]
-        raw[8:16].view(np.float64)[0] = last
-        at = 32
-        for k, size in FIELDS:
-            raw[at:at + size * n] = np.ascontiguousarray(state[k], dtype=TC.STATE_DTYPES[k]).reshape(-1).view(np.uint8)
-            at += size * cap
-        return raw
-
     def both(states, lasts, fr, Kc, cap, max_age):
         """The two entry points on the same states and frame, each checked against its restatement -> the record of a configuration."""
         B = len(states)
-        sin = dv(np.stack([state_bytes_of(s, l, cap) for s, l in zip(states, lasts)]))
+        sin = dv(np.stack([TC.state_to_bytes(s, l, cap) for s, l in zip(states, lasts)]))
         sout = torch.zeros_like(sin)
         args = [dv(fr[k]) for k in ("rec", "score", "name", "kept")]
         label, gate, ts, first = dv(TC.track_label_table()), dv(TC.max_diff_table()), dv(fr["timestamp"]), dv(fr["first"])
@@ -120,8 +96,8 @@ def main():
                us_per_round_is="(the Hungarian entry's median - the greedy entry's median on the same state) / the rounds of the stream with the most: the streams of a launch run "
                                "side by side on their own CUs; what the two entries share (launch, filter, state write) cancels, greedy's own matching does not and is small")
     for tag, B, classes, spacing in [(f"B{B}_all_classes", B, TC.ALL_CLASSES, 2.0) for B in (1, 2, 4)] + [("B1_one_label_crowded", 1, (TC.CAR,), 1.0)]:
-        trackers, fr = steady(B, classes, spacing)
-        res["sizes"][tag] = both([t.state for t in trackers], [t.last for t in trackers], fr, K, tracking.capacity_for(K, MAX_AGE), MAX_AGE)
+        _, trackers, fr = steady(B, classes, spacing, tracker=HC.Tracker)
+        res["sizes"][tag] = both([t.state for t in trackers], [t.last for t in trackers], dict(fr, thr=THR), K, tracking.capacity_for(K, MAX_AGE), MAX_AGE)
     c = HC.build_case(HC.CAPS_CASE)
     res["sizes"]["caps_512_rows_2048_tracks_one_label"] = both(c["init"], c["init_last"], dict(c["frames"][0], thr=c["thr"]), c["K"], HC.MAX_TRACKS, c["max_age"])
     c = HC.build_case("n128_m128_one_label")

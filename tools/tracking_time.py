@@ -41,10 +41,10 @@ def spread(ts, digits=4):
     return dict(median_ms=q(0.5), min_ms=round(ts[0], digits), p10_ms=q(0.1), p90_ms=q(0.9), reps=len(ts))
 
 
-def steady(B, classes=TC.ALL_CLASSES, spacing=2.0, seed=31):
-    """-> (case, the restatement's trackers after WARM_FRAMES frames, the next frame)."""
+def steady(B, classes=TC.ALL_CLASSES, spacing=2.0, seed=31, tracker=TC.Tracker):
+    """-> (case, the trackers of the restatement ``tracker`` after WARM_FRAMES frames, the next frame)."""
     c = TC.scene_case(seed, K, WARM_FRAMES + 1, 330, MAX_AGE, thr=THR, classes=classes, spacing=spacing, B=B)
-    trackers = [TC.Tracker(MAX_AGE) for _ in range(B)]
+    trackers = [tracker(MAX_AGE) for _ in range(B)]
     for fr in c["frames"][:WARM_FRAMES]:
         for b, t in enumerate(trackers):
             t.step(fr["rec"][b], fr["score"][b], fr["name"][b], fr["kept"][b], fr["timestamp"][b], fr["first"][b], THR)
@@ -117,22 +117,10 @@ def time_device(a):
             ts.append(e0.elapsed_time(e1))
         return spread(ts)
 
-    def state_bytes_of(t, cap):
-        s = t.state
-        raw = np.zeros(tracking.state_bytes(cap), dtype=np.uint8)
-        n = len(s["label"])
-        raw[0:8].view(np.int32)[:] = [n, s["id_count"]]
-        raw[8:16].view(np.float64)[0] = t.last
-        at = 32
-        for k, size in (("ct", 16), ("tracking", 16), ("label", 4), ("tracking_id", 4), ("age", 4), ("active", 4)):
-            raw[at:at + size * n] = np.ascontiguousarray(s[k], dtype=TC.STATE_DTYPES[k]).reshape(-1).view(np.uint8)
-            at += size * cap
-        return raw
-
     def entry(trackers, fr, Kc, cap):
         """The entry point on the trackers' state and the frame ``fr`` -> (the timed closure, outputs)."""
         B = len(trackers)
-        sin = dv(np.stack([state_bytes_of(t, cap) for t in trackers]))
+        sin = dv(np.stack([TC.state_to_bytes(t.state, t.last, cap) for t in trackers]))
         sout = torch.zeros_like(sin)
         args = [dv(fr[k]) for k in ("rec", "score", "name", "kept")]
         label, gate, ts, first = dv(TC.track_label_table()), dv(TC.max_diff_table()), dv(fr["timestamp"]), dv(fr["first"])
